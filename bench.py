@@ -4,6 +4,10 @@
     python bench.py --gpus N --steps K --warmup W          weak scaling: K frames per GPU
     python bench.py --gpus N --frames F --warmup W         strong scaling: F frames sharded in contiguous blocks of
                                                            ceil(F/N) (BASELINE.json configs[4]: --frames 1024 --gpus 8)
+    ... --full                                             also the legs listed below (roofline, cpu_baseline, parity,
+                                                           latency, sustained, pcie_inclusive_frames_per_s) and the side file
+    ... --dump-outputs DIR                                 after the timed steps: DIR/label_map.npy, the [480, 640] label
+                                                           map of the last timed frame as float32
 
 For N > 1 either launch it under torch.distributed.run (the driver does; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*
 are read from the environment) or call it bare: without WORLD_SIZE in the environment `python bench.py --gpus N`
@@ -21,7 +25,8 @@ the label-map block.  Weights are the calibrated synthetic set (synth.calibrated
 random-init backbone of the reference architecture + closed-form calibration so that synthetic
 frames segment into their objects and stage 2 really runs (K ~ 6-8 ROIs per frame).
 
-Prints ONE JSON line (rank 0).  Besides the contract fields:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the contract fields (the
+other blocks are null).  With --full, besides the contract fields:
   roofline      the kernel class with the largest share of GPU time in a profiled pass over the same frames (HIP
                 events on the launch stream, csrc/prof.hip)
   cpu_baseline  the CPU oracle (torch-CPU restatement of the reference path) on the FIRST frames of the timed set,
@@ -118,8 +123,10 @@ def cpu_baseline(frames, out_path):
         ncpu = os.cpu_count() or 1
     # The oracle is many small torch ops; beyond ~64 threads the intra-op pool only adds synchronisation cost (with
     # all 256+ hardware threads of the bench box a frame took minutes instead of seconds), so the thread count is
-    # capped at 64 and both numbers are reported: `cores` = threads used, `host_cores` = what the box has.
-    torch.set_num_threads(max(1, min(ncpu, 64)))
+    # capped at 64 and both numbers are reported: `cores` = threads used, `host_cores` = what the box has.  A job given
+    # fewer cores than the box has says so through OMP_NUM_THREADS, which then caps the count as well.
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    torch.set_num_threads(max(1, min(ncpu, 64, int(omp) if omp.isdigit() and int(omp) > 0 else 64)))
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.calibrated_state_dict().items()}
     captured = []
 
@@ -645,15 +652,20 @@ def _main():
     ap.add_argument("--frames", type=int, default=0,
                     help="strong scaling: this many frames in total, sharded in contiguous blocks over the GPUs")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--cpu-frames", type=int, default=3, help="frames for the CPU baseline + parity (0 = skip)")
-    ap.add_argument("--profile-steps", type=int, default=4, help="launch sets in the profiled pass (0 = skip)")
-    ap.add_argument("--sustained-seconds", type=float, default=10.0, help="sustained leg at N=1 (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: PCIe-inclusive, latency, sustained, profiled passes "
+                         "(roofline, kernel shares), CPU baseline + parity, and write the side file with the full record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the label map of the last timed frame to DIR/label_map.npy (float32)")
+    ap.add_argument("--cpu-frames", type=int, default=3, help="with --full: frames for the CPU baseline + parity (0 = skip)")
+    ap.add_argument("--profile-steps", type=int, default=4, help="with --full: launch sets in the profiled pass (0 = skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=10.0, help="with --full: sustained leg at N=1 (0 = skip)")
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("UOC_FRAMES_IN_FLIGHT", "3")),
                     help="streams per GPU, each working on one launch set of --frames-per-launch frames (runner._run_block_pipelined)")
     ap.add_argument("--frames-per-launch", type=int, default=int(os.environ.get("UOC_FRAMES_PER_LAUNCH", "4")),
                     help="frames batched into one set of launches per stage (fcn.test_dataset.FrameGroupJob)")
-    ap.add_argument("--skip-pcie", action="store_true", help="skip the PCIe-inclusive leg (profiling runs)")
-    ap.add_argument("--skip-latency", action="store_true", help="skip the one-frame-at-a-time latency leg (profiling runs)")
+    ap.add_argument("--skip-pcie", action="store_true", help="with --full: skip the PCIe-inclusive leg (profiling runs)")
+    ap.add_argument("--skip-latency", action="store_true", help="with --full: skip the one-frame-at-a-time latency leg (profiling runs)")
     ap.add_argument("--cpu-baseline-only", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-out", default="", help=argparse.SUPPRESS)
     ap.add_argument("--split-precision", action="store_true",
@@ -813,9 +825,15 @@ def _main():
     objects = float(np.mean([int(m.max()) for m in maps[:total]]))
     counts = frame_fn.roi_counts[-(hi - lo):] if frame_fn.roi_counts else []
     rois = float(np.mean(counts)) if counts else 0.0
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives for its last step: the label map of the last frame (rank 0 holds the
+        # gathered block), as float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "label_map.npy"), maps[total - 1].numpy().astype(np.float32))
     STATE["stage"] = "report"
-    solo = rank == 0 and world == 1 and not stub
-    lead = rank == 0 and not stub       # round 6: rank 0 also fills roofline / cpu_baseline / parity of a multi-GPU run (after the gather)
+    # every leg below the timed region runs only with --full: a plain run reports the headline figure alone
+    solo = rank == 0 and world == 1 and not stub and args.full
+    lead = rank == 0 and not stub and args.full       # rank 0 also fills roofline / cpu_baseline / parity of a multi-GPU run (after the gather)
 
     pcie = None
     if solo and not args.skip_pcie:
@@ -1040,7 +1058,7 @@ def _main():
     if use_dist:
         dist.destroy_process_group()
     if line is not None:
-        full_path = write_full_record(line)
+        full_path = write_full_record(line) if args.full else None
         out = compact_line(line, full_path)
         # last thing on stdout (RCCL writes a "Librccl path" banner to stdout while the process group is alive)
         sys.stdout.flush()

@@ -7,7 +7,7 @@ cd $R
 i=0
 for arm in "$@"; do i=$((i+1))
   [ "$arm" = "-" ] && arm=""
-  env $arm UOC_BENCH_FULL=$O/$i.json timeout 300 python bench.py --steps 64 --warmup 4 --cpu-frames 0 --profile-steps 2 --sustained-seconds 6 --skip-pcie --skip-latency > $O/$i.line 2> $O/$i.err
+  env $arm UOC_BENCH_FULL=$O/$i.json timeout 300 python bench.py --full --steps 64 --warmup 4 --cpu-frames 0 --profile-steps 2 --sustained-seconds 6 --skip-pcie --skip-latency > $O/$i.line 2> $O/$i.err
   python - "$O/$i.json" "$arm" <<'PY'
 import json, sys
 try:

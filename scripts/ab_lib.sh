@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/ab_lib; mkdir -p $O
 reps=$1; shift
 for i in $(seq 1 $reps); do n=0
   for lib in "$@"; do n=$((n+1)); [ "$lib" = "-" ] && a="A=1" || a="UOC_LIB_PATH=$R/$lib"
-    env $a UOC_BENCH_FULL=$O/$n.full.json timeout 300 python bench.py --steps 20 --warmup 5 --cpu-frames 0 --profile-steps 0 --sustained-seconds 4 --skip-pcie > $O/$n.json 2> $O/$n.err
+    env $a UOC_BENCH_FULL=$O/$n.full.json timeout 300 python bench.py --full --steps 20 --warmup 5 --cpu-frames 0 --profile-steps 0 --sustained-seconds 4 --skip-pcie > $O/$n.json 2> $O/$n.err
     python - $O/$n.json "$lib" <<'PY'
 import json, sys
 try:

@@ -5,7 +5,8 @@ R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/ab_r05; mkdir -p $O
 reps=${1:-2}
 run() { # tag dir env...
   tag=$1; dir=$2; shift 2
-  ( cd $dir && env "$@" UOC_BENCH_FULL=$O/$tag.full.json timeout 300 python bench.py --steps 20 --warmup 5 --cpu-frames 0 --profile-steps 0 --sustained-seconds 4 --skip-pcie > $O/$tag.json 2> $O/$tag.err )
+  full=; [ "$dir" = "$R" ] && full=--full     # the older tree's bench.py runs every leg by default and has no --full
+  ( cd $dir && env "$@" UOC_BENCH_FULL=$O/$tag.full.json timeout 300 python bench.py $full --steps 20 --warmup 5 --cpu-frames 0 --profile-steps 0 --sustained-seconds 4 --skip-pcie > $O/$tag.json 2> $O/$tag.err )
   python - $O/$tag.json $tag <<'PY'
 import json, sys
 try:

@@ -9,9 +9,9 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$1; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export UOC_CONV_TUNE_CACHE=/tmp/uoc_tune_$1.txt
 QUIET="--cpu-frames 0 --sustained-seconds 0 --skip-pcie --skip-latency"
-UOC_BENCH_FULL=$O/bench_full.json timeout 600 python $R/bench.py > $O/bench.json 2> $O/bench.err
+UOC_BENCH_FULL=$O/bench_full.json timeout 600 python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 export UOC_BENCH_FULL=$O/bench_scratch.json
-timeout 300 rocprofv3 --kernel-trace -d $O/trace_seq -o t -- python $R/bench.py --steps 12 --warmup 4 --inflight 1 $QUIET > $O/bench_seq_under_rocprof.json 2> $O/trace_seq.err
+timeout 300 rocprofv3 --kernel-trace -d $O/trace_seq -o t -- python $R/bench.py --full --steps 12 --warmup 4 --inflight 1 $QUIET > $O/bench_seq_under_rocprof.json 2> $O/trace_seq.err
 timeout 300 rocprofv3 --kernel-trace -d $O/trace_pipe -o t -- python $R/bench.py --steps 24 --warmup 3 $QUIET --profile-steps 0 > $O/bench_pipe_under_rocprof.json 2> $O/trace_pipe.err
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o f -- python $R/bench.py --steps 8 --warmup 4 --inflight 1 $QUIET --profile-steps 0 > /dev/null 2> $O/fetch.err
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o w -- python $R/bench.py --steps 8 --warmup 4 --inflight 1 $QUIET --profile-steps 0 > /dev/null 2> $O/write.err

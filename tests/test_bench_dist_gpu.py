@@ -22,19 +22,25 @@ def _bench(tmp_path, tag, force, steps=4):
         env["UOC_BENCH_FORCE_DIST"] = "1"
     else:
         env.pop("UOC_BENCH_FORCE_DIST", None)
+    outputs = os.path.join(str(tmp_path), tag + "_outputs")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
-                        "--cpu-frames", "0", "--profile-steps", "0", "--sustained-seconds", "0"], env=env,
+                        "--cpu-frames", "0", "--profile-steps", "0", "--sustained-seconds", "0", "--dump-outputs", outputs], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(line) == 1 and len(line[0]) < 3000
-    return json.loads(line[0]), np.load(dump)
+    block = np.load(dump)
+    last = np.load(os.path.join(outputs, "label_map.npy"))       # --dump-outputs: the last timed frame's label map
+    assert last.dtype == np.float32 and np.array_equal(last, block[-1].astype(np.float32))
+    return json.loads(line[0]), block
 
 
 def test_forced_collective_block_equals_plain_block(tmp_path, device):
     plain, a = _bench(tmp_path, "plain", False)
     coll, b = _bench(tmp_path, "coll", True)
     assert plain["config"]["collective"] is False and coll["config"]["collective"] is True
+    # a plain run (no --full) measures the headline figure only
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["latency"] is None and plain["full"] is None
     assert a.shape == b.shape == (4, 480, 640) and a.dtype == np.uint8
     assert np.array_equal(a, b), "all-gathered label-map block differs from the local block"
     assert int(a.max()) >= 5, "frames must segment into their objects"
@@ -99,7 +105,7 @@ def test_a_multi_rank_record_carries_roofline_cpu_baseline_and_parity(tmp_path, 
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "UOC_BENCH_FORCE_DIST"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "16", "--warmup", "1",
-                        "--cpu-frames", "1", "--profile-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-frames", "1", "--profile-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(line) == 1 and len(line[0]) < 3000

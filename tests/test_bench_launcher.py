@@ -42,6 +42,32 @@ def test_self_launch_two_ranks_matches_single_process(tmp_path, mode):
     assert len(two["per_rank"]) == 2 and all("gather_s" in r and "compute_s" in r for r in two["per_rank"])
 
 
+def test_dump_outputs_and_full_side_file(tmp_path):
+    """--dump-outputs DIR writes the last timed frame's label map as float32, the same on every run with the same arguments
+    (and the same at world size 2); a plain run writes no side file, --full does."""
+    maps = {}
+    for tag, flags in (("a", ()), ("b", ()), ("two", ("--gpus", "2")), ("full", ("--full",))):
+        out_dir = os.path.join(str(tmp_path), tag + "_outputs")
+        side = os.path.join(str(tmp_path), tag + "_full.json")
+        env = dict(os.environ, UOC_BENCH_DUMP=os.path.join(str(tmp_path), tag + ".npy"), UOC_BENCH_FULL=side)
+        for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+            env.pop(k, None)
+        args = ["--steps", "3", "--warmup", "1", "--dump-outputs", out_dir] if tag != "two" else \
+            ["--frames", "3", "--warmup", "1", "--dump-outputs", out_dir]
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", *flags, *args], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        last = np.load(os.path.join(out_dir, "label_map.npy"))
+        block = np.load(env["UOC_BENCH_DUMP"])
+        assert last.dtype == np.float32 and last.shape == block.shape[1:] and np.array_equal(last, block[-1])
+        maps[tag] = last
+        if tag != "two":
+            assert d["steps"] == 3 and block.shape[0] == 3 and d["ms_per_step"] > 0
+        assert (d["full"] is not None) == os.path.exists(side) == (tag == "full")
+    assert np.array_equal(maps["a"], maps["b"]) and np.array_equal(maps["a"], maps["two"]) and np.array_equal(maps["a"], maps["full"])
+
+
 def test_wrong_world_size_is_refused(tmp_path):
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--gpus", "1"], env=env,

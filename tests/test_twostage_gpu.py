@@ -153,12 +153,12 @@ def test_many_rois_vs_oracle(device):
 
 
 def test_bench_json_contract(device):
-    """bench.py prints ONE JSON line with the driver's keys plus the roofline / cpu_baseline objects."""
+    """bench.py --full prints ONE JSON line with the driver's keys plus the roofline / cpu_baseline objects."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-frames", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--cpu-frames", "1",
                           "--profile-steps", "1"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
