@@ -261,6 +261,45 @@ int uoc_eval_pair_stats(const int32_t *d_pred, const int32_t *d_gt, int H, int W
 
 
 /* ------------------------------------------------------------------------------------------
+ * Per-object point clouds and 3D statistics from label maps (no reference counterpart: the step every consumer of
+ * the label map takes next).  A pixel of object l has label l in [1, 127]; other ids, negative ones included, are
+ * background.  A valid point is a pixel of an object whose x, y, z are finite and whose z > 0.
+ * One record per (frame, id), all 128 ids; id 0 and absent ids are all zeros (box -1).  Float fields are 0 when
+ * count == 0.  Sums run in fp64 in a fixed order: every output is bitwise reproducible, and frame b's outputs do not
+ * depend on the other frames of the batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_OBJECTS_MAX_ATTR 8
+typedef struct uoc_object {
+  int32_t pixels;         /* pixels with the id                                                                  */
+  int32_t count;          /* valid points                                                                        */
+  int32_t box[4];         /* pixel box x0, y0, x1, y1 inclusive over the id's pixels; -1 when pixels == 0       */
+  float centroid[3];      /* mean of the valid points                                                            */
+  float cov[6];           /* population covariance (1/n) sum (p-c)(p-c)^T: xx, xy, xz, yy, yz, zz               */
+  float aabb_min[3];
+  float aabb_max[3];
+  float eig[3];           /* eigenvalues of cov, descending                                                      */
+  float axes[9];          /* row-major 3x3, column k = unit eigenvector e_k; e0, e1 have their largest-magnitude
+                             component positive (ties: lowest index), e2 = e0 x e1                                 */
+  float obb_center[3];    /* c + sum_k e_k (min d_k + max d_k) / 2,  d_k = (p - c) . e_k over the valid points     */
+  float obb_half[3];      /* (max d_k - min d_k) / 2                                                             */
+  int32_t offset;         /* first row of the object's points in the packed cloud                                */
+  int32_t kept;           /* rows of the object in the packed cloud                                              */
+} uoc_object;
+
+size_t uoc_objects_workspace_bytes(int B, int H, int W);
+/* d_labels [B][H][W] int32, d_xyz [B][3][H][W] fp32 metres, d_attr (nullable) [B][attr_ch][H][W] fp32 with
+ * attr_ch <= UOC_OBJECTS_MAX_ATTR.  d_objects [B][128].
+ * Packed cloud (d_points == NULL: records only): rows ordered by frame, id, raster index y*W + x; d_points [P][3],
+ * d_point_attr (nullable) [P][attr_ch], d_point_pixel (nullable) [P] raster index within the frame.  With
+ * max_points_per_object = M > 0 an object of count > M keeps the points of in-object rank floor(j*count/M),
+ * j = 0..M-1 (64-bit arithmetic); M <= 0 keeps all.  *d_total receives P; no row at or past `capacity` is written
+ * (capacity B*H*W always suffices). */
+int uoc_objects(const int32_t *d_labels, const float *d_xyz, const float *d_attr, int attr_ch, int B, int H, int W,
+                int max_points_per_object, uoc_object *d_objects, float *d_points, float *d_point_attr,
+                int32_t *d_point_pixel, long capacity, int32_t *d_total, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

@@ -1,0 +1,75 @@
+#!/usr/bin/env python
+"""Per-object point clouds and 3D boxes for a directory of RGB-D frames: the two-stage segmentation of
+tools/test_images.py, then extract_objects on the device (unseenobjectclustering_amd/objects.py).
+
+    python tools/export_objects.py --imgdir tests/golden/demo --out objs/ [--max-points 2048]
+                                   [--pretrained ckpt.pth --pretrained_crop crop.pth] [--cfg experiments/cfgs/<experiment>.yml]
+
+Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
+`label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
+`obb_half`) and the packed clouds (`points`, `pixel_index`, `offsets`: object k is points[offsets[k]:offsets[k+1]]).
+Without checkpoints the calibrated synthetic weights are used (test_images.load_weights).
+"""
+import argparse
+import glob
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from test_images import load_weights  # noqa: E402
+from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
+from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
+from unseenobjectclustering_amd.objects import segment_objects  # noqa: E402
+
+FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
+          "obb_center", "obb_half", "offsets", "points", "pixel_index")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--imgdir", required=True)
+    ap.add_argument("--color", default="*-color.png")
+    ap.add_argument("--depth", default="*-depth.png")
+    ap.add_argument("--pretrained", default=None)
+    ap.add_argument("--pretrained_crop", default=None)
+    ap.add_argument("--cfg", dest="cfg_file", default=None, help="experiment yml")
+    ap.add_argument("--out", required=True, help="output directory for <frame>_objects.npz")
+    ap.add_argument("--max-points", type=int, default=0, help="points kept per object (0 = all)")
+    args = ap.parse_args()
+    if args.cfg_file is not None:
+        cfg_from_file(args.cfg_file)
+    if network_mode() != "RGBD_ADD":
+        raise SystemExit("export_objects needs an RGB-D network (the objects are cut from the XYZ planes)")
+    np.random.seed(cfg.RNG_SEED)
+    cfg.gpu_id = args.gpu
+    cfg.device = torch.device("cuda:%d" % args.gpu)
+    colors = sorted(glob.glob(os.path.join(args.imgdir, args.color)))
+    depths = sorted(glob.glob(os.path.join(args.imgdir, args.depth)))
+    assert len(colors) == len(depths) and colors, "need matching colour/depth images"
+    cam_file = os.path.join(args.imgdir, "camera_params.json")
+    cam = json.load(open(cam_file)) if os.path.exists(cam_file) else dict(synth.DEMO_CAMERA)
+    network = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained)).eval()
+    network_crop = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained_crop)).eval()
+    os.makedirs(args.out, exist_ok=True)
+    for fc, fd in zip(colors, depths):
+        sample = uio.read_sample(fc, fd, cam)
+        out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
+        final = out_refined if out_refined is not None else out_label
+        rec = {k: getattr(objs, k).cpu().numpy() for k in FIELDS}
+        rec["label_map"] = final[0].numpy().astype(np.int32)
+        stem = os.path.basename(fc)
+        stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
+        name = os.path.join(args.out, stem + "_objects.npz")
+        np.savez(name, **rec)
+        print("save objects to {}  ({} objects, {} points)".format(name, len(objs), int(objs.points.shape[0])))
+
+
+if __name__ == "__main__":
+    main()

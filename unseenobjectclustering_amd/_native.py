@@ -82,6 +82,10 @@ def _declare(lib):
     lib.uoc_roi_match.argtypes = [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]
     for name in ("uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats", "uoc_roi_paste", "uoc_labels_to_u8", "uoc_roi_match"):
         getattr(lib, name).restype = c_int
+    lib.uoc_objects_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.uoc_objects_workspace_bytes.restype = c_size_t
+    lib.uoc_objects.argtypes = [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, ctypes.c_long, P, P, c_size_t, P]
+    lib.uoc_objects.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -102,7 +106,7 @@ EXPORTED_SYMBOLS = (
     "uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_workspace_bytes",
     "uoc_net_forward", "uoc_net_set_split_precision", "uoc_conv2d_nhwc", "uoc_conv2d_nhwc_algo",
     "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
-    "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -112,6 +116,17 @@ class RoiTable(ctypes.Structure):
 
 
 ROI_TABLE_BYTES = ctypes.sizeof(RoiTable)
+
+
+class UocObject(ctypes.Structure):
+    """Mirror of uoc_object (include/uoc_hip.h): one per (frame, id)."""
+    _fields_ = [("pixels", c_int32), ("count", c_int32), ("box", c_int32 * 4), ("centroid", c_float * 3), ("cov", c_float * 6),
+                ("aabb_min", c_float * 3), ("aabb_max", c_float * 3), ("eig", c_float * 3), ("axes", c_float * 9),
+                ("obb_center", c_float * 3), ("obb_half", c_float * 3), ("offset", c_int32), ("kept", c_int32)]
+
+
+OBJECT_BYTES = ctypes.sizeof(UocObject)
+OBJECTS_MAX_ATTR = 8        # include/uoc_hip.h: UOC_OBJECTS_MAX_ATTR
 
 
 def lib():

@@ -1,0 +1,171 @@
+"""Per-object point clouds and 3D statistics from label maps, on the device (uoc_objects, include/uoc_hip.h).
+
+    objs = extract_objects(labels, xyz)               # labels [B,H,W] / [H,W] on the GPU, xyz = sample['depth'] [B,3,H,W]
+    objs.centroid[k], objs.obb_center[k], objs.cloud(k)
+
+A pixel of object l has label l in [1, 127]; a valid point is such a pixel with finite x, y, z and z > 0.  The records
+and the packed clouds are computed by HIP kernels in a fixed summation order (bitwise reproducible, independent of the
+batch); the only host traffic is one small read of the per-object counts that sizes the result.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _native
+
+NUM_IDS = 128
+_W = _native.OBJECT_BYTES // 4          # 4-byte words per record
+_F = {name: (getattr(_native.UocObject, name).offset // 4, getattr(_native.UocObject, name).size // 4)
+      for name, _ in _native.UocObject._fields_}
+_COV_INDEX = [0, 1, 2, 1, 3, 4, 2, 4, 5]   # xx, xy, xz, yy, yz, zz -> 3x3
+
+
+class ObjectSet:
+    """Objects of the (frame, id) pairs with pixels > 0 and count >= min_points, in ascending (frame, id) order.
+    Every tensor lives on the device of the inputs; K = len(self).
+
+    frame, label, pixels, count [K] int32; box [K,4] int32 (x0, y0, x1, y1 inclusive); centroid, aabb_min, aabb_max,
+    eigenvalues (descending), obb_center, obb_half [K,3]; cov, axes [K,3,3] (column k of axes = e_k);
+    points [P,3]; pixel_index [P] int32 (raster index y*W + x in its frame); attrs [P,C] or None; offsets [K+1] int64:
+    the rows of object k are points[offsets[k]:offsets[k+1]]."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __len__(self):
+        return int(self.frame.shape[0])
+
+    def cloud(self, k):
+        """Points of object k, [n,3]."""
+        return self.points[self._offsets_host[k]:self._offsets_host[k + 1]]
+
+
+def _device_tensor(t, what):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise _native.NativeError(f"extract_objects: {what} must be a tensor on the GPU (there is no CPU fallback)")
+    return t
+
+
+def _workspace(dev, nbytes):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def object_records(labels, xyz, attrs=None, max_points_per_object=None, capacity=None, want_points=True):
+    """The raw uoc_objects call: (records [B,128,41] int32 holding uoc_object, points [cap,3], point_attr [cap,C] or None,
+    pixel_index [cap], total [1] int32), all on the device, no synchronisation.  labels int32 [B,H,W] and xyz float32
+    [B,3,H,W] contiguous on one GPU; capacity defaults to B*H*W (always enough)."""
+    B, H, W = labels.shape
+    dev = labels.device
+    C = 0 if attrs is None else int(attrs.shape[1])
+    lib = _native.lib()
+    cap = B * H * W if capacity is None else int(capacity)
+    rec = torch.empty((B, NUM_IDS, _W), dtype=torch.int32, device=dev)
+    pts = torch.empty((cap, 3), dtype=torch.float32, device=dev) if want_points else None
+    pat = torch.empty((cap, C), dtype=torch.float32, device=dev) if (want_points and C) else None
+    pix = torch.empty((cap,), dtype=torch.int32, device=dev) if want_points else None
+    total = torch.empty((1,), dtype=torch.int32, device=dev)
+    nws = lib.uoc_objects_workspace_bytes(B, H, W)
+    ws = _workspace(dev, nws)
+    M = 0 if max_points_per_object is None else int(max_points_per_object)
+    with torch.cuda.device(dev):
+        rc = lib.uoc_objects(_native.ptr(labels), _native.ptr(xyz), _native.ptr(attrs), C, B, H, W, M, _native.ptr(rec),
+                             _native.ptr(pts), _native.ptr(pat), _native.ptr(pix), ctypes.c_long(cap), _native.ptr(total),
+                             _native.ptr(ws), nws, _native.stream_ptr(dev))
+    _native.check(rc, "uoc_objects")
+    return rec, pts, pat, pix, total
+
+
+def _field(rec, name, dtype=torch.float32):
+    o, n = _F[name]
+    v = rec[..., o:o + n]
+    return v.view(torch.float32) if dtype == torch.float32 else v
+
+
+def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_points=1) -> ObjectSet:
+    """labels: device tensor [B,H,W] or [H,W] of int32 / int64 / float ids (test_sample's maps are float32);
+    xyz: [B,3,H,W] or [3,H,W] float metres (sample['depth']); attrs: optional [B,C,H,W] / [C,H,W], C <= 8, gathered
+    verbatim per point.  max_points_per_object = M keeps the points of in-object rank floor(j*count/M), j < M, of an
+    object with count > M.  Objects with pixels > 0 and count >= min_points are returned."""
+    _device_tensor(labels, "labels")
+    _device_tensor(xyz, "xyz")
+    if labels.dim() == 2:
+        labels = labels[None]
+    if xyz.dim() == 3:
+        xyz = xyz[None]
+    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
+            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
+        raise _native.NativeError(f"extract_objects: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
+                                  "([B,H,W] and [B,3,H,W])")
+    dev = labels.device
+    if xyz.device != dev:
+        raise _native.NativeError("extract_objects: labels and xyz are on different devices")
+    lab = labels if labels.dtype == torch.int32 else labels.to(torch.int32)
+    lab = lab.contiguous()
+    xyz = xyz.to(torch.float32).contiguous()
+    if attrs is not None:
+        _device_tensor(attrs, "attrs")
+        if attrs.dim() == 3:
+            attrs = attrs[None]
+        if attrs.dim() != 4 or attrs.shape[0] != lab.shape[0] or tuple(attrs.shape[2:]) != tuple(lab.shape[1:]) \
+                or not 1 <= attrs.shape[1] <= _native.OBJECTS_MAX_ATTR or attrs.device != dev:
+            raise _native.NativeError(f"extract_objects: attrs {tuple(attrs.shape)} must be [B,C,H,W] with 1 <= C <= 8")
+        attrs = attrs.to(torch.float32).contiguous()
+    rec, pts, pat, pix, total = object_records(lab, xyz, attrs, max_points_per_object)
+
+    head = torch.cat([_field(rec, "pixels", torch.int32), _field(rec, "count", torch.int32), _field(rec, "offset", torch.int32),
+                      _field(rec, "kept", torch.int32)], dim=-1).reshape(-1, 4).cpu()       # the one D2H read
+    keep = (head[:, 0] > 0) & (head[:, 1] >= min_points)
+    sel = torch.nonzero(keep).reshape(-1)
+    kept = head[sel, 3].to(torch.int64)
+    offsets_host = [0] + torch.cumsum(kept, 0).tolist()
+    n_out = offsets_host[-1]
+    starts = head[sel, 2].to(torch.int64)
+    sel_d = sel.to(dev)
+    flat = rec.reshape(-1, _W)[sel_d]
+    if n_out == int(head[:, 3].sum()):          # every kept row belongs to a returned object: already packed in order
+        rows = None
+    else:
+        base = starts - torch.tensor(offsets_host[:-1], dtype=torch.int64)
+        rows = (torch.repeat_interleave(base, kept) + torch.arange(n_out, dtype=torch.int64)).to(dev)
+
+    def take(t):
+        if t is None:
+            return None
+        return t[:n_out] if rows is None else t[rows]
+
+    K = int(sel.numel())
+    return ObjectSet(
+        frame=(sel_d // NUM_IDS).to(torch.int32), label=(sel_d % NUM_IDS).to(torch.int32),
+        pixels=_field(flat, "pixels", torch.int32)[:, 0].clone(), count=_field(flat, "count", torch.int32)[:, 0].clone(),
+        box=_field(flat, "box", torch.int32).clone(), centroid=_field(flat, "centroid").clone(),
+        cov=_field(flat, "cov")[:, _COV_INDEX].reshape(K, 3, 3), aabb_min=_field(flat, "aabb_min").clone(),
+        aabb_max=_field(flat, "aabb_max").clone(), eigenvalues=_field(flat, "eig").clone(),
+        axes=_field(flat, "axes").reshape(K, 3, 3).clone(), obb_center=_field(flat, "obb_center").clone(),
+        obb_half=_field(flat, "obb_half").clone(), points=take(pts), attrs=take(pat), pixel_index=take(pix),
+        offsets=torch.tensor(offsets_host, dtype=torch.int64, device=dev), _offsets_host=offsets_host,
+        image_size=(int(lab.shape[1]), int(lab.shape[2])))
+
+
+def segment_objects(sample, network, network_crop, use_refined=True, **kw):
+    """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
+    refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
+    maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
+    host), copied only after the extraction was enqueued.  kw goes to extract_objects."""
+    from . import io as uio
+    from .fcn import test_dataset as TD
+    dev = TD._device()
+    if "depth" not in sample and "depth_u16" in sample:       # raw sample (io.read_sample_raw): prepare it on the device
+        sample = uio.prepare_on_device(sample, dev)
+    if sample.get("depth") is None:
+        raise _native.NativeError("segment_objects needs the XYZ planes (sample['depth'])")
+    labels, refined = TD._run_frame(sample, network, network_crop, TD.DEPTH_FILTER, return_device=True, checked=True)
+    xyz = sample["depth"].to(dev)
+    if use_refined and refined is not None:
+        objs = extract_objects(refined[:1], xyz[:1], **kw)
+    else:
+        objs = extract_objects(labels, xyz, **kw)
+    out_label = labels.float().cpu()
+    out_refined = refined.float().cpu() if refined is not None else None
+    return out_label, out_refined, objs
