@@ -33,6 +33,8 @@ extern "C" {
 
 #define UOC_EMBED_DIM 64   /* channel count C the kernels are specialised for */
 #define UOC_MAX_SEEDS 128  /* num_seeds upper bound (reference default 100)   */
+#define UOC_METRIC_COSINE 0     /* embedding metric of the *_ex clustering calls: cfg.TRAIN.EMBEDDING_METRIC 'cosine' */
+#define UOC_METRIC_EUCLIDEAN 1  /* ... and 'euclidean' (the reference's code default)                                */
 
 int uoc_version(void);
 /* Always 0 since round 6: every kernel choice that affects rounding is a compile-time constant and the library holds one
@@ -50,7 +52,7 @@ const char *uoc_last_error(void);
 int uoc_reload_env(void);
 
 /* ------------------------------------------------------------------------------------------
- * Mean-shift clustering  — replaces lib/utils/mean_shift.py:128-229 (cosine metric)
+ * Mean-shift clustering  — replaces lib/utils/mean_shift.py:128-229 (cosine metric; the *_ex calls below also euclidean)
  * ---------------------------------------------------------------------------------------- */
 
 /* Seed selection runs as ONE persistent cooperative launch with X resident on chip when the batch
@@ -116,6 +118,30 @@ size_t uoc_ms_workspace_bytes_wide(int batch, int n, int m, int halves);
 int uoc_ms_cluster_wide(const float *d_X, int halves, int batch, int n, int m, float kappa, int iters, float epsilon,
                         const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
                         int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream);
+
+/* The calls above with the embedding metric as an argument (the reference's metric=, mean_shift.py): UOC_METRIC_COSINE
+ * is exactly the call without _ex; UOC_METRIC_EUCLIDEAN clusters with
+ *   seed selection  d = ||x - s||_2                                 (farthest point, first index on ties)
+ *   hill climbing   W = exp(-kappa ||z - x||^2), Z = W X / max(rowsum(W), 1)   (no renormalisation)
+ *   seed components ||z_j - z_i||_2 <= epsilon
+ *   assignment      argmin ||x - z||_2                               (first index on ties)
+ * Any other metric returns UOC_EINVAL (uoc_last_error says why) and launches nothing.  Same workspace, determinism and
+ * batch independence as the cosine calls. */
+int uoc_ms_select_seeds_ex(const float *d_X, int batch, int n, int m, int num_init, const int32_t *d_first_index,
+                           float *d_seeds, int32_t *d_indices, int metric, void *d_ws, size_t ws_bytes, void *stream);
+int uoc_ms_hill_climb_ex(const float *d_X, int batch, int n, float *d_Z, int m, float kappa, int iters, int metric,
+                         void *d_ws, size_t ws_bytes, void *stream);
+int uoc_ms_seed_components_ex(const float *d_Z, int batch, int m, float epsilon, int metric, int32_t *d_seed_labels,
+                              int32_t *d_num_unique, void *stream);
+int uoc_ms_assign_ex(const float *d_X, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
+                     const int32_t *d_num_unique, int m, int metric, int32_t *d_labels, int32_t *d_closest, void *d_ws,
+                     size_t ws_bytes, void *stream);
+int uoc_ms_cluster_ex(const float *d_X, int batch, int n, int m, float kappa, int iters, float epsilon, int metric,
+                      const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
+                      int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream);
+int uoc_ms_cluster_wide_ex(const float *d_X, int halves, int batch, int n, int m, float kappa, int iters, float epsilon,
+                           int metric, const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
+                           int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream);
 
 
 /* ------------------------------------------------------------------------------------------

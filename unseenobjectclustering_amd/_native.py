@@ -47,6 +47,16 @@ def _declare(lib):
     lib.uoc_ms_workspace_bytes_wide.argtypes = [c_int, c_int, c_int, c_int]
     lib.uoc_ms_cluster_wide.argtypes = [P, c_int, c_int, c_int, c_int, c_float, c_int, c_float, P, P, P, P, P, P, c_size_t, P]
     lib.uoc_ms_cluster_wide.restype = c_int
+    # the same calls with the embedding metric (METRIC_COSINE / METRIC_EUCLIDEAN) as an argument
+    lib.uoc_ms_select_seeds_ex.argtypes = [P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, c_size_t, P]
+    lib.uoc_ms_hill_climb_ex.argtypes = [P, c_int, c_int, P, c_int, c_float, c_int, c_int, P, c_size_t, P]
+    lib.uoc_ms_seed_components_ex.argtypes = [P, c_int, c_int, c_float, c_int, P, P, P]
+    lib.uoc_ms_assign_ex.argtypes = [P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, c_size_t, P]
+    lib.uoc_ms_cluster_ex.argtypes = [P, c_int, c_int, c_int, c_float, c_int, c_float, c_int, P, P, P, P, P, P, c_size_t, P]
+    lib.uoc_ms_cluster_wide_ex.argtypes = [P, c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_int, P, P, P, P, P, P,
+                                           c_size_t, P]
+    for name in METRIC_SYMBOLS:
+        getattr(lib, name).restype = c_int
     lib.uoc_net_embed_dim.argtypes = [P]
     lib.uoc_net_embed_dim.restype = c_int
     lib.uoc_net_create.argtypes = [POINTER(P)]
@@ -98,10 +108,26 @@ def _declare(lib):
         getattr(lib, name).restype = c_int
 
 
+# include/uoc_hip.h: UOC_METRIC_COSINE / UOC_METRIC_EUCLIDEAN, the metric argument of the *_ex clustering calls
+METRIC_COSINE = 0
+METRIC_EUCLIDEAN = 1
+METRICS = {"cosine": METRIC_COSINE, "euclidean": METRIC_EUCLIDEAN}
+METRIC_SYMBOLS = ("uoc_ms_select_seeds_ex", "uoc_ms_hill_climb_ex", "uoc_ms_seed_components_ex", "uoc_ms_assign_ex",
+                  "uoc_ms_cluster_ex", "uoc_ms_cluster_wide_ex")
+
+
+def metric_code(metric) -> int:
+    """cfg.TRAIN.EMBEDDING_METRIC / the reference's metric= string -> the C ABI's metric argument."""
+    if metric not in METRICS:
+        raise NotImplementedError(f"metric={metric!r}: only 'cosine' and 'euclidean' are implemented on gfx950")
+    return METRICS[metric]
+
+
 # every symbol include/uoc_hip.h declares (tests check the .so exports them all)
 EXPORTED_SYMBOLS = (
     "uoc_version", "uoc_is_dev_build", "uoc_config_fingerprint", "uoc_shutdown", "uoc_last_error", "uoc_reload_env", "uoc_ms_set_persistent_fps", "uoc_ms_set_stream_ordering", "uoc_ms_fps_fallbacks", "uoc_ms_check", "uoc_ms_workspace_bytes", "uoc_ms_select_seeds", "uoc_ms_select_seeds_from", "uoc_ms_hill_climb",
     "uoc_ms_seed_components", "uoc_ms_assign", "uoc_ms_cluster", "uoc_ms_workspace_bytes_wide", "uoc_ms_cluster_wide",
+) + METRIC_SYMBOLS + (
     "uoc_net_embed_dim",
     "uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_workspace_bytes",
     "uoc_net_forward", "uoc_net_set_split_precision", "uoc_conv2d_nhwc", "uoc_conv2d_nhwc_algo",

@@ -1,6 +1,6 @@
 // Seeded von-Mises-Fisher mean-shift clustering on gfx950 — hand-written HIP.
 //
-// Replaces /root/reference/lib/utils/mean_shift.py (cosine metric):
+// Replaces /root/reference/lib/utils/mean_shift.py (cosine and euclidean metrics, template parameter MET):
 //   select_smart_seeds       :128-189  -> fps_step_kernel        (HBM/L2-bound streaming + grid argmax)
 //   seed_hill_climbing_ball  :79-109   -> hc_iter_kernel         (fp32 MFMA, W never materialised)
 //                                         + hc_finalize_kernel   (partial reduce + L2 normalise)
@@ -29,6 +29,15 @@ constexpr int HC_THREADS = 256;
 constexpr int HC_MAX_BLOCKS = 1024;
 constexpr int ZP = 72;  // LDS row pitch (floats) of the seed tile: 18 x 16 B => conflict-free b128 fragment reads
 constexpr int NLAB = UOC_MAX_SEEDS;
+
+// Embedding metric (cfg.TRAIN.EMBEDDING_METRIC; the reference's metric= argument), a template parameter of every kernel
+// that measures a distance.  MS_COSINE is the 0.5 (1 - x.z) / exp(kappa x.z) / F.normalize path; MS_EUCLIDEAN uses
+// ||x - z||_2, exp(-kappa ||z - x||^2) and Z = W X / max(rowsum(W), 1) (mean_shift.py's metric == 'euclidean' branches).
+constexpr int MS_COSINE = UOC_METRIC_COSINE;
+constexpr int MS_EUCLIDEAN = UOC_METRIC_EUCLIDEAN;
+// ||x||^2 given to a hill-climbing pixel beyond n: its weight exp(-kappa (||z||^2 + XX_OUT - 2 z.x)) is exactly 0, so the
+// padding of a partial pixel tile adds nothing to the weight sums (its X rows are zeroed for W X already).
+constexpr float XX_OUT = 1e30f;
 
 struct ArgMax {
   float val;
@@ -61,7 +70,8 @@ __device__ __forceinline__ ArgMax wave_argmax(ArgMax v) {
 // NH = number of 64-channel halves of an embedding (1: the 64-d fields of every shipped mode but 'cat';
 // 2: 128-d fields stored as two planes X[b][h][n][64], seeds / Z likewise [b][h][m][64]); a dot product
 // is the sum over the halves.
-template <int NH>
+// MET = MS_EUCLIDEAN: d = ||x - seed||_2 from direct differences (torch.norm(X - seed, dim=1), mean_shift.py:160).
+template <int NH, int MET>
 __global__ __launch_bounds__(FPS_THREADS) void fps_step_kernel(
     const float *__restrict__ X, int n, int m, int step, int num_init, const int *__restrict__ first_index,
     float *__restrict__ dmin, float *__restrict__ seeds, int *__restrict__ indices,
@@ -133,23 +143,37 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_step_kernel(
     float mine = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      float s = x[0][i].x * sv[0].x;
-      s = fmaf(x[0][i].y, sv[0].y, s);
-      s = fmaf(x[0][i].z, sv[0].z, s);
-      s = fmaf(x[0][i].w, sv[0].w, s);
+      float s;
+      if constexpr (MET == MS_EUCLIDEAN) {
+        s = 0.f;
 #pragma unroll
-      for (int h = 1; h < NH; ++h) {
-        s = fmaf(x[h][i].x, sv[h].x, s);
-        s = fmaf(x[h][i].y, sv[h].y, s);
-        s = fmaf(x[h][i].z, sv[h].z, s);
-        s = fmaf(x[h][i].w, sv[h].w, s);
+        for (int h = 0; h < NH; ++h) {
+          const float dx = x[h][i].x - sv[h].x, dy = x[h][i].y - sv[h].y, dz = x[h][i].z - sv[h].z,
+                      dw = x[h][i].w - sv[h].w;
+          s = fmaf(dx, dx, s);
+          s = fmaf(dy, dy, s);
+          s = fmaf(dz, dz, s);
+          s = fmaf(dw, dw, s);
+        }
+      } else {
+        s = x[0][i].x * sv[0].x;
+        s = fmaf(x[0][i].y, sv[0].y, s);
+        s = fmaf(x[0][i].z, sv[0].z, s);
+        s = fmaf(x[0][i].w, sv[0].w, s);
+#pragma unroll
+        for (int h = 1; h < NH; ++h) {
+          s = fmaf(x[h][i].x, sv[h].x, s);
+          s = fmaf(x[h][i].y, sv[h].y, s);
+          s = fmaf(x[h][i].z, sv[h].z, s);
+          s = fmaf(x[h][i].w, sv[h].w, s);
+        }
       }
       s = row16_sum(s);
       if (t == i) mine = s;
     }
     const int p = base + 4 * t + g;
     if (p < n) {
-      float d = 0.5f * (1.0f - mine);
+      float d = MET == MS_EUCLIDEAN ? sqrtf(mine) : 0.5f * (1.0f - mine);
       if (step > 0) d = fminf(d, dmin[p]);
       dmin[p] = d;
       if (d > best.val) {  // p ascends per lane: strict '>' keeps the lowest index
@@ -218,6 +242,9 @@ __device__ __forceinline__ unsigned long long fpp_pack(float val, int idx, int t
   return ((unsigned long long)__float_as_uint(val) << 32) | (unsigned)(idx & 0xFFFFFF) | ((unsigned)(tag & 0xFF) << 24);
 }
 
+// MET = MS_EUCLIDEAN: d = sqrt(max(||x||^2 + ||s||^2 - 2 x.s, 0)) — the norms of the resident pixels are computed once at
+// load, the seed's once per step (64 FMAs on its wave-uniform row), so a step keeps one FMA per pixel-channel.
+template <int MET>
 __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
     const float *__restrict__ X, int n, int m, int bpi, int nslots, const int *__restrict__ first_index,
     float *__restrict__ seeds, int *__restrict__ indices, unsigned long long *gran, int *status) {
@@ -267,6 +294,30 @@ __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
   float dm[FPP_SLOTS];
 #pragma unroll
   for (int j = 0; j < FPP_SLOTS; ++j) dm[j] = 0.f;
+  float xx[FPP_SLOTS] = {};   // MS_EUCLIDEAN: ||x||^2 of the slots' pixels (the same fma chain as the seed's ||s||^2 below)
+  if constexpr (MET == MS_EUCLIDEAN) {
+    f32x2 q01 = {0.f, 0.f};
+    float q2 = 0.f, q3 = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      q01 = __builtin_elementwise_fma(x01[c], x01[c], q01);
+      q2 = fmaf(x2[c], x2[c], q2);
+    }
+    if (nslots > FPP_RS) {
+#pragma unroll
+      for (int c4 = 0; c4 < C / 4; ++c4) {
+        const float4 v = lds[c4 * FPP_THREADS];
+        q3 = fmaf(v.x, v.x, q3);
+        q3 = fmaf(v.y, v.y, q3);
+        q3 = fmaf(v.z, v.z, q3);
+        q3 = fmaf(v.w, v.w, q3);
+      }
+    }
+    xx[0] = q01.x;
+    xx[1] = q01.y;
+    xx[2] = q2;
+    xx[3] = q3;
+  }
 
   int cur = __builtin_amdgcn_readfirstlane(first_index[item]);
   if (cur < 0 || cur >= n) cur = 0;  // the host mirrors validate; never read outside X
@@ -288,6 +339,16 @@ __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
     f32x2 s01 = {0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < C; ++c) s01 = __builtin_elementwise_fma(x01[c], f32x2{srow[c], srow[c]}, s01);
+    float ss = 0.f;
+    if constexpr (MET == MS_EUCLIDEAN) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) ss = fmaf(srow[c], srow[c], ss);
+    }
+    // the distance of a slot's pixel with dot product s_ and squared norm xx_
+    auto dist = [&](float s_, float xx_) {
+      if constexpr (MET == MS_EUCLIDEAN) return sqrtf(fmaxf(fmaf(-2.0f, s_, xx_ + ss), 0.0f));
+      else return 0.5f * (1.0f - s_);
+    };
     float s2 = 0.f;
     if (nslots > 2) {
 #pragma unroll
@@ -297,7 +358,7 @@ __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
     for (int j = 0; j < FPP_RS; ++j) {
       if (j < nslots) {
         const float s_ = j == 0 ? s01.x : j == 1 ? s01.y : s2;
-        float d_ = 0.5f * (1.0f - s_);
+        float d_ = dist(s_, xx[j]);
         if (step > 0) d_ = fminf(d_, dm[j]);
         dm[j] = d_;
         const int p_ = pbase + j * FPP_THREADS;
@@ -317,7 +378,7 @@ __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
         s_ = fmaf(v.z, srow[4 * c4 + 2], s_);
         s_ = fmaf(v.w, srow[4 * c4 + 3], s_);
       }
-      float d_ = 0.5f * (1.0f - s_);
+      float d_ = dist(s_, xx[FPP_RS]);
       if (step > 0) d_ = fminf(d_, dm[FPP_RS]);
       dm[FPP_RS] = d_;
       const int p_ = pbase + FPP_RS * FPP_THREADS;
@@ -430,11 +491,16 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
 
 // NH = 2 (128-d fields as two 64-channel planes): S sums over both halves; the accumulators of one block
 // cover ONE half (blockIdx.z), so S is computed twice — the price of keeping the 64-d register tiling.
-template <int ST, int NH>
+// MS_EUCLIDEAN: W = exp(-kappa max(||z||^2 + ||x||^2 - 2 S, 0)) and per seed the weight sum, reduced in a fixed order
+// like the accumulators and stored (by the hz = 0 blocks) behind the partial sums: [batch][nvb][ST * 16].
+template <int ST, int NH, int MET>
 __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void hc_iter_kernel(const float *__restrict__ X, int n,
                                                              const float *__restrict__ Z, int m, float kappa,
                                                              float *__restrict__ partial_, int nvb) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr bool EUC = MET == MS_EUCLIDEAN;
+  __shared__ float zzs[EUC ? ST * 16 : 1];             // ||z||^2 per seed row
+  __shared__ float wred[EUC ? 4 * ST * 16 : 1];        // [wave][ST * 16] weight sums
   float *Zs = smem;  // [NH][ST*16][ZP]; later reused as the cross-wave reduction buffer
   const int b = blockIdx.y;
   const int nblk = nvb;                    // VIRTUAL blocks (hc_virtual_blocks: n only), walked by the physical ones
@@ -444,6 +510,7 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = lane & 15, q = lane >> 4;
+  float *const wpartial = partial_ + (size_t)gridDim.y * nblk * NH * (ST * 16) * C;
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
   float *partial = partial_ + (((size_t)b * nblk + vb) * NH + hz) * (ST * 16) * C;
 
@@ -455,6 +522,21 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     *reinterpret_cast<float4 *>(Zs + (h * ST * 16 + row) * ZP + 4 * c4) = v;
   }
   __syncthreads();
+  float ws[ST];
+  if constexpr (EUC) {
+    if (tid < ST * 16) {
+      float p = 0.f;
+      for (int h = 0; h < NH; ++h)
+        for (int c = 0; c < C; ++c) {
+          const float z = Zs[(h * ST * 16 + tid) * ZP + c];
+          p = fmaf(z, z, p);
+        }
+      zzs[tid] = p;
+    }
+#pragma unroll
+    for (int s = 0; s < ST; ++s) ws[s] = 0.f;
+    __syncthreads();
+  }
 
   f32x4 acc[ST][4];
 #pragma unroll
@@ -498,11 +580,37 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     int zo = 0;
     asm volatile("" : "+v"(zo));
     const float *Zt = Zs + zo;
+    float xx[4];   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3 (lane (t, q) holds 16 NH channels of pixel t in xa)
+    if constexpr (EUC) {
+      float p = 0.f;
+#pragma unroll
+      for (int v = 0; v < NH * 4; ++v) {
+        p = fmaf(xa[v].x, xa[v].x, p);
+        p = fmaf(xa[v].y, xa[v].y, p);
+        p = fmaf(xa[v].z, xa[v].z, p);
+        p = fmaf(xa[v].w, xa[v].w, p);
+      }
+      p += __shfl_xor(p, 16);
+      p += __shfl_xor(p, 32);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = __shfl(p, 4 * q + r);
+        xx[r] = tile * 16 + 4 * q + r < n ? v : XX_OUT;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < ST + 2; ++i) {
       if (i >= 1 && i - 1 < ST) {
+        if constexpr (EUC) {
+          const float zz = zzs[16 * (i - 1) + t];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) wv[i - 1][r] = UOC_EXP(kappa * Sv[i - 1][r]);
+          for (int r = 0; r < 4; ++r)
+            wv[i - 1][r] = UOC_EXP(-kappa * fmaxf(fmaf(-2.0f, Sv[i - 1][r], zz + xx[r]), 0.0f));
+          ws[i - 1] += (wv[i - 1][0] + wv[i - 1][1]) + (wv[i - 1][2] + wv[i - 1][3]);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) wv[i - 1][r] = UOC_EXP(kappa * Sv[i - 1][r]);
+        }
       }
       if (i < ST) Sv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (NH > 1 && i < ST) {  // second half of the dot products (not interleaved: 'cat' is the rare mode)
@@ -539,6 +647,15 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
 
   // ---- cross-wave reduction (fixed order: (w0 + w2) + (w1 + w3)) through LDS -------------
   f32x4 *red = reinterpret_cast<f32x4 *>(smem);  // [2][ST*4][64] f32x4
+  if constexpr (EUC) {
+#pragma unroll
+    for (int s = 0; s < ST; ++s) {
+      float v = ws[s];
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      if (q == 0) wred[wave * ST * 16 + 16 * s + t] = v;
+    }
+  }
   __syncthreads();
   if (wave >= 2) {
 #pragma unroll
@@ -562,6 +679,16 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
   }
   __syncthreads();
   if (wave == 0) {
+    if constexpr (EUC) {
+      if (hz == 0 && q == 0) {
+#pragma unroll
+        for (int s = 0; s < ST; ++s) {
+          const int i = 16 * s + t;
+          wpartial[((size_t)b * nblk + vb) * (ST * 16) + i] =
+              (wred[0 * ST * 16 + i] + wred[2 * ST * 16 + i]) + (wred[1 * ST * 16 + i] + wred[3 * ST * 16 + i]);
+        }
+      }
+    }
 #pragma unroll
     for (int s = 0; s < ST; ++s) {
 #pragma unroll
@@ -627,7 +754,42 @@ __device__ __forceinline__ void exp_op(ExpState (&es)[2], const f32x4 &s, float 
     w[2 * P + 1] = v.y;
   }
 }
+// MS_EUCLIDEAN: w = exp(-kappa max(||z||^2 + ||x||^2 - 2 s, 0)) — the argument is never positive, so exp() cannot
+// overflow — and the weight-sum accumulator ws (per lane: seed t, pixels 4q .. 4q+3).  27 VALU steps per seed tile, the
+// squared distance built in the registers of x: ops 0-1 x = zz + xx | 2-3 x = x - 2s | 4-7 max(x, 0) | 8-9 x = -kappa x |
+// 10-23 the cosine ops 2-15 | 24 x = (w0, w1) + (w2, w3) | 25-26 ws += x.
+constexpr int EUC_OPS = 27;
+template <int OP>
+__device__ __forceinline__ void euc_op(ExpState (&es)[2], const f32x4 &s, float kappa, float zz, const float (&xx)[4],
+                                       float (&w)[4], float &ws) {
+  constexpr int P = OP & 1;
+  ExpState &e = es[P];
+  if constexpr (OP < 2) e.x = f32x2{zz, zz} + f32x2{xx[2 * P], xx[2 * P + 1]};
+  else if constexpr (OP < 4) e.x = __builtin_elementwise_fma(f32x2{s[2 * P], s[2 * P + 1]}, f32x2{-2.0f, -2.0f}, e.x);
+  else if constexpr (OP < 8) {
+    constexpr int r = OP - 4;
+    es[r >> 1].x[r & 1] = fmaxf(es[r >> 1].x[r & 1], 0.0f);
+  } else if constexpr (OP < 10) e.x = f32x2{-kappa, -kappa} * e.x;
+  else if constexpr (OP < 24) exp_op<OP - 8>(es, s, kappa, w);
+  else if constexpr (OP == 24) es[0].x = f32x2{w[0], w[1]} + f32x2{w[2], w[3]};
+  else ws += es[0].x[OP - 25];
+}
+// ops [O0, O0 + sizeof...(Js)) one after the other (compile-time indices: no dispatch left to the unroller)
+template <int O0, int... Js>
+__device__ __forceinline__ void euc_ops(ExpState (&es)[2], const f32x4 &s, float kappa, float zz, const float (&xx)[4],
+                                        float (&w)[4], float &ws, std::integer_sequence<int, Js...>) {
+  (euc_op<O0 + Js>(es, s, kappa, zz, xx, w, ws), ...);
+}
 #pragma clang fp contract(fast)
+
+// MS_EUCLIDEAN per-lane inputs of a pixel tile: ||z||^2 of the lane's seed in every seed tile (zz), ||x||^2 of pixels
+// 4q .. 4q+3 (xx, XX_OUT beyond n) and the weight sums (ws).  Unused by the cosine instantiations.
+template <int ST>
+struct EucLane {
+  float zz[ST];
+  float xx[4];
+  float ws[ST];
+};
 
 
 // One pixel tile (16 pixels) against all ST seed tiles.  3-stage pipeline over the seed tiles, fully unrolled; step i:
@@ -648,10 +810,38 @@ __device__ __forceinline__ void exp_op(ExpState (&es)[2], const f32x4 &s, float 
 //   The result has the layout of a regular tile's S (reg r <-> pixel 4q+r) with seed t%4 in place of seed t, so exp()
 //   and the accumulate step keep their code: acc[last][ct] += W[pixel 4q+r][seed i] X[pixel 4q+r][chan 4t+ct] with
 //   block = (channel group t/4, pixel group q), summed over the four pixel groups once per virtual block.
-template <int ST, bool QUAD, int I>
+// The accumulate half of step I for MS_EUCLIDEAN: the same 16 MFMA slots as the cosine loop below, each followed by its
+// share of the 27 VALU steps of tile I-1 (behind MFMAs 3, 7, 11, 15), with every index a template argument.
+template <int ST, bool QUAD, int I, int K>
+__device__ __forceinline__ void hcr_euc_slot(const float4 (&xb)[4], f32x4 (&acc)[ST][4], f32x4 (&Sv)[ST + 2],
+                                             float (&wv)[ST + 2][4], ExpState (&es)[2], float kappa, EucLane<ST> &eu) {
+  constexpr bool do_a = I >= 2, do_e = I >= 1 && I - 1 < ST;
+  constexpr int IE = I >= 1 ? I - 1 : 0, IA = I >= 2 ? I - 2 : 0, IEz = IE < ST ? IE : 0;
+  constexpr bool quad_a = QUAD && IA == ST - 1;
+  if constexpr (do_a) {
+    constexpr int r = K >> 2, ct = K & 3;
+    if constexpr (quad_a)
+      acc[IA][ct] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[IA][r], f4c(xb[r], ct), acc[IA][ct], 0, 0, 0);
+    else
+      acc[IA][ct] = mfma4(wv[IA][r], f4c(xb[r], ct), acc[IA][ct]);
+  }
+  if constexpr (do_e && (K & 3) == 3) {
+    constexpr int c = K >> 2, o0 = c * EUC_OPS / 4, o1 = (c + 1) * EUC_OPS / 4;
+    euc_ops<o0>(es, Sv[IE], kappa, eu.zz[IEz], eu.xx, wv[IE], eu.ws[IEz], std::make_integer_sequence<int, o1 - o0>{});
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int ST, bool QUAD, int I, int... Ks>
+__device__ __forceinline__ void hcr_euc_slots(const float4 (&xb)[4], f32x4 (&acc)[ST][4], f32x4 (&Sv)[ST + 2],
+                                              float (&wv)[ST + 2][4], ExpState (&es)[2], float kappa, EucLane<ST> &eu,
+                                              std::integer_sequence<int, Ks...>) {
+  (hcr_euc_slot<ST, QUAD, I, Ks>(xb, acc, Sv, wv, es, kappa, eu), ...);
+}
+
+template <int ST, bool QUAD, int MET, int I>
 __device__ __forceinline__ void hcr_step(const float4 (&xa)[4], const float4 (&xb)[4], const float4 (&xc)[4],
                                          const float4 (&zb)[ST][4], f32x4 (&acc)[ST][4], f32x4 (&Sv)[ST + 2],
-                                         float (&wv)[ST + 2][4], ExpState (&es)[2], float kappa) {
+                                         float (&wv)[ST + 2][4], ExpState (&es)[2], float kappa, EucLane<ST> &eu) {
   // Sv / wv carry two spare rows so that the (never executed) I-1 / I-2 references of the first steps stay in range
   constexpr bool do_s = I < ST, do_a = I >= 2, do_e = I >= 1 && I - 1 < ST;
   constexpr int IS = I < ST ? I : 0, IE = I >= 1 ? I - 1 : 0, IA = I >= 2 ? I - 2 : 0;
@@ -674,6 +864,10 @@ __device__ __forceinline__ void hcr_step(const float4 (&xa)[4], const float4 (&x
       for (int r = 0; r < 4; ++r) Sv[IS][r] += dpp_f<0x124>(Sv[IS][r]);   // row_ror:4
       __builtin_amdgcn_sched_barrier(0);
     }
+  }
+  if constexpr (MET == MS_EUCLIDEAN) {
+    hcr_euc_slots<ST, QUAD, I>(xb, acc, Sv, wv, es, kappa, eu, std::make_integer_sequence<int, 16>{});
+    return;
   }
   constexpr int nops = do_e ? EXP_OPS : 0;
 #pragma unroll
@@ -715,20 +909,20 @@ __device__ __forceinline__ void hcr_step(const float4 (&xa)[4], const float4 (&x
   }
 }
 
-template <int ST, bool QUAD, int... Is>
+template <int ST, bool QUAD, int MET, int... Is>
 __device__ __forceinline__ void hcr_tile_steps(const float4 (&xa)[4], const float4 (&xb)[4], const float4 (&xc)[4],
                                                const float4 (&zb)[ST][4], f32x4 (&acc)[ST][4], float kappa,
-                                               std::integer_sequence<int, Is...>) {
+                                               EucLane<ST> &eu, std::integer_sequence<int, Is...>) {
   f32x4 Sv[ST + 2];
   float wv[ST + 2][4];
   ExpState es[2];
-  (hcr_step<ST, QUAD, Is>(xa, xb, xc, zb, acc, Sv, wv, es, kappa), ...);
+  (hcr_step<ST, QUAD, MET, Is>(xa, xb, xc, zb, acc, Sv, wv, es, kappa, eu), ...);
 }
 
-template <int ST, bool QUAD>
+template <int ST, bool QUAD, int MET>
 __device__ __forceinline__ void hcr_tile(const float4 (&xa)[4], const float4 (&xb)[4], const float4 (&xc)[4],
-                                         const float4 (&zb)[ST][4], f32x4 (&acc)[ST][4], float kappa) {
-  hcr_tile_steps<ST, QUAD>(xa, xb, xc, zb, acc, kappa, std::make_integer_sequence<int, ST + 2>{});
+                                         const float4 (&zb)[ST][4], f32x4 (&acc)[ST][4], float kappa, EucLane<ST> &eu) {
+  hcr_tile_steps<ST, QUAD, MET>(xa, xb, xc, zb, acc, kappa, eu, std::make_integer_sequence<int, ST + 2>{});
 }
 
 // THE SHIPPED KERNEL: one wave per SIMD (4 waves per block, one block per CU), every wave all ST seed tiles (~330 of
@@ -836,6 +1030,45 @@ __device__ __forceinline__ void hc_seed_mask(const HcGeom &ge, int m, float4 (&z
   }
 }
 
+// MS_EUCLIDEAN: ||z||^2 of every lane's seed, from its fragments (zero rows beyond m give 0).  A regular tile's lane holds
+// 16 of its seed's channels, the four pixel groups q the rest: (q0 + q1) + (q2 + q3).  The 4x4x1 tile's channel phases
+// meet like its S: two DPP row rotations.
+template <int ST, bool QUAD>
+__device__ __forceinline__ void hc_seed_norms(const float4 (&zb)[ST][4], float (&zz)[ST]) {
+#pragma unroll
+  for (int i = 0; i < ST; ++i) {
+    float p = 0.f;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      p = fmaf(zb[i][v].x, zb[i][v].x, p);
+      p = fmaf(zb[i][v].y, zb[i][v].y, p);
+      p = fmaf(zb[i][v].z, zb[i][v].z, p);
+      p = fmaf(zb[i][v].w, zb[i][v].w, p);
+    }
+    if (QUAD && i == ST - 1) {
+      p += dpp_f<0x128>(p);   // row_ror:8
+      p += dpp_f<0x124>(p);   // row_ror:4
+    } else {
+      p += __shfl_xor(p, 16);
+      p += __shfl_xor(p, 32);
+    }
+    zz[i] = p;
+  }
+}
+// MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3 of pixel tile tl from the accumulate view (lane t holds channels 4t .. 4t+3):
+// a row sum over t.  Pixels beyond n get XX_OUT (weight exactly 0).
+__device__ __forceinline__ void hc_pixel_norms(const HcGeom &ge, int tl, const float4 (&bb)[4], float (&xx)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float p = bb[r].x * bb[r].x;
+    p = fmaf(bb[r].y, bb[r].y, p);
+    p = fmaf(bb[r].z, bb[r].z, p);
+    p = fmaf(bb[r].w, bb[r].w, p);
+    p = row16_sum(p);
+    xx[r] = tl * 16 + 4 * ge.q + r < ge.n ? p : XX_OUT;
+  }
+}
+
 // All-zero accumulators from the matrix pipe (0 x 0 + 0): 28 MFMAs that run while the wave waits at a barrier or for its
 // first pixels.  112 v_accvgpr_write cost VALU issue — hipcc put them (twice) at the head of every item, 2 us per item.
 template <int ST>
@@ -853,11 +1086,14 @@ __device__ __forceinline__ void hc_zero_acc(f32x4 (&acc)[ST][4]) {
 // tile on entry and the first tile of the NEXT item (field nb, tile nt) on exit.  Znext != nullptr: the next item belongs
 // to another field — its seed fragments are requested as soon as the last pixel tile is done and arrive under the
 // cross-wave reduction.
-template <int ST, bool QUAD, bool KQ>
+// MS_EUCLIDEAN also: eu.zz holds the norms of zb's seeds (and of the next item's on exit), eu.ws is zero on entry and on
+// exit, and the item's weight sums go to wdst (row 0 = the first of these seeds).
+template <int ST, bool QUAD, bool KQ, int MET>
 __device__ __forceinline__ void hc_item(const HcGeom &ge, float4 (&zb)[ST][4], float kappa, int b, int vb, int nb,
                                         int nt, float4 (&xa)[4], float4 (&xb)[4], float4 (&xc)[4], int &held_b,
                                         int &held_t, f32x4 (&acc)[ST][4], f32x4 *red, float *__restrict__ dst,
-                                        const float *__restrict__ Znext, int m) {
+                                        const float *__restrict__ Znext, int m, EucLane<ST> &eu,
+                                        float *__restrict__ wdst) {
   // acc: all zero on entry, all zero again on exit
   const int lane = ge.lane, wave = ge.wave, t = ge.t, q = ge.q;
   f32x4 *red_wave = red + (size_t)wave * ST * 4 * 64;
@@ -874,7 +1110,8 @@ __device__ __forceinline__ void hc_item(const HcGeom &ge, float4 (&zb)[ST][4], f
     if (KQ) hc_load_quad_view(ge, b, tile, xc);
     hc_load_tile(ge, more ? b : nb, nxt, na, nbv);
     __builtin_amdgcn_sched_barrier(0);
-    hcr_tile<ST, QUAD>(ca, cb, xc, zb, acc, kappa);
+    if constexpr (MET == MS_EUCLIDEAN) hc_pixel_norms(ge, tile, cb, eu.xx);
+    hcr_tile<ST, QUAD, MET>(ca, cb, xc, zb, acc, kappa, eu);
     __builtin_amdgcn_sched_barrier(0);
     hc_mask_tile(ge, nxt, nbv);
     held_b = more ? b : nb;
@@ -914,6 +1151,17 @@ __device__ __forceinline__ void hc_item(const HcGeom &ge, float4 (&zb)[ST][4], f
   for (int s = 0; s < ST; ++s)
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) red_wave[(s * 4 + ct) * 64 + lane] = acc[s][ct];
+  float *wred = reinterpret_cast<float *>(red + (size_t)4 * ST * 4 * 64);   // MS_EUCLIDEAN: [4 waves][ST][16] weight sums
+  if constexpr (MET == MS_EUCLIDEAN) {
+#pragma unroll
+    for (int s = 0; s < ST; ++s) {   // lane order: the pixel tiles, then the pixel groups (q0 + q1) + (q2 + q3)
+      float v = eu.ws[s];
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      if (q == 0) wred[(wave * ST + s) * 16 + t] = v;
+      eu.ws[s] = 0.f;
+    }
+  }
   hc_zero_acc<ST>(acc);   // on the matrix pipe, under the barrier
   __syncthreads();
   for (int s = wave; s < ST; s += 4) {
@@ -930,17 +1178,25 @@ __device__ __forceinline__ void hc_item(const HcGeom &ge, float4 (&zb)[ST][4], f
     for (int r = 0; r < 4; ++r)
       *reinterpret_cast<float4 *>(dst + (size_t)(16 * s + 4 * q + r) * C + 4 * t) =
           make_float4(o[0][r], o[1][r], o[2][r], o[3][r]);
+    if constexpr (MET == MS_EUCLIDEAN) {
+      if (q == 0)
+        wdst[16 * s + t] = (wred[(0 * ST + s) * 16 + t] + wred[(1 * ST + s) * 16 + t]) +
+                           (wred[(2 * ST + s) * 16 + t] + wred[(3 * ST + s) * 16 + t]);
+    }
   }
   __syncthreads();  // the reduction buffer is written again by the next item
-  if (Znext) hc_seed_mask<ST, QUAD>(ge, m, zb);
+  if (Znext) {
+    hc_seed_mask<ST, QUAD>(ge, m, zb);
+    if constexpr (MET == MS_EUCLIDEAN) hc_seed_norms<ST, QUAD>(zb, eu.zz);
+  }
 }
 
 // A tail part: seed tiles [s0, s0 + ST) of the launch's tiles, with its own fragments and its own first pixel tile (no
 // hand-over of registers between the bodies: hipcc then keeps the whole-item loop's live ranges to itself — with the
 // next item's pixels carried across the bodies it parked them in AGPRs and paid 66 extra VALU moves per pixel tile).
-template <int ST, bool QUAD>
+template <int ST, bool QUAD, int MET>
 __device__ __forceinline__ void hc_part(const HcGeom &ge, const float *__restrict__ Zb, int m, int s0, float kappa, int b,
-                                        int vb, f32x4 *red, float *__restrict__ dst_item) {
+                                        int vb, f32x4 *red, float *__restrict__ dst_item, float *__restrict__ wdst_item) {
   float4 zb[ST][4];
   hc_seed_loads<ST, QUAD>(ge, Zb + (size_t)16 * s0 * C, m - 16 * s0, zb);
   float4 xa[4], xb[4], xc[4];
@@ -950,13 +1206,21 @@ __device__ __forceinline__ void hc_part(const HcGeom &ge, const float *__restric
   hc_load_tile(ge, b, held_t, xa, xb);
   hc_seed_mask<ST, QUAD>(ge, m - 16 * s0, zb);
   hc_mask_tile(ge, held_t, xb);
+  EucLane<ST> eu;
+  if constexpr (MET == MS_EUCLIDEAN) {
+    hc_seed_norms<ST, QUAD>(zb, eu.zz);
+#pragma unroll
+    for (int s = 0; s < ST; ++s) eu.ws[s] = 0.f;
+  }
   f32x4 acc[ST][4];
   hc_zero_acc<ST>(acc);
-  hc_item<ST, QUAD, QUAD>(ge, zb, kappa, b, vb, b, held_t, xa, xb, xc, held_b, held_t, acc, red,
-                          dst_item + (size_t)16 * s0 * C, nullptr, 0);
+  hc_item<ST, QUAD, QUAD, MET>(ge, zb, kappa, b, vb, b, held_t, xa, xb, xc, held_b, held_t, acc, red,
+                               dst_item + (size_t)16 * s0 * C, nullptr, 0, eu, wdst_item + 16 * s0);
 }
 
-template <int ST, bool QUAD>
+// MS_EUCLIDEAN: the items' weight sums [items][ST * 16] follow their partial sums [items][ST * 16][64] in `partial`
+// (the workspace reserves them, carve); the dynamic LDS holds the [4][ST][16] weight-sum buffer behind the reduction one.
+template <int ST, bool QUAD, int MET>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void hc_iter_flat_kernel(
     const float *__restrict__ X, int n, const float *__restrict__ Z, int m, float kappa, float *__restrict__ partial,
     HcPlan plan) {
@@ -974,6 +1238,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   ge.q = ge.lane >> 4;
   const int g = blockIdx.x;
   constexpr bool SPLIT = ST == 7 && QUAD;   // the seed-tile parts exist for the 97..100-seed launches (the reference's 100)
+  float *const wpartial = partial + (size_t)plan.items * (ST * 16) * C;   // MS_EUCLIDEAN only
 
   // ---- whole items.  If every block can stay inside ONE field (q items per block, q | nvb, whole fields only) block
   //      (field f, x) takes the virtual blocks x, x + nvb/q, ...: the pixel tiles of its items then share their pages
@@ -997,6 +1262,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     hc_seed_loads<ST, QUAD>(ge, Z + (size_t)b * m * C, m, zb);
     hc_mask_tile(ge, held_t, xb);
     hc_seed_mask<ST, QUAD>(ge, m, zb);
+    EucLane<ST> eu;
+    if constexpr (MET == MS_EUCLIDEAN) {
+      hc_seed_norms<ST, QUAD>(zb, eu.zz);
+#pragma unroll
+      for (int s = 0; s < ST; ++s) eu.ws[s] = 0.f;
+    }
     f32x4 acc[ST][4];
     hc_zero_acc<ST>(acc);
     for (int j = 0; j < count; ++j) {
@@ -1010,9 +1281,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         hc_load_tile(ge, b, held_t, xa, xb);
         hc_mask_tile(ge, held_t, xb);
       }
-      hc_item<ST, QUAD, QUAD>(ge, zb, kappa, b, vb, nb, nvb_ * 4 + ge.wave, xa, xb, xc, held_b, held_t, acc, red,
-                              partial + ((size_t)b * plan.nvb + vb) * (ST * 16) * C,
-                              nb != b ? Z + (size_t)nb * m * C : nullptr, m);
+      hc_item<ST, QUAD, QUAD, MET>(ge, zb, kappa, b, vb, nb, nvb_ * 4 + ge.wave, xa, xb, xc, held_b, held_t, acc, red,
+                                   partial + ((size_t)b * plan.nvb + vb) * (ST * 16) * C,
+                                   nb != b ? Z + (size_t)nb * m * C : nullptr, m, eu,
+                                   wpartial + ((size_t)b * plan.nvb + vb) * (ST * 16));
       b = nb;
       vb = nvb_;
     }
@@ -1027,7 +1299,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int b = item / plan.nvb, vb = item % plan.nvb;
       const float *Zb = Z + (size_t)b * m * C;
       float *dst = partial + ((size_t)b * plan.nvb + vb) * (ST * 16) * C;
-#define UOC_HC_PART(SUB, Q4, S0) hc_part<SUB, Q4>(ge, Zb, m, S0, kappa, b, vb, red, dst)
+      float *wdst = wpartial + ((size_t)b * plan.nvb + vb) * (ST * 16);
+#define UOC_HC_PART(SUB, Q4, S0) hc_part<SUB, Q4, MET>(ge, Zb, m, S0, kappa, b, vb, red, dst, wdst)
       // seed tiles 0..5 are full, tile 6 holds the last <= 4 seeds (a tenth of a full tile's time): balanced splits
       const int P = plan.parts;
       if (P == 2) {                                   // {0 1 2} {3 4 5 6}
@@ -1046,7 +1319,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // partial [b][blk][NH][rows][64] -> Z [b][NH][m][64], the norm runs over all NH * 64 channels.
 // One block per seed: 16 lanes x float4 cover a 256-byte row, so a wave reads the rows of 4 blocks per load and
 // the 4 waves keep 64 rows in flight per step (4 independent accumulators); fixed summation order.
-template <int NH>
+// MS_EUCLIDEAN: Z[seed] = sum_blk partial / max(sum_blk weight sum, 1) (mean_shift.py:100-104, no normalisation); the
+// weight sums [b][blk][rows] follow the partial sums.  Wave 0 sums them: lane l takes blocks l, l + 64, ..., then a
+// fixed butterfly over the lanes.
+template <int NH, int MET>
 __global__ __launch_bounds__(256) void hc_finalize_kernel(const float *__restrict__ partial, int nblk, int rows,
                                                           int m, float *__restrict__ Z) {
   const int b = blockIdx.y, seed = blockIdx.x;
@@ -1093,7 +1369,17 @@ __global__ __launch_bounds__(256) void hc_finalize_kernel(const float *__restric
     }
 #pragma unroll
     for (int off = 8; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);  // over the 16 channel groups
-    const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+    float nrm;
+    if constexpr (MET == MS_EUCLIDEAN) {
+      const float *wsrc = partial + (size_t)gridDim.y * nblk * NH * rows * C + (size_t)b * nblk * rows + seed;
+      float ws = 0.f;
+      for (int blk = lane; blk < nblk; blk += 64) ws += wsrc[(size_t)blk * rows];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) ws += __shfl_xor(ws, off);
+      nrm = fmaxf(ws, 1.0f);
+    } else {
+      nrm = fmaxf(sqrtf(ss), 1e-12f);
+    }
     if (sub == 0) {
 #pragma unroll
       for (int h = 0; h < NH; ++h)
@@ -1108,7 +1394,8 @@ __global__ __launch_bounds__(256) void hc_finalize_kernel(const float *__restric
 // so ONE wavefront per batch item; lane l owns seeds l and l+64.  Quirks kept: the component
 // takes the MODE of already-present labels (ties -> smallest) and overwrites every member.
 // -------------------------------------------------------------------------------------------
-template <int NH>
+// MS_EUCLIDEAN: member if ||z_j - z_i||_2 <= eps (direct differences, torch.norm, mean_shift.py:58-59).
+template <int NH, int MET>
 __global__ __launch_bounds__(64) void seed_cc_kernel(const float *__restrict__ Z, int m, float eps,
                                                      int *__restrict__ seed_labels, int *__restrict__ num_unique) {
   constexpr int CW = NH * C;  // a seed row in LDS: the NH halves back to back, pitch CW + 1
@@ -1129,12 +1416,28 @@ __global__ __launch_bounds__(64) void seed_cc_kernel(const float *__restrict__ Z
     const float *zi = Zs + i * (CW + 1);
     const float *z0 = Zs + lane * (CW + 1);
     const float *z1 = Zs + (lane + 64) * (CW + 1);
-    if (have0)
-      for (int c = 0; c < CW; ++c) dot0 = fmaf(z0[c], zi[c], dot0);
-    if (have1)
-      for (int c = 0; c < CW; ++c) dot1 = fmaf(z1[c], zi[c], dot1);
-    const bool in0 = have0 && (0.5f * (1.0f - dot0) <= eps);
-    const bool in1 = have1 && (0.5f * (1.0f - dot1) <= eps);
+    bool in0, in1;
+    if constexpr (MET == MS_EUCLIDEAN) {
+      if (have0)
+        for (int c = 0; c < CW; ++c) {
+          const float d = z0[c] - zi[c];
+          dot0 = fmaf(d, d, dot0);
+        }
+      if (have1)
+        for (int c = 0; c < CW; ++c) {
+          const float d = z1[c] - zi[c];
+          dot1 = fmaf(d, d, dot1);
+        }
+      in0 = have0 && (sqrtf(dot0) <= eps);
+      in1 = have1 && (sqrtf(dot1) <= eps);
+    } else {
+      if (have0)
+        for (int c = 0; c < CW; ++c) dot0 = fmaf(z0[c], zi[c], dot0);
+      if (have1)
+        for (int c = 0; c < CW; ++c) dot1 = fmaf(z1[c], zi[c], dot1);
+      in0 = have0 && (0.5f * (1.0f - dot0) <= eps);
+      in1 = have1 && (0.5f * (1.0f - dot1) <= eps);
+    }
     unsigned long long lm0 = __ballot(in0 && lab0 != -1), lm1 = __ballot(in1 && lab1 != -1);
     const bool any_unl = (__ballot(in0 && lab0 == -1) | __ballot(in1 && lab1 == -1)) != 0ull;
     // distinct values among members' labels (the value -1 counts as one, :66)
@@ -1178,7 +1481,9 @@ __global__ __launch_bounds__(64) void seed_cc_kernel(const float *__restrict__ Z
 // Nearest-seed assignment: S = X Z^T on fp32 MFMA, d = 0.5(1 - S), argmin over seeds
 // (ties -> lowest seed index, torch.argmin), label = seed_labels[argmin], per-label histogram.
 // -------------------------------------------------------------------------------------------
-template <int ST, int NH>
+// MS_EUCLIDEAN: d = sqrt(max(||x||^2 + ||z||^2 - 2 S, 0)), the square root taken before the argmin like the reference's
+// torch.norm (mean_shift.py:211-212).
+template <int ST, int NH, int MET>
 __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restrict__ X, int n,
                                                             const float *__restrict__ Z,
                                                             const int *__restrict__ seed_labels, int m,
@@ -1187,6 +1492,7 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
   extern __shared__ __attribute__((aligned(16))) float Zs[];  // [NH][ST * 16][ZP]
   __shared__ int slab[NLAB];
   __shared__ int hist[NLAB];
+  __shared__ float zzs[MET == MS_EUCLIDEAN ? ST * 16 : 1];   // ||z||^2 per seed row
   const int b = blockIdx.y;
   X += (size_t)b * NH * n * C;
   Z += (size_t)b * NH * m * C;
@@ -1209,6 +1515,18 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
     hist[tid] = 0;
   }
   __syncthreads();
+  if constexpr (MET == MS_EUCLIDEAN) {
+    if (tid < ST * 16) {
+      float p = 0.f;
+      for (int h = 0; h < NH; ++h)
+        for (int c = 0; c < C; ++c) {
+          const float z = Zs[(h * ST * 16 + tid) * ZP + c];
+          p = fmaf(z, z, p);
+        }
+      zzs[tid] = p;
+    }
+    __syncthreads();
+  }
 
   const int ntile = (n + 15) >> 4;
   for (int tile = blockIdx.x * (HC_THREADS / 64) + wave; tile < ntile; tile += gridDim.x * (HC_THREADS / 64)) {
@@ -1218,6 +1536,21 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
     for (int v = 0; v < NH * 4; ++v)
       xa[v] = (pa < n) ? *reinterpret_cast<const float4 *>(X + ((size_t)(v >> 2) * n + pa) * C + 16 * (v & 3) + 4 * q)
                        : make_float4(0.f, 0.f, 0.f, 0.f);
+    float xx[4] = {};   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3 (lane (t, q) holds 16 NH channels of pixel t)
+    if constexpr (MET == MS_EUCLIDEAN) {
+      float p = 0.f;
+#pragma unroll
+      for (int v = 0; v < NH * 4; ++v) {
+        p = fmaf(xa[v].x, xa[v].x, p);
+        p = fmaf(xa[v].y, xa[v].y, p);
+        p = fmaf(xa[v].z, xa[v].z, p);
+        p = fmaf(xa[v].w, xa[v].w, p);
+      }
+      p += __shfl_xor(p, 16);
+      p += __shfl_xor(p, 32);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xx[r] = __shfl(p, 4 * q + r);
+    }
     float bd[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
     int bi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
 #pragma unroll
@@ -1235,7 +1568,8 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
       const int seed = 16 * s + t;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float d = 0.5f * (1.0f - S[r]);
+        const float d = MET == MS_EUCLIDEAN ? sqrtf(fmaxf(fmaf(-2.0f, S[r], xx[r] + zzs[MET == MS_EUCLIDEAN ? seed : 0]), 0.0f))
+                                            : 0.5f * (1.0f - S[r]);
         if (seed < m && d < bd[r]) {  // s ascends: strict '<' keeps the lowest seed index
           bd[r] = d;
           bi[r] = seed;
@@ -1308,7 +1642,7 @@ __global__ __launch_bounds__(256) void relabel_swap_kernel(int *__restrict__ lab
 struct MsWorkspace {
   float *dmin;        // [batch][n]
   ArgMax *part[2];    // [batch][FPS_MAX_BLOCKS] ping-pong
-  float *hc_partial;  // [batch][nblk][128][64]
+  float *hc_partial;  // [batch][nblk][128][64] + [batch][nblk][128]
   int *counts;        // [batch][128]
   int *num_unique;    // [batch]
   int *seed_labels;   // [batch][128]
@@ -1377,7 +1711,8 @@ static MsWorkspace carve(void *base, int batch, int n, int nh = 1) {
   w.dmin = (float *)take((size_t)batch * n * sizeof(float));
   w.part[0] = (ArgMax *)take((size_t)batch * FPS_MAX_BLOCKS * sizeof(ArgMax));
   w.part[1] = (ArgMax *)take((size_t)batch * FPS_MAX_BLOCKS * sizeof(ArgMax));
-  w.hc_partial = (float *)take((size_t)batch * w.hc_nblk * nh * NLAB * C * sizeof(float));
+  // [batch][nblk][nh][rows][64] partial sums, then (euclidean metric) [batch][nblk][rows] weight sums
+  w.hc_partial = (float *)take((size_t)batch * w.hc_nblk * (nh * NLAB * C + NLAB) * sizeof(float));
   w.counts = (int *)take((size_t)batch * NLAB * sizeof(int));
   w.num_unique = (int *)take((size_t)batch * sizeof(int));
   w.seed_labels = (int *)take((size_t)batch * NLAB * sizeof(int));
@@ -1437,7 +1772,8 @@ static int fps_persistent_plan(int batch, int n, int *bpi, int *nslots) {
 }
 
 static int run_select_seeds_streaming(const float *X, int batch, int n, int m, const int32_t *first, float *seeds,
-                                      int32_t *indices, const MsWorkspace &w, hipStream_t st, int num_init = 0);
+                                      int32_t *indices, const MsWorkspace &w, hipStream_t st, int num_init = 0,
+                                      int met = MS_COSINE);
 
 // One event per device that orders the persistent sampling kernels of all streams (see run_select_seeds).
 struct FpsChain {
@@ -1459,7 +1795,9 @@ static FpsChain &fps_chain() {
 // caller replaying such graphs on ONE stream per device, with nothing else running beside them.
 
 static int run_select_seeds(const float *X, int batch, int n, int m, const int32_t *first, float *seeds,
-                            int32_t *indices, const MsWorkspace &w, hipStream_t st) {
+                            int32_t *indices, const MsWorkspace &w, hipStream_t st, int met = MS_COSINE) {
+  const void *fpp = met == MS_EUCLIDEAN ? reinterpret_cast<const void *>(&fps_persistent_kernel<MS_EUCLIDEAN>)
+                                        : reinterpret_cast<const void *>(&fps_persistent_kernel<MS_COSINE>);
   // Persistent path: as many items per cooperative launch as stay co-resident; a larger batch
   // (stage 2 with > 8 ROIs) is split into several launches rather than dropped to the streaming kernel.
   int done = 0;
@@ -1481,12 +1819,11 @@ static int run_select_seeds(const float *X, int batch, int n, int m, const int32
     // the LDS pixel slot is only touched when a lane owns more than FPP_RS pixels; without it the kernel needs no
     // dynamic LDS at all and can share a CU with another stream's convolution blocks (two frames in flight)
     const size_t lds = (nslots > FPP_RS) ? (size_t)FPP_LS * (C / 4) * FPP_THREADS * sizeof(float4) : 0;
-    static DeviceOnce attr_set;
-    if (!attr_set.done()) {
-      UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&fps_persistent_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+    static DeviceOnce attr_set[2];
+    if (!attr_set[met].done()) {
+      UOC_HIP_CHECK(hipFuncSetAttribute(fpp, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)((size_t)FPP_LS * (C / 4) * FPP_THREADS * sizeof(float4))));
-      attr_set.mark();
+      attr_set[met].mark();
     }
     const float *Xc = X + (size_t)done * n * C;
     const int32_t *fc = first + done;
@@ -1508,11 +1845,9 @@ static int run_select_seeds(const float *X, int batch, int n, int m, const int32
         ProfScope prof(KC_FPS_STEP, st, 2.0 * sub * (double)n * C * (m - 1), 4.0 * sub * (double)n * C,
                        ProfTag{{n, sub, bpi, nslots}});
         if (!capturing)
-          e = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&fps_persistent_kernel), dim3(sub * bpi),
-                                         dim3(FPP_THREADS), args, (unsigned)lds, st);
+          e = hipLaunchCooperativeKernel(fpp, dim3(sub * bpi), dim3(FPP_THREADS), args, (unsigned)lds, st);
         else
-          e = hipLaunchKernel(reinterpret_cast<const void *>(&fps_persistent_kernel), dim3(sub * bpi), dim3(FPP_THREADS),
-                              args, lds, st);
+          e = hipLaunchKernel(fpp, dim3(sub * bpi), dim3(FPP_THREADS), args, lds, st);
       }
       if (e == hipSuccess && ev) UOC_HIP_CHECK(hipEventRecord(ev, st));
     }
@@ -1531,23 +1866,26 @@ static int run_select_seeds(const float *X, int batch, int n, int m, const int32
               "kernel does not fit / is not co-resident on this device); see uoc_ms_fps_fallbacks()\n", batch - done, batch, n);
   }
   return run_select_seeds_streaming(X + (size_t)done * w.nh * n * C, batch - done, n, m, first + done,
-                                    seeds + (size_t)done * w.nh * m * C, indices + (size_t)done * m, w, st);
+                                    seeds + (size_t)done * w.nh * m * C, indices + (size_t)done * m, w, st, 0, met);
 }
 
 static int run_select_seeds_streaming(const float *X, int batch, int n, int m, const int32_t *first, float *seeds,
-                                      int32_t *indices, const MsWorkspace &w, hipStream_t st, int num_init) {
+                                      int32_t *indices, const MsWorkspace &w, hipStream_t st, int num_init, int met) {
   const int nblk = fps_blocks(n);
   for (int s = 0; s < m; ++s) {
     dim3 grid(nblk, batch);  // gridDim.x doubles as the partial count, so it is the same every step
     const bool last = s == m - 1;
     ProfScope prof(KC_FPS_STEP, st, last ? 0.0 : 2.0 * batch * n * C * w.nh,
                    last ? 0.0 : 4.0 * batch * ((double)n * C * w.nh + 2.0 * n));
-    if (w.nh == 2)
-      hipLaunchKernelGGL(fps_step_kernel<2>, grid, dim3(FPS_THREADS), 0, st, X, n, m, s, num_init, first, w.dmin, seeds,
-                         indices, w.part[(s + 1) & 1], w.part[s & 1]);
-    else
-      hipLaunchKernelGGL(fps_step_kernel<1>, grid, dim3(FPS_THREADS), 0, st, X, n, m, s, num_init, first, w.dmin, seeds,
-                         indices, w.part[(s + 1) & 1], w.part[s & 1]);
+#define UOC_FPS_STEP(NH_, MET_)                                                                                       \
+  hipLaunchKernelGGL((fps_step_kernel<NH_, MET_>), grid, dim3(FPS_THREADS), 0, st, X, n, m, s, num_init, first, w.dmin, \
+                     seeds, indices, w.part[(s + 1) & 1], w.part[s & 1])
+    if (met == MS_EUCLIDEAN) {
+      if (w.nh == 2) UOC_FPS_STEP(2, MS_EUCLIDEAN); else UOC_FPS_STEP(1, MS_EUCLIDEAN);
+    } else {
+      if (w.nh == 2) UOC_FPS_STEP(2, MS_COSINE); else UOC_FPS_STEP(1, MS_COSINE);
+    }
+#undef UOC_FPS_STEP
   }
   UOC_LAUNCH_CHECK();
   return UOC_OK;
@@ -1621,7 +1959,7 @@ static HcPlan hc_make_plan(int batch, int nvb, bool splittable) {
   return best;
 }
 
-template <int ST, int NH>
+template <int ST, int NH, int MET>
 static void launch_hc(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
                       const MsWorkspace &w, hipStream_t st) {
   const size_t zbytes = (size_t)NH * ST * 16 * ZP * sizeof(float);
@@ -1629,12 +1967,12 @@ static void launch_hc(const float *X, int batch, int n, float *Z, int m, float k
   const size_t lds = zbytes > rbytes ? zbytes : rbytes;
   static DeviceOnce attr_set;
   if (!attr_set.done() && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_kernel<ST, NH>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_kernel<ST, NH, MET>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set.mark();
   }
   const bool reg = NH == 1 && hc_variant() == 2;   // register-resident kernel, one wave per SIMD
-  const size_t lds_reg = (size_t)4 * ST * 4 * 64 * sizeof(f32x4);
+  const size_t lds_reg = (size_t)4 * ST * 4 * 64 * sizeof(f32x4) + (MET == MS_EUCLIDEAN ? (size_t)4 * ST * 16 * sizeof(float) : 0);
   const int nvb = w.hc_nblk;
   const int last = m - 16 * (ST - 1);                  // seeds in the last tile
   const bool quad = ST >= 2 && last >= 1 && last <= 4;   // they run on the 4x4x1 MFMA instead of a padded 16-seed tile
@@ -1644,9 +1982,9 @@ static void launch_hc(const float *X, int batch, int n, float *Z, int m, float k
       plan = hc_make_plan(batch, nvb, ST == 7 && quad);
       static DeviceOnce attr_reg;
       if (!attr_reg.done() && lds_reg > 64 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, false, MET>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, true, MET>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
         attr_reg.mark();
       }
@@ -1661,48 +1999,54 @@ static void launch_hc(const float *X, int batch, int n, float *Z, int m, float k
       if constexpr (NH == 1) {
         if (reg) {
           if (quad)
-            hipLaunchKernelGGL((hc_iter_flat_kernel<ST, true>), dim3(plan.grid), dim3(256), lds_reg, st, X, n, Z, m, kappa,
-                               w.hc_partial, plan);
+            hipLaunchKernelGGL((hc_iter_flat_kernel<ST, true, MET>), dim3(plan.grid), dim3(256), lds_reg, st, X, n, Z, m,
+                               kappa, w.hc_partial, plan);
           else
-            hipLaunchKernelGGL((hc_iter_flat_kernel<ST, false>), dim3(plan.grid), dim3(256), lds_reg, st, X, n, Z, m, kappa,
-                               w.hc_partial, plan);
+            hipLaunchKernelGGL((hc_iter_flat_kernel<ST, false, MET>), dim3(plan.grid), dim3(256), lds_reg, st, X, n, Z, m,
+                               kappa, w.hc_partial, plan);
         }
       }
       if (!reg)
-        hipLaunchKernelGGL((hc_iter_kernel<ST, NH>), dim3(phys, batch, NH), dim3(HC_THREADS), lds, st, X, n, Z, m,
+        hipLaunchKernelGGL((hc_iter_kernel<ST, NH, MET>), dim3(phys, batch, NH), dim3(HC_THREADS), lds, st, X, n, Z, m,
                            kappa, w.hc_partial, nvb);
     }
     ProfScope prof(KC_HC_FINALIZE, st, 0.0, 4.0 * batch * w.hc_nblk * NH * ST * 16.0 * C);
-    hipLaunchKernelGGL(hc_finalize_kernel<NH>, dim3(m, batch), dim3(256), 0, st, w.hc_partial, w.hc_nblk, ST * 16, m, Z);
+    hipLaunchKernelGGL((hc_finalize_kernel<NH, MET>), dim3(m, batch), dim3(256), 0, st, w.hc_partial, w.hc_nblk, ST * 16,
+                       m, Z);
   }
 }
 
-template <int NH>
+template <int NH, int MET>
 static void run_hill_climb_nh(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
                               const MsWorkspace &w, hipStream_t st) {
   switch ((m + 15) / 16) {
-    case 1: launch_hc<1, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 2: launch_hc<2, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 3: launch_hc<3, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 4: launch_hc<4, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 5: launch_hc<5, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 6: launch_hc<6, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 7: launch_hc<7, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    default: launch_hc<8, NH>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 1: launch_hc<1, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 2: launch_hc<2, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 3: launch_hc<3, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 4: launch_hc<4, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 5: launch_hc<5, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 6: launch_hc<6, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    case 7: launch_hc<7, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
+    default: launch_hc<8, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
   }
 }
 
 static int run_hill_climb(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
-                          const MsWorkspace &w, hipStream_t st) {
-  if (w.nh == 2)
-    run_hill_climb_nh<2>(X, batch, n, Z, m, kappa, iters, w, st);
+                          const MsWorkspace &w, hipStream_t st, int met = MS_COSINE) {
+  if (met == MS_EUCLIDEAN) {
+    if (w.nh == 2)
+      run_hill_climb_nh<2, MS_EUCLIDEAN>(X, batch, n, Z, m, kappa, iters, w, st);
+    else
+      run_hill_climb_nh<1, MS_EUCLIDEAN>(X, batch, n, Z, m, kappa, iters, w, st);
+  } else if (w.nh == 2)
+    run_hill_climb_nh<2, MS_COSINE>(X, batch, n, Z, m, kappa, iters, w, st);
   else
-    run_hill_climb_nh<1>(X, batch, n, Z, m, kappa, iters, w, st);
+    run_hill_climb_nh<1, MS_COSINE>(X, batch, n, Z, m, kappa, iters, w, st);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
 
-template <int ST, int NH>
+template <int ST, int NH, int MET>
 static void launch_assign(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m,
                           int *labels, int *closest, const MsWorkspace &w, hipStream_t st) {
   int nblk = hc_blocks(batch, n, 1, true) * 2;
@@ -1711,38 +2055,43 @@ static void launch_assign(const float *X, int batch, int n, const float *Z, cons
   const size_t lds = (size_t)NH * ST * 16 * ZP * sizeof(float);
   static DeviceOnce attr_set;
   if (!attr_set.done() && lds > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_kernel<ST, NH>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_kernel<ST, NH, MET>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set.mark();
   }
   ProfScope prof(KC_ASSIGN, st, 2.0 * batch * m * (double)n * C * NH, 4.0 * batch * ((double)n * C * NH + n));
-  hipLaunchKernelGGL((assign_kernel<ST, NH>), dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m,
+  hipLaunchKernelGGL((assign_kernel<ST, NH, MET>), dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m,
                      labels, closest, w.counts);
 }
 
-template <int NH>
+template <int NH, int MET>
 static void run_assign_nh(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m, int *labels,
                           int *closest, const MsWorkspace &w, hipStream_t st) {
   switch ((m + 15) / 16) {
-    case 1: launch_assign<1, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 2: launch_assign<2, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 3: launch_assign<3, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 4: launch_assign<4, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 5: launch_assign<5, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 6: launch_assign<6, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 7: launch_assign<7, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    default: launch_assign<8, NH>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 1: launch_assign<1, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 2: launch_assign<2, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 3: launch_assign<3, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 4: launch_assign<4, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 5: launch_assign<5, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 6: launch_assign<6, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    case 7: launch_assign<7, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
+    default: launch_assign<8, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
   }
 }
 
 static int run_assign(const float *X, int batch, int n, const float *Z, const int *seed_labels,
                       const int *num_unique, int m, int *labels, int *closest, const MsWorkspace &w,
-                      hipStream_t st) {
+                      hipStream_t st, int met = MS_COSINE) {
   UOC_HIP_CHECK(hipMemsetAsync(w.counts, 0, (size_t)batch * NLAB * sizeof(int), st));
-  if (w.nh == 2)
-    run_assign_nh<2>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+  if (met == MS_EUCLIDEAN) {
+    if (w.nh == 2)
+      run_assign_nh<2, MS_EUCLIDEAN>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+    else
+      run_assign_nh<1, MS_EUCLIDEAN>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+  } else if (w.nh == 2)
+    run_assign_nh<2, MS_COSINE>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
   else
-    run_assign_nh<1>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+    run_assign_nh<1, MS_COSINE>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
   int rb = (n + 255) / 256;
   if (rb > 512) rb = 512;
   ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n);
@@ -1751,21 +2100,30 @@ static int run_assign(const float *X, int batch, int n, const float *Z, const in
   return UOC_OK;
 }
 
-static int run_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique, int nh,
-                       hipStream_t st) {
-  ProfScope prof(KC_SEED_CC, st, 0.0, 4.0 * batch * m * C * nh);
+template <int MET>
+static int launch_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique, int nh,
+                          hipStream_t st) {
   const size_t lds = (size_t)NLAB * (nh * C + 1) * sizeof(float);
   if (nh == 2) {
     static DeviceOnce attr_set;
     if (!attr_set.done()) {
-      UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&seed_cc_kernel<2>),
+      UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&seed_cc_kernel<2, MET>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       attr_set.mark();
     }
-    hipLaunchKernelGGL(seed_cc_kernel<2>, dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
+    hipLaunchKernelGGL((seed_cc_kernel<2, MET>), dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
   } else {
-    hipLaunchKernelGGL(seed_cc_kernel<1>, dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
+    hipLaunchKernelGGL((seed_cc_kernel<1, MET>), dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
   }
+  return UOC_OK;
+}
+
+static int run_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique, int nh,
+                       hipStream_t st, int met = MS_COSINE) {
+  ProfScope prof(KC_SEED_CC, st, 0.0, 4.0 * batch * m * C * nh);
+  const int rc = met == MS_EUCLIDEAN ? launch_seed_cc<MS_EUCLIDEAN>(Z, batch, m, eps, seed_labels, num_unique, nh, st)
+                                     : launch_seed_cc<MS_COSINE>(Z, batch, m, eps, seed_labels, num_unique, nh, st);
+  if (rc) return rc;
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -1821,6 +2179,10 @@ size_t uoc_ms_workspace_bytes(int batch, int n, int m) {
   return carve(nullptr, batch, n).total;
 }
 
+#define UOC_REQUIRE_METRIC(metric)                                                                             \
+  UOC_REQUIRE((metric) == UOC_METRIC_COSINE || (metric) == UOC_METRIC_EUCLIDEAN,                              \
+              "metric=%d: expected %d (cosine) or %d (euclidean)", (metric), UOC_METRIC_COSINE, UOC_METRIC_EUCLIDEAN)
+
 int uoc_ms_select_seeds(const float *d_X, int batch, int n, int m, const int32_t *d_first_index, float *d_seeds,
                         int32_t *d_indices, void *d_ws, size_t ws_bytes, void *stream) {
   if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
@@ -1829,56 +2191,68 @@ int uoc_ms_select_seeds(const float *d_X, int batch, int n, int m, const int32_t
                           (hipStream_t)stream);
 }
 
-int uoc_ms_select_seeds_from(const float *d_X, int batch, int n, int m, int num_init, const int32_t *d_first_index,
-                             float *d_seeds, int32_t *d_indices, void *d_ws, size_t ws_bytes, void *stream) {
+int uoc_ms_select_seeds_ex(const float *d_X, int batch, int n, int m, int num_init, const int32_t *d_first_index,
+                           float *d_seeds, int32_t *d_indices, int metric, void *d_ws, size_t ws_bytes, void *stream) {
+  UOC_REQUIRE_METRIC(metric);
   if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
   UOC_REQUIRE(d_seeds && d_indices && ((uintptr_t)d_seeds & 15) == 0, "seeds / indices null or seeds not 16-byte aligned");
   UOC_REQUIRE(num_init >= 0 && num_init <= m, "num_init=%d out of range [0, %d]", num_init, m);
   UOC_REQUIRE(num_init > 0 || d_first_index, "null first_index pointer");
   if (num_init == 0)
-    return run_select_seeds(d_X, batch, n, m, d_first_index, d_seeds, d_indices, carve(d_ws, batch, n), (hipStream_t)stream);
+    return run_select_seeds(d_X, batch, n, m, d_first_index, d_seeds, d_indices, carve(d_ws, batch, n), (hipStream_t)stream,
+                            metric);
   return run_select_seeds_streaming(d_X, batch, n, m, d_first_index, d_seeds, d_indices, carve(d_ws, batch, n),
-                                    (hipStream_t)stream, num_init);
+                                    (hipStream_t)stream, num_init, metric);
+}
+
+int uoc_ms_select_seeds_from(const float *d_X, int batch, int n, int m, int num_init, const int32_t *d_first_index,
+                             float *d_seeds, int32_t *d_indices, void *d_ws, size_t ws_bytes, void *stream) {
+  return uoc_ms_select_seeds_ex(d_X, batch, n, m, num_init, d_first_index, d_seeds, d_indices, UOC_METRIC_COSINE, d_ws,
+                                ws_bytes, stream);
+}
+
+int uoc_ms_hill_climb_ex(const float *d_X, int batch, int n, float *d_Z, int m, float kappa, int iters, int metric,
+                         void *d_ws, size_t ws_bytes, void *stream) {
+  UOC_REQUIRE_METRIC(metric);
+  if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
+  UOC_REQUIRE(d_Z != nullptr && ((uintptr_t)d_Z & 15) == 0, "Z null or not 16-byte aligned");
+  UOC_REQUIRE(iters >= 0, "iters=%d must be >= 0", iters);
+  return run_hill_climb(d_X, batch, n, d_Z, m, kappa, iters, carve(d_ws, batch, n), (hipStream_t)stream, metric);
 }
 
 int uoc_ms_hill_climb(const float *d_X, int batch, int n, float *d_Z, int m, float kappa, int iters, void *d_ws,
                       size_t ws_bytes, void *stream) {
-  if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
-  UOC_REQUIRE(d_Z != nullptr && ((uintptr_t)d_Z & 15) == 0, "Z null or not 16-byte aligned");
-  UOC_REQUIRE(iters >= 0, "iters=%d must be >= 0", iters);
-  return run_hill_climb(d_X, batch, n, d_Z, m, kappa, iters, carve(d_ws, batch, n), (hipStream_t)stream);
+  return uoc_ms_hill_climb_ex(d_X, batch, n, d_Z, m, kappa, iters, UOC_METRIC_COSINE, d_ws, ws_bytes, stream);
+}
+
+int uoc_ms_seed_components_ex(const float *d_Z, int batch, int m, float epsilon, int metric, int32_t *d_seed_labels,
+                              int32_t *d_num_unique, void *stream) {
+  UOC_REQUIRE_METRIC(metric);
+  UOC_REQUIRE(d_Z && d_seed_labels && d_num_unique, "null pointer");
+  UOC_REQUIRE(batch >= 1 && m >= 1 && m <= UOC_MAX_SEEDS, "batch=%d m=%d out of range", batch, m);
+  return run_seed_cc(d_Z, batch, m, epsilon, d_seed_labels, d_num_unique, 1, (hipStream_t)stream, metric);
 }
 
 int uoc_ms_seed_components(const float *d_Z, int batch, int m, float epsilon, int32_t *d_seed_labels,
                            int32_t *d_num_unique, void *stream) {
-  UOC_REQUIRE(d_Z && d_seed_labels && d_num_unique, "null pointer");
-  UOC_REQUIRE(batch >= 1 && m >= 1 && m <= UOC_MAX_SEEDS, "batch=%d m=%d out of range", batch, m);
-  return run_seed_cc(d_Z, batch, m, epsilon, d_seed_labels, d_num_unique, 1, (hipStream_t)stream);
+  return uoc_ms_seed_components_ex(d_Z, batch, m, epsilon, UOC_METRIC_COSINE, d_seed_labels, d_num_unique, stream);
+}
+
+int uoc_ms_assign_ex(const float *d_X, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
+                     const int32_t *d_num_unique, int m, int metric, int32_t *d_labels, int32_t *d_closest, void *d_ws,
+                     size_t ws_bytes, void *stream) {
+  UOC_REQUIRE_METRIC(metric);
+  if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
+  UOC_REQUIRE(d_Z && d_seed_labels && d_num_unique && d_labels, "null pointer");
+  return run_assign(d_X, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, d_closest, carve(d_ws, batch, n),
+                    (hipStream_t)stream, metric);
 }
 
 int uoc_ms_assign(const float *d_X, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
                   const int32_t *d_num_unique, int m, int32_t *d_labels, int32_t *d_closest, void *d_ws,
                   size_t ws_bytes, void *stream) {
-  if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
-  UOC_REQUIRE(d_Z && d_seed_labels && d_num_unique && d_labels, "null pointer");
-  return run_assign(d_X, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, d_closest, carve(d_ws, batch, n),
-                    (hipStream_t)stream);
-}
-
-int uoc_ms_cluster(const float *d_X, int batch, int n, int m, float kappa, int iters, float epsilon,
-                   const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
-                   int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
-  if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
-  UOC_REQUIRE(d_first_index && d_labels && d_indices, "null pointer");
-  UOC_REQUIRE(iters >= 0, "iters=%d must be >= 0", iters);
-  hipStream_t st = (hipStream_t)stream;
-  MsWorkspace w = carve(d_ws, batch, n);
-  float *Z = d_Z_out ? d_Z_out : w.Z;
-  int *sl = d_seed_labels_out ? d_seed_labels_out : w.seed_labels;
-  if (int rc = run_select_seeds(d_X, batch, n, m, d_first_index, Z, d_indices, w, st)) return rc;
-  if (int rc = run_hill_climb(d_X, batch, n, Z, m, kappa, iters, w, st)) return rc;
-  if (int rc = run_seed_cc(Z, batch, m, epsilon, sl, w.num_unique, 1, st)) return rc;
-  return run_assign(d_X, batch, n, Z, sl, w.num_unique, m, d_labels, nullptr, w, st);
+  return uoc_ms_assign_ex(d_X, batch, n, d_Z, d_seed_labels, d_num_unique, m, UOC_METRIC_COSINE, d_labels, d_closest,
+                          d_ws, ws_bytes, stream);
 }
 
 size_t uoc_ms_workspace_bytes_wide(int batch, int n, int m, int halves) {
@@ -1887,9 +2261,10 @@ size_t uoc_ms_workspace_bytes_wide(int batch, int n, int m, int halves) {
   return carve(nullptr, batch, n, halves).total;
 }
 
-int uoc_ms_cluster_wide(const float *d_X, int halves, int batch, int n, int m, float kappa, int iters, float epsilon,
-                        const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
-                        int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
+int uoc_ms_cluster_wide_ex(const float *d_X, int halves, int batch, int n, int m, float kappa, int iters, float epsilon,
+                           int metric, const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
+                           int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
+  UOC_REQUIRE_METRIC(metric);
   UOC_REQUIRE(halves == 1 || halves == 2, "halves=%d (64-d or 128-d embeddings only)", halves);
   if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes, halves)) return rc;
   UOC_REQUIRE(d_first_index && d_labels && d_indices, "null pointer");
@@ -1898,10 +2273,31 @@ int uoc_ms_cluster_wide(const float *d_X, int halves, int batch, int n, int m, f
   MsWorkspace w = carve(d_ws, batch, n, halves);
   float *Z = d_Z_out ? d_Z_out : w.Z;
   int *sl = d_seed_labels_out ? d_seed_labels_out : w.seed_labels;
-  if (int rc = run_select_seeds(d_X, batch, n, m, d_first_index, Z, d_indices, w, st)) return rc;
-  if (int rc = run_hill_climb(d_X, batch, n, Z, m, kappa, iters, w, st)) return rc;
-  if (int rc = run_seed_cc(Z, batch, m, epsilon, sl, w.num_unique, halves, st)) return rc;
-  return run_assign(d_X, batch, n, Z, sl, w.num_unique, m, d_labels, nullptr, w, st);
+  if (int rc = run_select_seeds(d_X, batch, n, m, d_first_index, Z, d_indices, w, st, metric)) return rc;
+  if (int rc = run_hill_climb(d_X, batch, n, Z, m, kappa, iters, w, st, metric)) return rc;
+  if (int rc = run_seed_cc(Z, batch, m, epsilon, sl, w.num_unique, halves, st, metric)) return rc;
+  return run_assign(d_X, batch, n, Z, sl, w.num_unique, m, d_labels, nullptr, w, st, metric);
+}
+
+int uoc_ms_cluster_ex(const float *d_X, int batch, int n, int m, float kappa, int iters, float epsilon, int metric,
+                      const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
+                      int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
+  return uoc_ms_cluster_wide_ex(d_X, 1, batch, n, m, kappa, iters, epsilon, metric, d_first_index, d_labels, d_indices,
+                                d_Z_out, d_seed_labels_out, d_ws, ws_bytes, stream);
+}
+
+int uoc_ms_cluster(const float *d_X, int batch, int n, int m, float kappa, int iters, float epsilon,
+                   const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
+                   int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
+  return uoc_ms_cluster_wide_ex(d_X, 1, batch, n, m, kappa, iters, epsilon, UOC_METRIC_COSINE, d_first_index, d_labels,
+                                d_indices, d_Z_out, d_seed_labels_out, d_ws, ws_bytes, stream);
+}
+
+int uoc_ms_cluster_wide(const float *d_X, int halves, int batch, int n, int m, float kappa, int iters, float epsilon,
+                        const int32_t *d_first_index, int32_t *d_labels, int32_t *d_indices, float *d_Z_out,
+                        int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
+  return uoc_ms_cluster_wide_ex(d_X, halves, batch, n, m, kappa, iters, epsilon, UOC_METRIC_COSINE, d_first_index,
+                                d_labels, d_indices, d_Z_out, d_seed_labels_out, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -164,7 +164,7 @@ _frames = {}
 def _key(network, network_crop, H, W, dev, thr):
     gen = lambda n: (id(n), getattr(n, "_native_gen", 0)) if n is not None else None
     return (gen(network), gen(network_crop), H, W, dev.type, dev.index, thr, cfg.INPUT, cfg.TRAIN.FUSION_TYPE,
-            int(cfg.TRAIN.SYN_CROP_SIZE), float(cfg.TRAIN.EMBEDDING_ALPHA))
+            int(cfg.TRAIN.SYN_CROP_SIZE), float(cfg.TRAIN.EMBEDDING_ALPHA), str(cfg.TRAIN.EMBEDDING_METRIC))
 
 
 def frame_for(network, network_crop, H, W, dev, thr):

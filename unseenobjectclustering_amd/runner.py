@@ -27,11 +27,19 @@ def shard_range(num_frames: int, rank: int, world: int):
     return lo, min(lo + per, num_frames)
 
 
+# folded into the fingerprint when cfg.TRAIN.EMBEDDING_METRIC is 'euclidean' (cosine leaves it as the library's)
+EUCLIDEAN_FINGERPRINT_SALT = 0x45554344_4D455452   # "EUCDMETR"
+
+
 def config_fingerprint() -> int:
-    """63 bits of uoc_config_fingerprint() (what could make two ranks compute different bits).  Tests of the mismatch path
-    replace this function (monkeypatch); nothing in the environment overrides it."""
+    """63 bits of uoc_config_fingerprint() (what could make two ranks compute different bits), with the embedding metric
+    folded in: ranks that cluster with different metrics refuse to gather.  Tests of the mismatch path replace this
+    function (monkeypatch); nothing in the environment overrides it."""
     from . import _native
-    return _native.config_fingerprint() & 0x7FFFFFFFFFFFFFFF
+    fp = _native.config_fingerprint()
+    if cfg.TRAIN.EMBEDDING_METRIC == "euclidean":
+        fp ^= EUCLIDEAN_FINGERPRINT_SALT
+    return fp & 0x7FFFFFFFFFFFFFFF
 
 
 def frame_rng_seed(frame_index: int) -> int:

@@ -1,5 +1,8 @@
-"""Host-side mirror of the reference's lib/utils/mean_shift.py (cosine metric), backed by the
+"""Host-side mirror of the reference's lib/utils/mean_shift.py (metric='cosine' and metric='euclidean'), backed by the
 HIP kernels in csrc/meanshift.hip through the C ABI (include/uoc_hip.h).
+
+metric='euclidean' on these reference-surface functions needs the program's opt-in, cfg.TRAIN.EMBEDDING_METRIC =
+'euclidean' (fcn/config.py); cluster_batch takes the metric as an argument and defaults to the configured one.
 
 Same names, argument meaning and return types as the reference:
     mean_shift_smart_init(X, kappa, num_seeds=100, max_iters=10, metric='cosine')
@@ -16,7 +19,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..fcn.config import cfg
+from ..fcn.config import cfg, euclidean_enabled
 
 EMBED_DIM = 64          # one 64-channel "half"; 128-d ('cat' fusion) fields are two of them
 _ws_cache = {}
@@ -42,9 +45,20 @@ def _check_points(X: torch.Tensor, what="X") -> torch.Tensor:
     return X.contiguous()
 
 
-def _require_cosine(metric):
-    if metric != "cosine":
-        raise NotImplementedError("only metric='cosine' is implemented on gfx950")
+def _metric(metric) -> int:
+    """The metric= argument of cluster_batch -> the C ABI's metric argument; anything but 'cosine' / 'euclidean' raises."""
+    return _native.metric_code(metric)
+
+
+def _surface_metric(metric) -> int:
+    """The metric= argument of the reference-surface functions.  'euclidean' needs the program's opt-in
+    (cfg.TRAIN.EMBEDDING_METRIC = 'euclidean', fcn/config.py); without it these functions refuse it, as they always did."""
+    code = _metric(metric)
+    if code == _native.METRIC_EUCLIDEAN and not euclidean_enabled():
+        raise NotImplementedError("metric='euclidean' needs the opt-in cfg.TRAIN.EMBEDDING_METRIC = 'euclidean' "
+                                  "(or UOC_EMBEDDING_METRIC=euclidean); the configured metric is %r"
+                                  % (cfg.TRAIN.EMBEDDING_METRIC,))
+    return code
 
 
 def _first_indices(first_index, B: int, n: int) -> torch.Tensor:
@@ -70,17 +84,20 @@ def to_planes(X: torch.Tensor) -> torch.Tensor:
 
 
 def cluster_batch(X: torch.Tensor, first_index, kappa: float = 20.0, num_seeds: int = 100, max_iters: int = 10,
-                  epsilon: float = None, return_parts: bool = False):
+                  epsilon: float = None, return_parts: bool = False, metric: str = None):
     """Cluster B independent fields in one set of launches.
 
     X [B, n, 64] float32 unit rows (pixel-major) — or, for 128-d embeddings, the plane layout
-    [B, 2, n, 64] (to_planes) — first_index: B ints.
+    [B, 2, n, 64] (to_planes) — first_index: B ints.  metric: 'cosine' or 'euclidean'; None (default) = the configured
+    cfg.TRAIN.EMBEDDING_METRIC, so every clustering stage of fcn/test_dataset.py follows the configuration.  epsilon is a
+    cosine distance or a euclidean length accordingly.
     Returns labels [B, n] int32 and indices [B, num_seeds] int32 (device tensors); with
     return_parts also the converged seeds Z [B, m, 64] ([B, 2, m, 64]) and their labels [B, m].
     """
+    met = _metric(cfg.TRAIN.EMBEDDING_METRIC if metric is None else metric)
     X = _check_points(X)
     if X.dim() == 4:
-        return _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, return_parts)
+        return _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, return_parts, met)
     assert X.dim() == 3
     B, n, _ = X.shape
     if epsilon is None:
@@ -95,16 +112,16 @@ def cluster_batch(X: torch.Tensor, first_index, kappa: float = 20.0, num_seeds: 
     nbytes = L.uoc_ms_workspace_bytes(B, n, num_seeds)
     ws = _workspace(dev, nbytes)
     with torch.cuda.device(dev):
-        rc = L.uoc_ms_cluster(_native.ptr(X), B, n, num_seeds, float(kappa), int(max_iters), float(epsilon),
-                              _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
-                              _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_cluster")
+        rc = L.uoc_ms_cluster_ex(_native.ptr(X), B, n, num_seeds, float(kappa), int(max_iters), float(epsilon), met,
+                                 _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
+                                 _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
+    _native.check(rc, "uoc_ms_cluster_ex")
     if return_parts:
         return labels, indices, Z, seed_labels
     return labels, indices
 
 
-def _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, return_parts):
+def _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, return_parts, met):
     B, H2, n, _ = X.shape
     if H2 != 2:
         raise NotImplementedError("embedding dimension must be 64 or 128 (two 64-channel planes)")
@@ -119,10 +136,10 @@ def _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, re
     seed_labels = torch.empty((B, num_seeds), dtype=torch.int32, device=dev)
     ws = _workspace(dev, L.uoc_ms_workspace_bytes_wide(B, n, num_seeds, H2))
     with torch.cuda.device(dev):
-        rc = L.uoc_ms_cluster_wide(_native.ptr(X), H2, B, n, num_seeds, float(kappa), int(max_iters), float(epsilon),
-                                   _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
-                                   _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_cluster_wide")
+        rc = L.uoc_ms_cluster_wide_ex(_native.ptr(X), H2, B, n, num_seeds, float(kappa), int(max_iters), float(epsilon),
+                                      met, _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
+                                      _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
+    _native.check(rc, "uoc_ms_cluster_wide_ex")
     if return_parts:
         return labels, indices, Z, seed_labels
     return labels, indices
@@ -130,7 +147,7 @@ def _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, re
 
 def mean_shift_smart_init(X, kappa, num_seeds=100, max_iters=10, metric="cosine"):
     """mean_shift.py:192-229.  X [n, d] unit rows on the GPU, d = 64 or 128 -> (labels [n] int64, indices [m] int64)."""
-    _require_cosine(metric)
+    _surface_metric(metric)
     n = X.shape[0]
     first = np.random.randint(0, n)          # mean_shift.py:155 — same global-RNG draw as the reference
     Xb = X.unsqueeze(0)
@@ -138,7 +155,7 @@ def mean_shift_smart_init(X, kappa, num_seeds=100, max_iters=10, metric="cosine"
         if not X.is_cuda:
             raise _native.NativeError("X must be on a ROCm device (no CPU fallback)")
         Xb = to_planes(Xb.float())
-    labels, indices = cluster_batch(Xb, [first], kappa, num_seeds, max_iters)
+    labels, indices = cluster_batch(Xb, [first], kappa, num_seeds, max_iters, metric=metric)
     idx = indices[0].long().cpu()            # synchronises; then ask whether the grid exchange completed
     with torch.cuda.device(labels.device):
         _native.check(_native.lib().uoc_ms_check(_native.stream_ptr(labels.device)), "uoc_ms_check")
@@ -150,7 +167,7 @@ def select_smart_seeds(X, num_seeds, return_selected_indices=False, init_seeds=N
     """mean_shift.py:128-189.  With init_seeds [num_seeds, d] (first num_init_seeds rows already chosen, :142-170) the
     selection continues from them and — as in the reference, where `seeds = init_seeds` — is written into that tensor;
     the returned indices are -1 for the given rows.  The global RNG is drawn only when no seed is given yet (:154-155)."""
-    _require_cosine(metric)
+    met = _surface_metric(metric)
     X = _check_points(X)
     n = X.shape[0]
     dev = X.device
@@ -176,9 +193,9 @@ def select_smart_seeds(X, num_seeds, return_selected_indices=False, init_seeds=N
     indices = torch.empty((num_seeds,), dtype=torch.int32, device=dev)
     ws = _workspace(dev, L.uoc_ms_workspace_bytes(1, n, num_seeds))
     with torch.cuda.device(dev):
-        rc = L.uoc_ms_select_seeds_from(_native.ptr(X), 1, n, num_seeds, num_init, _native.ptr(first), _native.ptr(seeds),
-                                        _native.ptr(indices), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_select_seeds_from")
+        rc = L.uoc_ms_select_seeds_ex(_native.ptr(X), 1, n, num_seeds, num_init, _native.ptr(first), _native.ptr(seeds),
+                                      _native.ptr(indices), met, _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
+    _native.check(rc, "uoc_ms_select_seeds_ex")
     if return_selected_indices:
         return seeds, indices.long().cpu()
     return (seeds,)
@@ -186,36 +203,37 @@ def select_smart_seeds(X, num_seeds, return_selected_indices=False, init_seeds=N
 
 def seed_hill_climbing_ball(X, Z, kappa, max_iters=10, metric="cosine"):
     """mean_shift.py:79-109.  Returns the updated seeds (a new tensor, Z is not modified)."""
-    _require_cosine(metric)
+    met = _surface_metric(metric)
     X = _check_points(X)
     Zc = _check_points(Z, "Z").clone()
     n, m = X.shape[0], Zc.shape[0]
     L = _native.lib()
     ws = _workspace(X.device, L.uoc_ms_workspace_bytes(1, n, m))
     with torch.cuda.device(X.device):
-        rc = L.uoc_ms_hill_climb(_native.ptr(X), 1, n, _native.ptr(Zc), m, float(kappa), int(max_iters),
-                                 _native.ptr(ws), ws.numel(), _native.stream_ptr(X.device))
-    _native.check(rc, "uoc_ms_hill_climb")
+        rc = L.uoc_ms_hill_climb_ex(_native.ptr(X), 1, n, _native.ptr(Zc), m, float(kappa), int(max_iters), met,
+                                    _native.ptr(ws), ws.numel(), _native.stream_ptr(X.device))
+    _native.check(rc, "uoc_ms_hill_climb_ex")
     return Zc
 
 
 def connected_components(Z, epsilon, metric="cosine"):
     """mean_shift.py:41-76.  Z [m, d] -> [m] int64 labels (CPU tensor, like the reference)."""
-    _require_cosine(metric)
+    met = _surface_metric(metric)
     Zc = _check_points(Z, "Z")
     m = Zc.shape[0]
     L = _native.lib()
     out = torch.empty((m,), dtype=torch.int32, device=Zc.device)
     nu = torch.empty((1,), dtype=torch.int32, device=Zc.device)
     with torch.cuda.device(Zc.device):
-        rc = L.uoc_ms_seed_components(_native.ptr(Zc), 1, m, float(epsilon), _native.ptr(out), _native.ptr(nu),
-                                      _native.stream_ptr(Zc.device))
-    _native.check(rc, "uoc_ms_seed_components")
+        rc = L.uoc_ms_seed_components_ex(_native.ptr(Zc), 1, m, float(epsilon), met, _native.ptr(out), _native.ptr(nu),
+                                         _native.stream_ptr(Zc.device))
+    _native.check(rc, "uoc_ms_seed_components_ex")
     return out.long().cpu()
 
 
 def mean_shift_with_seeds(X, Z, kappa, max_iters=10, metric="cosine"):
     """mean_shift.py:112-125: hill climbing then seed connected components (eps = 2*alpha)."""
+    _surface_metric(metric)
     Znew = seed_hill_climbing_ball(X, Z, kappa, max_iters=max_iters, metric=metric)
     labels = connected_components(Znew, 2 * cfg.TRAIN.EMBEDDING_ALPHA, metric=metric)
     return labels, Znew
