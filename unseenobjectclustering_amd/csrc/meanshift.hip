@@ -2,7 +2,8 @@
 //
 // Replaces /root/reference/lib/utils/mean_shift.py (cosine and euclidean metrics, template parameter MET):
 //   select_smart_seeds       :128-189  -> fps_step_kernel        (HBM/L2-bound streaming + grid argmax)
-//   seed_hill_climbing_ball  :79-109   -> hc_iter_kernel         (fp32 MFMA, W never materialised)
+//   seed_hill_climbing_ball  :79-109   -> hc_iter_flat_kernel    (64-d fields: fp32 MFMA, W never materialised)
+//                                         | hc_iter_kernel       (128-d 'cat' fields: LDS-staged seed fragments)
 //                                         + hc_finalize_kernel   (partial reduce + L2 normalise)
 //   connected_components     :41-76    -> seed_cc_kernel         (one wavefront, ballots)
 //   mean_shift_smart_init    :211-227  -> assign_kernel          (fp32 MFMA + row argmin + histogram)
@@ -18,6 +19,7 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 namespace uoc {
@@ -464,7 +466,8 @@ __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
 }
 
 // -------------------------------------------------------------------------------------------
-// One hill-climbing iteration.  Each wave owns 16-pixel tiles and all ST seed tiles:
+// One hill-climbing iteration of a 128-d field (NH = 2; 64-d fields run hc_iter_flat_kernel below).  Each wave owns
+// 16-pixel tiles and all ST seed tiles:
 //   S^T[pixel][seed] = X Z^T       16 x v_mfma_f32_16x16x4_f32 per (16 px x 16 seeds)
 //   W = exp(kappa S)               in registers: the D fragment of step 1 IS the A fragment of step 3
 //   acc[seed][chan] += W^T X       16 x v_mfma_f32_16x16x4_f32
@@ -481,22 +484,65 @@ __global__ __launch_bounds__(FPP_THREADS) void fps_persistent_kernel(
 // pipeline): 109 us.  All four sit at ~56 % of the fp32 MFMA peak (12 % of the MFMAs are the padding of 100 seeds
 // to 7 tiles), so the simplest one stays; no single bound was found (clock 2.4 GHz, 850 W under this kernel).
 // -------------------------------------------------------------------------------------------
-#ifndef UOC_EXP
-#define UOC_EXP expf
-#endif
 __device__ __forceinline__ float f4c(const float4 &v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// NH = 2 (128-d fields as two 64-channel planes): S sums over both halves; the accumulators of one block
-// cover ONE half (blockIdx.z), so S is computed twice — the price of keeping the 64-d register tiling.
+// Shared by the two LDS-staged kernels (hc_iter_kernel, assign_kernel); the fma order of the norms is part of the
+// euclidean results.
+// The seeds Z [NH][m][64] as the zero-padded tile Zs [NH][ST * 16][ZP] (no barrier: the caller syncs).
+template <int ST, int NH>
+__device__ __forceinline__ void lds_stage_seeds(const float *Z, int m, int tid, float *Zs) {
+  for (int i = tid; i < NH * ST * 16 * (C / 4); i += HC_THREADS) {
+    const int h = i / (ST * 16 * (C / 4)), j = i % (ST * 16 * (C / 4));
+    const int row = j / (C / 4), c4 = j % (C / 4);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row < m) v = *reinterpret_cast<const float4 *>(Z + ((size_t)h * m + row) * C + 4 * c4);
+    *reinterpret_cast<float4 *>(Zs + (h * ST * 16 + row) * ZP + 4 * c4) = v;
+  }
+}
+// MS_EUCLIDEAN: ||z||^2 of every seed row of the staged tile.
+template <int ST, int NH>
+__device__ __forceinline__ void lds_seed_norms(const float *Zs, int tid, float *zzs) {
+  if (tid < ST * 16) {
+    float p = 0.f;
+    for (int h = 0; h < NH; ++h)
+      for (int c = 0; c < C; ++c) {
+        const float z = Zs[(h * ST * 16 + tid) * ZP + c];
+        p = fmaf(z, z, p);
+      }
+    zzs[tid] = p;
+  }
+}
+// MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3 of a pixel tile from its xa view (lane (t, q) holds 16 NH channels of
+// pixel t).
+template <int NH>
+__device__ __forceinline__ void lds_pixel_norms(const float4 (&xa)[NH * 4], int q, float (&xx)[4]) {
+  float p = 0.f;
+#pragma unroll
+  for (int v = 0; v < NH * 4; ++v) {
+    p = fmaf(xa[v].x, xa[v].x, p);
+    p = fmaf(xa[v].y, xa[v].y, p);
+    p = fmaf(xa[v].z, xa[v].z, p);
+    p = fmaf(xa[v].w, xa[v].w, p);
+  }
+  p += __shfl_xor(p, 16);
+  p += __shfl_xor(p, 32);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) xx[r] = __shfl(p, 4 * q + r);
+}
+
+// NH = 2 (128-d fields as two 64-channel planes; kept a parameter so the kernel keeps its name): S sums over both
+// halves; the accumulators of one block cover ONE half (blockIdx.z), so S is computed twice — the price of keeping the
+// 64-d register tiling.
 // MS_EUCLIDEAN: W = exp(-kappa max(||z||^2 + ||x||^2 - 2 S, 0)) and per seed the weight sum, reduced in a fixed order
 // like the accumulators and stored (by the hz = 0 blocks) behind the partial sums: [batch][nvb][ST * 16].
 template <int ST, int NH, int MET>
 __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void hc_iter_kernel(const float *__restrict__ X, int n,
                                                              const float *__restrict__ Z, int m, float kappa,
                                                              float *__restrict__ partial_, int nvb) {
+  static_assert(NH == 2, "64-d fields run hc_iter_flat_kernel");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr bool EUC = MET == MS_EUCLIDEAN;
   __shared__ float zzs[EUC ? ST * 16 : 1];             // ||z||^2 per seed row
@@ -504,7 +550,7 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
   float *Zs = smem;  // [NH][ST*16][ZP]; later reused as the cross-wave reduction buffer
   const int b = blockIdx.y;
   const int nblk = nvb;                    // VIRTUAL blocks (hc_virtual_blocks: n only), walked by the physical ones
-  const int hz = NH > 1 ? blockIdx.z : 0;  // the half this block accumulates
+  const int hz = blockIdx.z;               // the half this block accumulates
   X += (size_t)b * NH * n * C;
   Z += (size_t)b * NH * m * C;
 
@@ -514,25 +560,11 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
   float *partial = partial_ + (((size_t)b * nblk + vb) * NH + hz) * (ST * 16) * C;
 
-  for (int i = tid; i < NH * ST * 16 * (C / 4); i += HC_THREADS) {
-    const int h = i / (ST * 16 * (C / 4)), j = i % (ST * 16 * (C / 4));
-    const int row = j / (C / 4), c4 = j % (C / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < m) v = *reinterpret_cast<const float4 *>(Z + ((size_t)h * m + row) * C + 4 * c4);
-    *reinterpret_cast<float4 *>(Zs + (h * ST * 16 + row) * ZP + 4 * c4) = v;
-  }
+  lds_stage_seeds<ST, NH>(Z, m, tid, Zs);
   __syncthreads();
   float ws[ST];
   if constexpr (EUC) {
-    if (tid < ST * 16) {
-      float p = 0.f;
-      for (int h = 0; h < NH; ++h)
-        for (int c = 0; c < C; ++c) {
-          const float z = Zs[(h * ST * 16 + tid) * ZP + c];
-          p = fmaf(z, z, p);
-        }
-      zzs[tid] = p;
-    }
+    lds_seed_norms<ST, NH>(Zs, tid, zzs);
 #pragma unroll
     for (int s = 0; s < ST; ++s) ws[s] = 0.f;
     __syncthreads();
@@ -566,8 +598,6 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
   load_tile(tile, xa, xb);
 
   for (; tile < ntile; tile += stride) {
-    float4 na[NH * 4], nb[4];
-    if (NH == 1) load_tile(tile + stride, na, nb);  // software prefetch of the wave's next tile
     // Software pipeline over the seed tiles (3 stages, fully unrolled): in step i the 16-deep
     // DEPENDENT MFMA chain S_i = X Z_i^T is interleaved 1:1 with the 16 INDEPENDENT accumulate MFMAs of
     // tile i-2 (hides the 40-cycle dependent-accumulator latency), while exp() of tile i-1 runs on the
@@ -580,23 +610,12 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     int zo = 0;
     asm volatile("" : "+v"(zo));
     const float *Zt = Zs + zo;
-    float xx[4];   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3 (lane (t, q) holds 16 NH channels of pixel t in xa)
+    float xx[4];   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3, XX_OUT beyond n
     if constexpr (EUC) {
-      float p = 0.f;
+      lds_pixel_norms<NH>(xa, q, xx);
 #pragma unroll
-      for (int v = 0; v < NH * 4; ++v) {
-        p = fmaf(xa[v].x, xa[v].x, p);
-        p = fmaf(xa[v].y, xa[v].y, p);
-        p = fmaf(xa[v].z, xa[v].z, p);
-        p = fmaf(xa[v].w, xa[v].w, p);
-      }
-      p += __shfl_xor(p, 16);
-      p += __shfl_xor(p, 32);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = __shfl(p, 4 * q + r);
-        xx[r] = tile * 16 + 4 * q + r < n ? v : XX_OUT;
-      }
+      for (int r = 0; r < 4; ++r)
+        if (tile * 16 + 4 * q + r >= n) xx[r] = XX_OUT;
     }
 #pragma unroll
     for (int i = 0; i < ST + 2; ++i) {
@@ -605,15 +624,15 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
           const float zz = zzs[16 * (i - 1) + t];
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            wv[i - 1][r] = UOC_EXP(-kappa * fmaxf(fmaf(-2.0f, Sv[i - 1][r], zz + xx[r]), 0.0f));
+            wv[i - 1][r] = expf(-kappa * fmaxf(fmaf(-2.0f, Sv[i - 1][r], zz + xx[r]), 0.0f));
           ws[i - 1] += (wv[i - 1][0] + wv[i - 1][1]) + (wv[i - 1][2] + wv[i - 1][3]);
         } else {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) wv[i - 1][r] = UOC_EXP(kappa * Sv[i - 1][r]);
+          for (int r = 0; r < 4; ++r) wv[i - 1][r] = expf(kappa * Sv[i - 1][r]);
         }
       }
       if (i < ST) Sv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (NH > 1 && i < ST) {  // second half of the dot products (not interleaved: 'cat' is the rare mode)
+      if (i < ST) {  // second half of the dot products (not interleaved: 'cat' is the rare mode)
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
           const int v = k >> 2, e = k & 3;
@@ -634,15 +653,7 @@ __global__ __launch_bounds__(HC_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
         }
       }
     }
-    if (NH == 1) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        xa[v] = na[v];
-        xb[v] = nb[v];
-      }
-    } else {
-      load_tile(tile + stride, xa, xb);  // no double buffering: the registers go to the second half of the row
-    }
+    load_tile(tile + stride, xa, xb);  // no double buffering: the registers go to the second half of the row
   }
 
   // ---- cross-wave reduction (fixed order: (w0 + w2) + (w1 + w3)) through LDS -------------
@@ -1503,28 +1514,14 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = lane & 15, q = lane >> 4;
-  for (int i = tid; i < NH * ST * 16 * (C / 4); i += HC_THREADS) {
-    const int h = i / (ST * 16 * (C / 4)), j = i % (ST * 16 * (C / 4));
-    const int row = j / (C / 4), c4 = j % (C / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < m) v = *reinterpret_cast<const float4 *>(Z + ((size_t)h * m + row) * C + 4 * c4);
-    *reinterpret_cast<float4 *>(Zs + (h * ST * 16 + row) * ZP + 4 * c4) = v;
-  }
+  lds_stage_seeds<ST, NH>(Z, m, tid, Zs);
   if (tid < NLAB) {
     slab[tid] = tid < m ? seed_labels[tid] : 0;
     hist[tid] = 0;
   }
   __syncthreads();
   if constexpr (MET == MS_EUCLIDEAN) {
-    if (tid < ST * 16) {
-      float p = 0.f;
-      for (int h = 0; h < NH; ++h)
-        for (int c = 0; c < C; ++c) {
-          const float z = Zs[(h * ST * 16 + tid) * ZP + c];
-          p = fmaf(z, z, p);
-        }
-      zzs[tid] = p;
-    }
+    lds_seed_norms<ST, NH>(Zs, tid, zzs);
     __syncthreads();
   }
 
@@ -1536,21 +1533,8 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
     for (int v = 0; v < NH * 4; ++v)
       xa[v] = (pa < n) ? *reinterpret_cast<const float4 *>(X + ((size_t)(v >> 2) * n + pa) * C + 16 * (v & 3) + 4 * q)
                        : make_float4(0.f, 0.f, 0.f, 0.f);
-    float xx[4] = {};   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3 (lane (t, q) holds 16 NH channels of pixel t)
-    if constexpr (MET == MS_EUCLIDEAN) {
-      float p = 0.f;
-#pragma unroll
-      for (int v = 0; v < NH * 4; ++v) {
-        p = fmaf(xa[v].x, xa[v].x, p);
-        p = fmaf(xa[v].y, xa[v].y, p);
-        p = fmaf(xa[v].z, xa[v].z, p);
-        p = fmaf(xa[v].w, xa[v].w, p);
-      }
-      p += __shfl_xor(p, 16);
-      p += __shfl_xor(p, 32);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xx[r] = __shfl(p, 4 * q + r);
-    }
+    float xx[4] = {};   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3
+    if constexpr (MET == MS_EUCLIDEAN) lds_pixel_norms<NH>(xa, q, xx);
     float bd[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
     int bi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
 #pragma unroll
@@ -1652,9 +1636,6 @@ struct MsWorkspace {
   size_t total;
 };
 
-// 64-d fields run the register-resident kernel (one wave per SIMD), 128-d fields the LDS-fragment kernel.
-static int hc_variant() { return 2; }
-
 // Virtual blocks of a hill-climbing launch: a function of the field size ONLY (about 16 pixel tiles per wave, at most 256
 // blocks of 4 waves), so the fp32 summation order of the new seed positions is the same whether a field is clustered
 // alone, with three other frames or among 30 crops.  (Round 2 derived the block count from the batch: a frame's label
@@ -1668,8 +1649,8 @@ static int hc_virtual_blocks(int n) {
   return nvb;
 }
 
-// Physical blocks per field: the count p that minimises (rounds of CUs the grid needs) x (virtual blocks per physical
-// block); one 4-wave block per CU (register-resident kernel) or two (LDS-fragment kernel).
+// Physical blocks per field of the LDS-fragment kernel (128-d fields): the count p that minimises (rounds of CUs the grid
+// needs) x (virtual blocks per physical block), with per_cu 4-wave blocks per CU.
 static int hc_physical_blocks(int batch, int nvb, int per_cu) {
   const int slots = (device_num_cu() > 0 ? device_num_cu() : 256) * per_cu;
   int best = 1;
@@ -1686,9 +1667,7 @@ static int hc_physical_blocks(int batch, int nvb, int per_cu) {
 }
 
 // grid of the per-pixel kernels that have no cross-pixel sums (assign): any block count gives the same result
-static int hc_blocks(int batch, int n, int nh = 1, bool lds_kernel = false) {
-  (void)nh;
-  (void)lds_kernel;
+static int hc_blocks(int batch, int n) {
   const int ntile = (n + 15) / 16;
   int nblk = 512 / (batch > 0 ? batch : 1);
   if (nblk < 8) nblk = 8;
@@ -1771,6 +1750,25 @@ static int fps_persistent_plan(int batch, int n, int *bpi, int *nslots) {
   return 1;
 }
 
+// Runtime shape -> template arguments: f(std::integral_constant<int, V>{}) for the V in Vs equal to v.  Callers pass only
+// validated values (the C entry points reject an unknown metric, halves or seed count), so exactly one V matches.
+template <int... Vs, class F>
+static void dispatch(int v, F &&f) {
+  (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+// f(MET, NH): the metric and the 64-channel halves of an embedding
+template <class F>
+static void dispatch_metric_halves(int met, int nh, F &&f) {
+  dispatch<MS_COSINE, MS_EUCLIDEAN>(met, [&](auto MET) { dispatch<1, 2>(nh, [&](auto NH) { f(MET, NH); }); });
+}
+// f(ST, NH, MET): also the seed tiles ST = ceil(m / 16) of the hill-climbing and assignment kernels
+template <class F>
+static void dispatch_shape(int met, int nh, int m, F &&f) {
+  dispatch_metric_halves(met, nh, [&](auto MET, auto NH) {
+    dispatch<1, 2, 3, 4, 5, 6, 7, 8>((m + 15) / 16, [&](auto ST) { f(ST, NH, MET); });
+  });
+}
+
 static int run_select_seeds_streaming(const float *X, int batch, int n, int m, const int32_t *first, float *seeds,
                                       int32_t *indices, const MsWorkspace &w, hipStream_t st, int num_init = 0,
                                       int met = MS_COSINE);
@@ -1796,8 +1794,9 @@ static FpsChain &fps_chain() {
 
 static int run_select_seeds(const float *X, int batch, int n, int m, const int32_t *first, float *seeds,
                             int32_t *indices, const MsWorkspace &w, hipStream_t st, int met = MS_COSINE) {
-  const void *fpp = met == MS_EUCLIDEAN ? reinterpret_cast<const void *>(&fps_persistent_kernel<MS_EUCLIDEAN>)
-                                        : reinterpret_cast<const void *>(&fps_persistent_kernel<MS_COSINE>);
+  const void *fpp = nullptr;
+  dispatch<MS_COSINE, MS_EUCLIDEAN>(met,
+                                    [&](auto MET) { fpp = reinterpret_cast<const void *>(&fps_persistent_kernel<MET>); });
   // Persistent path: as many items per cooperative launch as stay co-resident; a larger batch
   // (stage 2 with > 8 ROIs) is split into several launches rather than dropped to the streaming kernel.
   int done = 0;
@@ -1872,21 +1871,16 @@ static int run_select_seeds(const float *X, int batch, int n, int m, const int32
 static int run_select_seeds_streaming(const float *X, int batch, int n, int m, const int32_t *first, float *seeds,
                                       int32_t *indices, const MsWorkspace &w, hipStream_t st, int num_init, int met) {
   const int nblk = fps_blocks(n);
-  for (int s = 0; s < m; ++s) {
-    dim3 grid(nblk, batch);  // gridDim.x doubles as the partial count, so it is the same every step
-    const bool last = s == m - 1;
-    ProfScope prof(KC_FPS_STEP, st, last ? 0.0 : 2.0 * batch * n * C * w.nh,
-                   last ? 0.0 : 4.0 * batch * ((double)n * C * w.nh + 2.0 * n));
-#define UOC_FPS_STEP(NH_, MET_)                                                                                       \
-  hipLaunchKernelGGL((fps_step_kernel<NH_, MET_>), grid, dim3(FPS_THREADS), 0, st, X, n, m, s, num_init, first, w.dmin, \
-                     seeds, indices, w.part[(s + 1) & 1], w.part[s & 1])
-    if (met == MS_EUCLIDEAN) {
-      if (w.nh == 2) UOC_FPS_STEP(2, MS_EUCLIDEAN); else UOC_FPS_STEP(1, MS_EUCLIDEAN);
-    } else {
-      if (w.nh == 2) UOC_FPS_STEP(2, MS_COSINE); else UOC_FPS_STEP(1, MS_COSINE);
+  dispatch_metric_halves(met, w.nh, [&](auto MET, auto NH) {
+    for (int s = 0; s < m; ++s) {
+      dim3 grid(nblk, batch);  // gridDim.x doubles as the partial count, so it is the same every step
+      const bool last = s == m - 1;
+      ProfScope prof(KC_FPS_STEP, st, last ? 0.0 : 2.0 * batch * n * C * w.nh,
+                     last ? 0.0 : 4.0 * batch * ((double)n * C * w.nh + 2.0 * n));
+      hipLaunchKernelGGL((fps_step_kernel<NH, MET>), grid, dim3(FPS_THREADS), 0, st, X, n, m, s, num_init, first, w.dmin,
+                         seeds, indices, w.part[(s + 1) & 1], w.part[s & 1]);
     }
-#undef UOC_FPS_STEP
-  }
+  });
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -1962,53 +1956,51 @@ static HcPlan hc_make_plan(int batch, int nvb, bool splittable) {
 template <int ST, int NH, int MET>
 static void launch_hc(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
                       const MsWorkspace &w, hipStream_t st) {
-  const size_t zbytes = (size_t)NH * ST * 16 * ZP * sizeof(float);
-  const size_t rbytes = (size_t)2 * ST * 4 * 64 * sizeof(f32x4);
-  const size_t lds = zbytes > rbytes ? zbytes : rbytes;
-  static DeviceOnce attr_set;
-  if (!attr_set.done() && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_kernel<ST, NH, MET>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set.mark();
-  }
-  const bool reg = NH == 1 && hc_variant() == 2;   // register-resident kernel, one wave per SIMD
-  const size_t lds_reg = (size_t)4 * ST * 4 * 64 * sizeof(f32x4) + (MET == MS_EUCLIDEAN ? (size_t)4 * ST * 16 * sizeof(float) : 0);
   const int nvb = w.hc_nblk;
   const int last = m - 16 * (ST - 1);                  // seeds in the last tile
   const bool quad = ST >= 2 && last >= 1 && last <= 4;   // they run on the 4x4x1 MFMA instead of a padded 16-seed tile
   HcPlan plan = {};
-  if constexpr (NH == 1) {
-    if (reg) {
-      plan = hc_make_plan(batch, nvb, ST == 7 && quad);
-      static DeviceOnce attr_reg;
-      if (!attr_reg.done() && lds_reg > 64 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, false, MET>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
+  int phys;
+  size_t lds;
+  if constexpr (NH == 1) {   // 64-d fields: the register-resident kernel, one wave per SIMD
+    plan = hc_make_plan(batch, nvb, ST == 7 && quad);
+    phys = plan.grid;
+    lds = (size_t)4 * ST * 4 * 64 * sizeof(f32x4) + (MET == MS_EUCLIDEAN ? (size_t)4 * ST * 16 * sizeof(float) : 0);
+    static DeviceOnce attr_set;
+    if (!attr_set.done() && lds > 64 * 1024) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, false, MET>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if constexpr (ST >= 2)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, true, MET>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
-        attr_reg.mark();
-      }
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set.mark();
+    }
+  } else {                   // 128-d fields: the LDS-fragment kernel
+    phys = hc_physical_blocks(batch, nvb, 2);
+    const size_t zbytes = (size_t)NH * ST * 16 * ZP * sizeof(float);
+    const size_t rbytes = (size_t)2 * ST * 4 * 64 * sizeof(f32x4);
+    lds = zbytes > rbytes ? zbytes : rbytes;
+    static DeviceOnce attr_set;
+    if (!attr_set.done() && lds > 64 * 1024) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_kernel<ST, NH, MET>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set.mark();
     }
   }
-  const int phys = reg ? plan.grid : hc_physical_blocks(batch, nvb, 2);
   for (int it = 0; it < iters; ++it) {
     {
       // NH = 2 recomputes S for each half of the accumulators: (2 + 1) / 2 of the algorithmic flops per half
       ProfScope prof(KC_HC_ITER, st, 4.0 * batch * m * (double)n * C * NH,
                      4.0 * batch * ((double)n * C * NH + 2.0 * m * C * NH), ProfTag{{n, batch, nvb, phys}});
-      if constexpr (NH == 1) {
-        if (reg) {
-          if (quad)
-            hipLaunchKernelGGL((hc_iter_flat_kernel<ST, true, MET>), dim3(plan.grid), dim3(256), lds_reg, st, X, n, Z, m,
-                               kappa, w.hc_partial, plan);
-          else
-            hipLaunchKernelGGL((hc_iter_flat_kernel<ST, false, MET>), dim3(plan.grid), dim3(256), lds_reg, st, X, n, Z, m,
-                               kappa, w.hc_partial, plan);
-        }
-      }
-      if (!reg)
+      if constexpr (NH == 2)
         hipLaunchKernelGGL((hc_iter_kernel<ST, NH, MET>), dim3(phys, batch, NH), dim3(HC_THREADS), lds, st, X, n, Z, m,
                            kappa, w.hc_partial, nvb);
+      else if (!quad)
+        hipLaunchKernelGGL((hc_iter_flat_kernel<ST, false, MET>), dim3(plan.grid), dim3(256), lds, st, X, n, Z, m, kappa,
+                           w.hc_partial, plan);
+      else if constexpr (ST >= 2)
+        hipLaunchKernelGGL((hc_iter_flat_kernel<ST, true, MET>), dim3(plan.grid), dim3(256), lds, st, X, n, Z, m, kappa,
+                           w.hc_partial, plan);
     }
     ProfScope prof(KC_HC_FINALIZE, st, 0.0, 4.0 * batch * w.hc_nblk * NH * ST * 16.0 * C);
     hipLaunchKernelGGL((hc_finalize_kernel<NH, MET>), dim3(m, batch), dim3(256), 0, st, w.hc_partial, w.hc_nblk, ST * 16,
@@ -2016,32 +2008,11 @@ static void launch_hc(const float *X, int batch, int n, float *Z, int m, float k
   }
 }
 
-template <int NH, int MET>
-static void run_hill_climb_nh(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
-                              const MsWorkspace &w, hipStream_t st) {
-  switch ((m + 15) / 16) {
-    case 1: launch_hc<1, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 2: launch_hc<2, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 3: launch_hc<3, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 4: launch_hc<4, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 5: launch_hc<5, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 6: launch_hc<6, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    case 7: launch_hc<7, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-    default: launch_hc<8, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st); break;
-  }
-}
-
 static int run_hill_climb(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
                           const MsWorkspace &w, hipStream_t st, int met = MS_COSINE) {
-  if (met == MS_EUCLIDEAN) {
-    if (w.nh == 2)
-      run_hill_climb_nh<2, MS_EUCLIDEAN>(X, batch, n, Z, m, kappa, iters, w, st);
-    else
-      run_hill_climb_nh<1, MS_EUCLIDEAN>(X, batch, n, Z, m, kappa, iters, w, st);
-  } else if (w.nh == 2)
-    run_hill_climb_nh<2, MS_COSINE>(X, batch, n, Z, m, kappa, iters, w, st);
-  else
-    run_hill_climb_nh<1, MS_COSINE>(X, batch, n, Z, m, kappa, iters, w, st);
+  dispatch_shape(met, w.nh, m, [&](auto ST, auto NH, auto MET) {
+    launch_hc<ST, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st);
+  });
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -2049,7 +2020,7 @@ static int run_hill_climb(const float *X, int batch, int n, float *Z, int m, flo
 template <int ST, int NH, int MET>
 static void launch_assign(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m,
                           int *labels, int *closest, const MsWorkspace &w, hipStream_t st) {
-  int nblk = hc_blocks(batch, n, 1, true) * 2;
+  int nblk = hc_blocks(batch, n) * 2;
   const int maxb = ((n + 15) / 16 + 3) / 4;
   if (nblk > maxb) nblk = maxb;
   const size_t lds = (size_t)NH * ST * 16 * ZP * sizeof(float);
@@ -2064,34 +2035,13 @@ static void launch_assign(const float *X, int batch, int n, const float *Z, cons
                      labels, closest, w.counts);
 }
 
-template <int NH, int MET>
-static void run_assign_nh(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m, int *labels,
-                          int *closest, const MsWorkspace &w, hipStream_t st) {
-  switch ((m + 15) / 16) {
-    case 1: launch_assign<1, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 2: launch_assign<2, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 3: launch_assign<3, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 4: launch_assign<4, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 5: launch_assign<5, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 6: launch_assign<6, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    case 7: launch_assign<7, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-    default: launch_assign<8, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st); break;
-  }
-}
-
 static int run_assign(const float *X, int batch, int n, const float *Z, const int *seed_labels,
                       const int *num_unique, int m, int *labels, int *closest, const MsWorkspace &w,
                       hipStream_t st, int met = MS_COSINE) {
   UOC_HIP_CHECK(hipMemsetAsync(w.counts, 0, (size_t)batch * NLAB * sizeof(int), st));
-  if (met == MS_EUCLIDEAN) {
-    if (w.nh == 2)
-      run_assign_nh<2, MS_EUCLIDEAN>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
-    else
-      run_assign_nh<1, MS_EUCLIDEAN>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
-  } else if (w.nh == 2)
-    run_assign_nh<2, MS_COSINE>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
-  else
-    run_assign_nh<1, MS_COSINE>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+  dispatch_shape(met, w.nh, m, [&](auto ST, auto NH, auto MET) {
+    launch_assign<ST, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+  });
   int rb = (n + 255) / 256;
   if (rb > 512) rb = 512;
   ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n);
@@ -2100,29 +2050,29 @@ static int run_assign(const float *X, int batch, int n, const float *Z, const in
   return UOC_OK;
 }
 
-template <int MET>
-static int launch_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique, int nh,
+template <int NH, int MET>
+static int launch_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique,
                           hipStream_t st) {
-  const size_t lds = (size_t)NLAB * (nh * C + 1) * sizeof(float);
-  if (nh == 2) {
+  const size_t lds = (size_t)NLAB * (NH * C + 1) * sizeof(float);
+  if constexpr (NH == 2) {   // more than 64 KB
     static DeviceOnce attr_set;
     if (!attr_set.done()) {
-      UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&seed_cc_kernel<2, MET>),
+      UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&seed_cc_kernel<NH, MET>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       attr_set.mark();
     }
-    hipLaunchKernelGGL((seed_cc_kernel<2, MET>), dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
-  } else {
-    hipLaunchKernelGGL((seed_cc_kernel<1, MET>), dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
   }
+  hipLaunchKernelGGL((seed_cc_kernel<NH, MET>), dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
   return UOC_OK;
 }
 
 static int run_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique, int nh,
                        hipStream_t st, int met = MS_COSINE) {
   ProfScope prof(KC_SEED_CC, st, 0.0, 4.0 * batch * m * C * nh);
-  const int rc = met == MS_EUCLIDEAN ? launch_seed_cc<MS_EUCLIDEAN>(Z, batch, m, eps, seed_labels, num_unique, nh, st)
-                                     : launch_seed_cc<MS_COSINE>(Z, batch, m, eps, seed_labels, num_unique, nh, st);
+  int rc = UOC_OK;
+  dispatch_metric_halves(met, nh, [&](auto MET, auto NH) {
+    rc = launch_seed_cc<NH, MET>(Z, batch, m, eps, seed_labels, num_unique, st);
+  });
   if (rc) return rc;
   UOC_LAUNCH_CHECK();
   return UOC_OK;

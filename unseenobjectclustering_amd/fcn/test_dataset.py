@@ -65,6 +65,15 @@ def _detach_keep_planes(features: torch.Tensor) -> torch.Tensor:
     return features
 
 
+def _kernel_layout(features: torch.Tensor) -> torch.Tensor:
+    """[B,C,h,w] features -> the layout of cluster_batch: [B, h*w, 64], or the planes [B, 2, h*w, 64] of 128-d fields."""
+    planes = getattr(features, "_uoc_planes", None)     # 128-d output of SEGNET ('cat' fusion): already in kernel layout
+    if planes is not None and planes.shape[0] == features.shape[0]:
+        return planes
+    X = _pixel_major(features.float())
+    return to_planes(X) if X.shape[-1] == 128 else X
+
+
 def _cluster_device(features: torch.Tensor, num_seeds: int = 100, rng=None):
     """Device-resident clustering of every batch item: int32 labels [B, h*w], indices [B, m].
     `rng`: where the first-seed draws come from — the global NumPy RNG like the reference (mean_shift.py:155), or a
@@ -72,13 +81,7 @@ def _cluster_device(features: torch.Tensor, num_seeds: int = 100, rng=None):
     require_supported()
     if not features.is_cuda:
         raise _native.NativeError("features must be on a ROCm device (no CPU fallback)")
-    planes = getattr(features, "_uoc_planes", None)     # 128-d output of SEGNET ('cat' fusion): already in kernel layout
-    if planes is not None and planes.shape[0] == features.shape[0]:
-        X = planes
-    else:
-        X = _pixel_major(features.float())
-        if X.shape[-1] == 128:
-            X = to_planes(X)
+    X = _kernel_layout(features)
     B, n = X.shape[0], X.shape[-2]
     draw = (rng if rng is not None else np.random).randint
     firsts = [draw(0, n) for _ in range(B)]                # mean_shift.py:155, one draw per field, in order
@@ -620,14 +623,7 @@ class FrameGroupJob:
 
 def _cluster_fields(features, firsts):
     """Clusters the B fields of `features` [B,C,h,w] with the given first-seed indices -> int32 labels [B, h*w]."""
-    planes = getattr(features, "_uoc_planes", None)
-    if planes is not None and planes.shape[0] == features.shape[0]:
-        X = planes
-    else:
-        X = _pixel_major(features.float())
-        if X.shape[-1] == 128:
-            X = to_planes(X)
-    labels, _ = cluster_batch(X, firsts, KAPPA, 100, MAX_ITERS, 2 * cfg.TRAIN.EMBEDDING_ALPHA)
+    labels, _ = cluster_batch(_kernel_layout(features), firsts, KAPPA, 100, MAX_ITERS, 2 * cfg.TRAIN.EMBEDDING_ALPHA)
     return labels
 
 

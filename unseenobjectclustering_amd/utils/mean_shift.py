@@ -96,35 +96,11 @@ def cluster_batch(X: torch.Tensor, first_index, kappa: float = 20.0, num_seeds: 
     """
     met = _metric(cfg.TRAIN.EMBEDDING_METRIC if metric is None else metric)
     X = _check_points(X)
-    if X.dim() == 4:
-        return _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, return_parts, met)
-    assert X.dim() == 3
-    B, n, _ = X.shape
-    if epsilon is None:
-        epsilon = 2 * cfg.TRAIN.EMBEDDING_ALPHA
-    dev = X.device
-    L = _native.lib()
-    first = _first_indices(first_index, B, n).to(dev, non_blocking=True)
-    labels = torch.empty((B, n), dtype=torch.int32, device=dev)
-    indices = torch.empty((B, num_seeds), dtype=torch.int32, device=dev)
-    Z = torch.empty((B, num_seeds, EMBED_DIM), dtype=torch.float32, device=dev)
-    seed_labels = torch.empty((B, num_seeds), dtype=torch.int32, device=dev)
-    nbytes = L.uoc_ms_workspace_bytes(B, n, num_seeds)
-    ws = _workspace(dev, nbytes)
-    with torch.cuda.device(dev):
-        rc = L.uoc_ms_cluster_ex(_native.ptr(X), B, n, num_seeds, float(kappa), int(max_iters), float(epsilon), met,
-                                 _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
-                                 _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_cluster_ex")
-    if return_parts:
-        return labels, indices, Z, seed_labels
-    return labels, indices
-
-
-def _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, return_parts, met):
-    B, H2, n, _ = X.shape
-    if H2 != 2:
+    assert X.dim() in (3, 4)
+    H = 1 if X.dim() == 3 else X.shape[1]        # 64-channel halves: [B, n, 64] or the planes [B, 2, n, 64]
+    if X.dim() == 4 and H != 2:
         raise NotImplementedError("embedding dimension must be 64 or 128 (two 64-channel planes)")
+    B, n = X.shape[0], X.shape[-2]
     if epsilon is None:
         epsilon = 2 * cfg.TRAIN.EMBEDDING_ALPHA
     dev = X.device
@@ -132,11 +108,11 @@ def _cluster_batch_wide(X, first_index, kappa, num_seeds, max_iters, epsilon, re
     first = _first_indices(first_index, B, n).to(dev, non_blocking=True)
     labels = torch.empty((B, n), dtype=torch.int32, device=dev)
     indices = torch.empty((B, num_seeds), dtype=torch.int32, device=dev)
-    Z = torch.empty((B, H2, num_seeds, EMBED_DIM), dtype=torch.float32, device=dev)
+    Z = torch.empty(X.shape[:-2] + (num_seeds, EMBED_DIM), dtype=torch.float32, device=dev)
     seed_labels = torch.empty((B, num_seeds), dtype=torch.int32, device=dev)
-    ws = _workspace(dev, L.uoc_ms_workspace_bytes_wide(B, n, num_seeds, H2))
+    ws = _workspace(dev, L.uoc_ms_workspace_bytes_wide(B, n, num_seeds, H))
     with torch.cuda.device(dev):
-        rc = L.uoc_ms_cluster_wide_ex(_native.ptr(X), H2, B, n, num_seeds, float(kappa), int(max_iters), float(epsilon),
+        rc = L.uoc_ms_cluster_wide_ex(_native.ptr(X), H, B, n, num_seeds, float(kappa), int(max_iters), float(epsilon),
                                       met, _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
                                       _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
     _native.check(rc, "uoc_ms_cluster_wide_ex")
