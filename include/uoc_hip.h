@@ -326,6 +326,46 @@ int uoc_objects(const int32_t *d_labels, const float *d_xyz, const float *d_attr
 
 
 /* ------------------------------------------------------------------------------------------
+ * Object tracking across the frames of a stream (no reference counterpart): each raw label map
+ * becomes a tracked label map whose ids are track slots 1..127.  An object keeps its slot while it is in view and gets
+ * it back after an occlusion of at most max_age frames.  Object ids are 1..127, every other value is background.
+ * All arithmetic is integer: the result is defined exactly and does not depend on launch order or batch.
+ *
+ * State per stream (caller-owned device memory, uoc_track_state_bytes(B, H, W) / B bytes each, stream b at byte offset
+ * b * that; 16-byte aligned): int32 [1024] header = the slot table uoc_track[128] (slot 0 unused), then at word 640 the
+ * number of uids handed out (next uid = that + 1), the step counter and the sticky count of dropped objects;
+ * int32 [128*128] contingency scratch (all zero between steps); int32 [H*W] memory map (for every live track the
+ * pixels of its last sighting that no later object has covered).  An all-zero state is a reset stream.
+ *
+ * One step with the raw map L: cont[t][c] = #pixels with mem == t and L == c; candidates are pairs of a live track t
+ * and a present id c with inter = cont[t][c] > 0 and inter * 65536 >= q * union, union = area_mem[t] + area_cur[c] -
+ * inter; greedy matching takes the candidate of largest IoU among unmatched t and c (exact comparison by 64-bit cross
+ * multiplication; ties: larger inter, lower t, lower c) until none is left; a matched track gets age 0, hits + 1, the
+ * id's area; an unmatched one age + 1 and is retired (record zeroed) when age > max_age; unmatched ids in ascending
+ * order take the free slots in ascending order (a slot retired in this step included) with uid = next uid, hits 1,
+ * born = step; without a free slot the object becomes background and `dropped` grows.  out = slot of L (0 = background);
+ * mem' = out where out != 0, else mem where its track was live, is unmatched and was not retired, else 0.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct uoc_track {
+  int32_t uid;    /* 0 = free slot; else the stream's running object number 1, 2, 3, ..., never reused */
+  int32_t age;    /* frames since the last match (0 = matched in the last step)                         */
+  int32_t hits;   /* frames in which the track was matched (the birth included)                         */
+  int32_t area;   /* pixels at the last match                                                           */
+  int32_t born;   /* step index of the birth                                                            */
+} uoc_track;
+
+size_t uoc_track_state_bytes(int B, int H, int W);
+size_t uoc_track_workspace_bytes(int B);
+/* Zeroes the state of stream `which`, or of all B streams when which = -1. */
+int uoc_track_reset(void *d_state, int B, int H, int W, int which, void *stream);
+/* d_labels, d_out [B][H*W] int32 (distinct buffers); q = round(min_iou * 65536) in [1, 65536]; max_age >= 0;
+ * d_lut (nullable) [B][128]: raw id -> slot of this step; d_tracks (nullable) [B][128]: the slot table after the step.
+ * H*W must be below 2^31.  Three launches on `stream`, nothing synchronises. */
+int uoc_track_step(const int32_t *d_labels, int B, int H, int W, int q, int max_age, void *d_state, int32_t *d_out,
+                   int32_t *d_lut, uoc_track *d_tracks, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

@@ -4,11 +4,17 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
 
     python tools/export_objects.py --imgdir tests/golden/demo --out objs/ [--max-points 2048]
                                    [--pretrained ckpt.pth --pretrained_crop crop.pth] [--cfg experiments/cfgs/<experiment>.yml]
+                                   [--track [--track-min-iou 0.3] [--track-max-age 5]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
 `obb_half`) and the packed clouds (`points`, `pixel_index`, `offsets`: object k is points[offsets[k]:offsets[k+1]]).
 Without checkpoints the calibrated synthetic weights are used (test_images.load_weights).
+
+With --track the frames are taken as one stream in file order: every final label map goes through the device-side tracker
+(unseenobjectclustering_amd/tracking.py) and the objects are extracted from the TRACKED map, so `label` is the track slot
+an object keeps from frame to frame, `label_map` the tracked map, `raw_label_map` the segmentation's own numbering and
+`track_uid` the stream-wide object number of every row.
 """
 import argparse
 import glob
@@ -25,7 +31,8 @@ import torch  # noqa: E402
 from test_images import load_weights  # noqa: E402
 from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
-from unseenobjectclustering_amd.objects import segment_objects  # noqa: E402
+from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
+from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
           "obb_center", "obb_half", "offsets", "points", "pixel_index")
@@ -42,6 +49,9 @@ def main():
     ap.add_argument("--cfg", dest="cfg_file", default=None, help="experiment yml")
     ap.add_argument("--out", required=True, help="output directory for <frame>_objects.npz")
     ap.add_argument("--max-points", type=int, default=0, help="points kept per object (0 = all)")
+    ap.add_argument("--track", action="store_true", help="stable ids across the frames (taken in file order)")
+    ap.add_argument("--track-min-iou", type=float, default=0.3)
+    ap.add_argument("--track-max-age", type=int, default=5)
     args = ap.parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
@@ -58,12 +68,22 @@ def main():
     network = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained)).eval()
     network_crop = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained_crop)).eval()
     os.makedirs(args.out, exist_ok=True)
+    tracker = Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None
     for fc, fd in zip(colors, depths):
         sample = uio.read_sample(fc, fd, cam)
         out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
         final = out_refined if out_refined is not None else out_label
+        track_uid = raw_map = None
+        if tracker is not None:
+            raw_map = final[0].numpy().astype(np.int32)
+            tracked = tracker.update(final[0].to(cfg.device))
+            objs = extract_objects(tracked, sample["depth"][:1].to(cfg.device), max_points_per_object=args.max_points)
+            track_uid = tracker.table[0, :, 0][objs.label.long()].cpu().numpy()
+            final = tracked[None].cpu()
         rec = {k: getattr(objs, k).cpu().numpy() for k in FIELDS}
         rec["label_map"] = final[0].numpy().astype(np.int32)
+        if tracker is not None:
+            rec["raw_label_map"], rec["track_uid"] = raw_map, track_uid
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")

@@ -96,6 +96,14 @@ def _declare(lib):
     lib.uoc_objects_workspace_bytes.restype = c_size_t
     lib.uoc_objects.argtypes = [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, ctypes.c_long, P, P, c_size_t, P]
     lib.uoc_objects.restype = c_int
+    lib.uoc_track_state_bytes.argtypes = [c_int, c_int, c_int]
+    lib.uoc_track_state_bytes.restype = c_size_t
+    lib.uoc_track_workspace_bytes.argtypes = [c_int]
+    lib.uoc_track_workspace_bytes.restype = c_size_t
+    lib.uoc_track_reset.argtypes = [P, c_int, c_int, c_int, c_int, P]
+    lib.uoc_track_reset.restype = c_int
+    lib.uoc_track_step.argtypes = [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]
+    lib.uoc_track_step.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -132,7 +140,8 @@ EXPORTED_SYMBOLS = (
     "uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_workspace_bytes",
     "uoc_net_forward", "uoc_net_set_split_precision", "uoc_conv2d_nhwc", "uoc_conv2d_nhwc_algo",
     "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
-    "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
+    "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -152,6 +161,18 @@ class UocObject(ctypes.Structure):
 
 
 OBJECT_BYTES = ctypes.sizeof(UocObject)
+
+
+class UocTrack(ctypes.Structure):
+    """Mirror of uoc_track (include/uoc_hip.h): one per (stream, slot)."""
+    _fields_ = [("uid", c_int32), ("age", c_int32), ("hits", c_int32), ("area", c_int32), ("born", c_int32)]
+
+
+TRACK_FIELDS = tuple(name for name, _ in UocTrack._fields_)
+TRACK_SLOTS = 128               # slot 0 is never a track
+TRACK_HEADER_WORDS = 1024       # int32 words of a stream's state before its contingency scratch (include/uoc_hip.h)
+TRACK_META_WORD = 640           # ... of which words 640, 641, 642 = uids handed out, step, dropped
+TRACK_CONT_WORDS = 128 * 128
 OBJECTS_MAX_ATTR = 8        # include/uoc_hip.h: UOC_OBJECTS_MAX_ATTR
 
 
