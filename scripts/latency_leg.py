@@ -1,6 +1,6 @@
 """One frame at a time on one stream (BASELINE configs[3] read literally, bench.py's `latency` leg) in isolation: resident
 frames, full two-stage path, host waiting for each uint8 label map.  --graph 1 replays hipGraphs (fcn/graph_replay.py),
-0 runs the eager FrameJob.  Run it under `rocprofv3 --kernel-trace` for scripts/rocpd_gaps.py / rocpd_stats.py.
+0 runs the eager FrameGroupJob.  Run it under `rocprofv3 --kernel-trace` for scripts/rocpd_gaps.py / rocpd_stats.py.
     python scripts/latency_leg.py --frames 12 --reps 4 --graph 1"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""Round 6: one frame at a time as hipGraph replays (fcn/graph_replay.py) against the eager FrameJob path — the same
+"""Round 6: one frame at a time as hipGraph replays (fcn/graph_replay.py) against the eager FrameGroupJob path — the same
 kernels in the same order, so both label maps must be torch.equal and the NumPy RNG must be left in the same state
 (1 + K draws per frame, lib/utils/mean_shift.py:155 through lib/fcn/test_dataset.py:247-261).  Frames with K = 0 (no
 ROI: stage 2 skipped, refined is None), K = 1 and several K; every K is seen twice so that both the first-use path (eager

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.golden.cases import e2e_stub_features
 from unseenobjectclustering_amd import _native, networks, runner, synth
 from unseenobjectclustering_amd.fcn.config import cfg
 
@@ -149,3 +150,47 @@ def test_host_order_and_the_rerun_when_the_device_ordering_flags_a_block(device)
     got = runner.run_sharded(6, fn3, 240, 320, device, 0, 1, False, inflight=3).cpu()
     assert seen == [False, True] and TD.FORCE_HOST_ORDER is was
     assert torch.equal(got, want) and list(fn3.roi_counts) == counts
+
+
+def test_group_job_equals_one_frame_at_a_time_at_a_small_shape(device):
+    """FrameGroupJob, the one job class of the two-stage path, at the smallest useful shape: three 120x160 single-image frames
+    (one with an all-zero z plane: every label fails the depth filter, K = 0) as ONE job with a RandomState per frame,
+    against _run_frame on each frame alone with the global NumPy RNG seeded alike.  torch.equal maps, equal ROI counts, and
+    the next draw of both RNGs is equal: both paths consumed 1 + K_f draws, in the same order.  Then the same job with the
+    ROI ordering on the host.
+    Stub networks (4 objects in stage 1, 2 per crop) that pick their field from the CONTENT of an item — a tag in the
+    image's first pixel, the sum of the integer mask crop — and not from its position in the batch, which differs between
+    the two paths."""
+    from unseenobjectclustering_amd.fcn import test_dataset as TD
+    cfg.device = device
+    H, W, S = 120, 160, int(cfg.TRAIN.SYN_CROP_SIZE)
+    fields = [e2e_stub_features(300 + f, H, W, 4).to(device) for f in range(3)]
+    pool = [e2e_stub_features(400 + k, S, S, 2).to(device) for k in range(3)]
+    s1 = lambda i, l, d: torch.cat([fields[int(i[j, 0, 0, 0])] for j in range(i.shape[0])])
+    s2 = lambda i, l, d: torch.cat([pool[int(l[j].sum()) % 3] for j in range(i.shape[0])])
+    samples, seeds = [], (7001, 7002, 7003)
+    for f in range(3):
+        fr = synth.rgbd_frame(81 + f, H, W, 3)
+        img, dep = torch.from_numpy(fr["image_color"]).clone(), torch.from_numpy(fr["depth"]).clone()
+        img[0, 0, 0, 0] = float(f)
+        if f == 1:
+            dep[:, 2] = 0.0
+        samples.append(dict(image_color=img.to(device), depth=dep.to(device)))
+    want = []
+    for sm, seed in zip(samples, seeds):
+        np.random.seed(seed)
+        labels, refined = TD._run_frame(sm, s1, s2, TD.DEPTH_FILTER, return_device=True, checked=True)
+        want.append(((refined if refined is not None else labels)[0].clone(), TD.LAST_FRAME_STATS["rois"], np.random.randint(0, 1 << 30)))
+    Ks = [w[1] for w in want]
+    assert Ks[1] == 0 and Ks[0] >= 1 and Ks[2] >= 1, Ks
+    for host_order in (False, True):
+        rngs = [np.random.RandomState(seed) for seed in seeds]
+        job = TD.FrameGroupJob(samples, s1, s2, TD.DEPTH_FILTER, rngs, host_order=host_order)
+        job.stage1()
+        job.stage2()
+        maps = job.final_maps()
+        TD._finish_block(device)
+        assert job.K == Ks, (host_order, job.K, Ks)
+        for f in range(3):
+            assert maps[f].shape == (H, W) and torch.equal(maps[f], want[f][0]), f"host_order={host_order}: frame {f} differs"
+            assert rngs[f].randint(0, 1 << 30) == want[f][2], f"host_order={host_order}: frame {f} did not consume 1 + {Ks[f]} draws"

@@ -249,15 +249,15 @@ def test_device_roi_order_is_pythons_sorted(device, with_depth):
                 dep_d = depth.to(device) if with_depth else None
                 want, keep_w = TD._match_host_order(lab_d, mask_d, dep_d, table, K, H, W, device)
                 got, keep_g = TD._match_device(lab_d, mask_d, dep_d, table, K, H, W, device, want_keep=True)
-                assert not TD._order_needs_host(device), (K, nan_rate, tie)
+                assert not TD._take_order_flag(TD._status_word(device)), (K, nan_rate, tie)
                 assert torch.equal(keep_w.cpu(), keep_g.cpu())
                 assert torch.equal(want.cpu(), got.cpu()), (K, nan_rate, tie, rep)
         if with_depth:
             labels, mask, depth, t = _order_case(rng, 70, 8, 0.5, 0)
             table = torch.frombuffer(bytearray(bytes(t)), dtype=torch.uint8).to(device)
             TD._match_device(labels.to(device), mask.to(device), depth.to(device), table, 70, H, W, device)
-            assert TD._order_needs_host(device), "NaN keys with >= 64 ROIs must be flagged for the host path"
-            assert not TD._order_needs_host(device), "the flag is cleared by reading it"
+            assert TD._take_order_flag(TD._status_word(device)), "NaN keys with >= 64 ROIs must be flagged for the host path"
+            assert not TD._take_order_flag(TD._status_word(device)), "the flag is cleared by reading it"
             # ... and match_label_crop (the reference-surface entry) takes that path by itself
             rois = torch.tensor([[t.box[k][i] for i in range(4)] for k in range(70)], dtype=torch.float32)
             init = torch.zeros(1, H, W)

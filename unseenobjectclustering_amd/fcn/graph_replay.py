@@ -9,8 +9,9 @@ A frame is TWO graph launches with ONE small device->host read between them:
               indices from the caller's RNG (mean_shift.py:155: 1 + K draws per frame, in the reference's order)
     graph 2[K] crop K ROIs -> network_crop -> K mean shifts -> match statistics, ROI order, renumbering, paste (device)
 
-What is replayed is exactly the eager path's launch sequence (the same Python functions run under stream capture), so
-the label maps are bit-identical to FrameJob's (tests/test_graph_replay_gpu.py: torch.equal).  Graph 2 is captured
+What is replayed is exactly the eager path's launch sequence (test_dataset._stage1_launches / _stage2_launches, the two
+functions FrameGroupJob calls, run under stream capture on static buffers), so the label maps are bit-identical to the eager
+job's (tests/test_graph_replay_gpu.py: torch.equal).  Graph 2 is captured
 lazily per K; the first frame with a new K runs eagerly (that run is also the warm-up that sizes the workspaces and lets
 the convolution tuner look its shapes up) and captures for the next time.
 
@@ -25,12 +26,11 @@ cooperative launch, no cross-stream event chain), so replays must not overlap ot
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _native
+from . import test_dataset as TD
 from .config import cfg, uses_depth
 
 MAX_ROIS = 127
@@ -59,38 +59,21 @@ class GraphedFrame:
         self.g1 = None
         self.g2 = {}
         self.calls = 0
-        from . import test_dataset as TD
         with torch.cuda.stream(self.stream):
             self.status = TD._status_word(dev)      # the ordering flag of THIS stream (uoc_roi_match)
 
-    def order_flagged(self) -> bool:
-        """Reads and clears the sticky ordering flag of the replay stream (synchronises)."""
-        flagged = int(self.status.item()) != 0
-        if flagged:
-            self.status.zero_()
-        return flagged
-
-    # -- the two stage bodies: the eager path's own functions, on the static buffers -----------------------------------
+    # -- the two stage bodies: the eager path's own launch functions, on the static buffers ------------------------------
     def _body1(self):
-        from . import test_dataset as TD
-        H, W, dev = self.H, self.W, self.dev
-        thr = self.thr if self.depth is not None else None
-        features = TD._detach_keep_planes(self.network(self.image, None, self.depth))
-        labels = TD._cluster_fields(features, self.first1)
-        zptr = ctypes.c_void_p(self.depth.data_ptr() + 2 * H * W * 4) if thr is not None else ctypes.c_void_p(0)
-        table = TD._build_rois(labels[0], zptr, H, W, dev, thr if thr is not None else 0.0)
+        labels, (table,) = TD._stage1_launches(self.network, self.image, self.depth, self.first1,
+                                               self.thr if self.depth is not None else None)
         if self.network_crop is not None:
             self.table_h.copy_(table, non_blocking=True)
         return labels, table
 
     def _body2(self, K):
-        from . import test_dataset as TD
-        H, W, dev = self.H, self.W, self.dev
-        rgb_crop, mask_crop, depth_crop = TD._crop(self.image, self.depth, self.labels[0], self.table, K, H, W, dev)
-        features_crop = TD._detach_keep_planes(self.network_crop(rgb_crop, mask_crop, depth_crop))
-        labels_crop = TD._cluster_fields(features_crop, self.first2[:K])
-        refined, _ = TD._match_device(labels_crop, mask_crop, depth_crop, self.table, K, H, W, dev)
-        return refined, (labels_crop, mask_crop, depth_crop)
+        (refined,), parts = TD._stage2_launches(self.network_crop, self.image, self.depth, self.labels, [self.table], [K],
+                                                self.first2[:K])
+        return refined, parts
 
     def _capture(self, body):
         # (capture_begin / capture_end directly: the torch.cuda.graph context manager also runs gc.collect() and
@@ -148,7 +131,6 @@ class GraphedFrame:
                 refined = refined.view(1, H, W)
 
                 def redo(parts=parts, K=K):
-                    from . import test_dataset as TD
                     with torch.cuda.stream(self.stream):
                         r, _ = TD._match_host_order(parts[0], parts[1], parts[2], self.table, K, H, W, dev)
                     torch.cuda.current_stream(dev).wait_stream(self.stream)

@@ -7,6 +7,10 @@ tensors, `out_label` lives on the CPU, ROIs are [K,4] float x0,y0,x1,y1 inclusiv
 NumPy RNG is consumed once per clustered field in the reference's order).  Internally labels stay
 int32 on the device and the per-object Python loops of the reference are single batched launches.
 There is no CPU fallback: inputs are moved to the ROCm device and every stage runs as HIP kernels.
+
+The two-stage frame path is written once: _stage1_launches / _stage2_launches queue the device work of the two stages,
+FrameGroupJob adds what needs the host (uploads, RNG draws, the read of the ROI counts between the stages).  test_sample,
+test_segnet and the frame-parallel runner run that job; fcn/graph_replay.py replays the same two functions as hipGraphs.
 """
 from __future__ import annotations
 
@@ -74,24 +78,20 @@ def _kernel_layout(features: torch.Tensor) -> torch.Tensor:
     return to_planes(X) if X.shape[-1] == 128 else X
 
 
-def _cluster_device(features: torch.Tensor, num_seeds: int = 100, rng=None):
-    """Device-resident clustering of every batch item: int32 labels [B, h*w], indices [B, m].
-    `rng`: where the first-seed draws come from — the global NumPy RNG like the reference (mean_shift.py:155), or a
-    per-frame np.random.RandomState when several frames are in flight and must not interleave their draws."""
-    require_supported()
-    if not features.is_cuda:
-        raise _native.NativeError("features must be on a ROCm device (no CPU fallback)")
-    X = _kernel_layout(features)
-    B, n = X.shape[0], X.shape[-2]
-    draw = (rng if rng is not None else np.random).randint
-    firsts = [draw(0, n) for _ in range(B)]                # mean_shift.py:155, one draw per field, in order
-    return cluster_batch(X, firsts, KAPPA, num_seeds, MAX_ITERS, 2 * cfg.TRAIN.EMBEDDING_ALPHA)
+def _cluster(features: torch.Tensor, firsts, num_seeds: int = 100):
+    """Clusters the B fields of `features` [B,C,h,w] from the given first-seed indices (B ints, or an int32 device tensor
+    [B]) -> int32 labels [B, h*w], seed indices [B, m], both on the device."""
+    return cluster_batch(_kernel_layout(features), firsts, KAPPA, num_seeds, MAX_ITERS, 2 * cfg.TRAIN.EMBEDDING_ALPHA)
 
 
 def clustering_features(features, num_seeds=100):
     """test_dataset.py:44-59 -> (out_label [B,h,w] float32 on the CPU, list of [m] int64 seed indices)."""
-    labels, indices = _cluster_device(features, num_seeds)
+    require_supported()
+    if not features.is_cuda:
+        raise _native.NativeError("features must be on a ROCm device (no CPU fallback)")
     B, _, h, w = features.shape
+    firsts = [np.random.randint(0, h * w) for _ in range(B)]       # mean_shift.py:155, one draw per field, in order
+    labels, indices = _cluster(features, firsts, num_seeds)
     out_label = labels.view(B, h, w).float().cpu()
     _check_clustering(labels.device)
     return out_label, [indices[j].long().cpu() for j in range(B)]
@@ -145,19 +145,26 @@ def _build_rois(lab0: torch.Tensor, z_plane_ptr, H, W, dev, threshold=DEPTH_FILT
     return table
 
 
-def _crop(rgb, depth, lab0, table, K, H, W, dev):
+def _crop_buffers(K, has_depth, dev):
+    """(rgb_crops [K,3,S,S], mask_crops [K,S,S], depth_crops [K,3,S,S] or None), uninitialised."""
+    S = cfg.TRAIN.SYN_CROP_SIZE
+    return (torch.empty((K, 3, S, S), dtype=torch.float32, device=dev), torch.empty((K, S, S), dtype=torch.float32, device=dev),
+            torch.empty((K, 3, S, S), dtype=torch.float32, device=dev) if has_depth else None)       # :73-76
+
+
+def _crop(rgb, depth, lab0, table, K, H, W, dev, out=None):
+    """The K ROI crops of one image -> (rgb_crops, mask_crops, depth_crops): new tensors, or the views `out` (same order)
+    of a batch that holds the crops of several images."""
     S = cfg.TRAIN.SYN_CROP_SIZE
     L = _native.lib()
-    rgb_crops = torch.empty((K, 3, S, S), dtype=torch.float32, device=dev)
-    depth_crops = torch.empty((K, 3, S, S), dtype=torch.float32, device=dev) if depth is not None else None   # :73-76
-    mask_crops = torch.empty((K, S, S), dtype=torch.float32, device=dev)
+    rgb_crops, mask_crops, depth_crops = out = out if out is not None else _crop_buffers(K, depth is not None, dev)
     if K > 0:
         with torch.cuda.device(dev):
             rc = L.uoc_roi_crop(_native.ptr(rgb), _native.ptr(depth), _native.ptr(lab0), H, W, _native.ptr(table), K, S,
                                 _native.ptr(rgb_crops), _native.ptr(depth_crops), _native.ptr(mask_crops),
                                 _native.stream_ptr(dev))
         _native.check(rc, "uoc_roi_crop")
-    return rgb_crops, mask_crops, depth_crops
+    return out
 
 
 def crop_rois(rgb, initial_masks, depth):
@@ -192,21 +199,17 @@ def _order_and_map(keep: np.ndarray, sort_key: torch.Tensor):
 
 
 class _HostMirror:
-    """Pinned host buffers of one frame slot: the two small device->host reads of a frame (ROI table; keep table + mean
-    depths) and the host->device paint plan go through them as asynchronous copies guarded by an event, so the host
-    can queue another frame's work on another stream while a read is in flight."""
+    """Pinned host buffers of one job slot: the ROI tables of a job's frames (the one small device->host read of a frame)
+    arrive here as asynchronous copies guarded by an event, so the host can queue another job's work on another stream
+    while the read is in flight.  A second event marks that the job's stage 2 has run."""
 
     def __init__(self, frames=1):
-        n = MAX_LABELS * MAX_LABELS + MAX_LABELS
         self.frames = frames
         self.tables = torch.empty((frames, _native.ROI_TABLE_BYTES), dtype=torch.uint8).pin_memory()
-        self.stats_all = torch.empty((frames, n), dtype=torch.int32).pin_memory()
-        self.plans = torch.empty((frames, n), dtype=torch.int32).pin_memory()
-        self.table, self.stats, self.plan = self.tables[0], self.stats_all[0], self.plans[0]
         # blocking events: a host thread that waits on one sleeps instead of spinning (the runner's core budget per rank)
         blocking = os.environ.get("UOC_PIPE_BLOCKING_EVENTS", "0") == "1"
         self.table_ready = torch.cuda.Event(blocking=blocking)
-        self.stats_ready = torch.cuda.Event(blocking=blocking)
+        self.stage2_done = torch.cuda.Event(blocking=blocking)
 
 
 _mirrors = {}
@@ -237,7 +240,7 @@ def _match_stats(labels_crop_i32, mask_crops, depth_crops, K, dev):
     return stats
 
 
-def _paste(labels_crop_i32, table_dev, table_host, stats_h, has_depth, K, H, W, dev, plan_host=None):
+def _paste(labels_crop_i32, table_dev, table_host, stats_h, has_depth, K, H, W, dev):
     """Host ordering of the ROIs (:129-151) from the statistics read back, then one paste launch (:156-177)."""
     S = cfg.TRAIN.SYN_CROP_SIZE
     L = _native.lib()
@@ -249,11 +252,7 @@ def _paste(labels_crop_i32, table_dev, table_host, stats_h, has_depth, K, H, W, 
         sort_key = (box[:, 3] - box[:, 1] + 1) * (box[:, 2] - box[:, 0] + 1)
     order, mapping = _order_and_map(keep_h, sort_key)
     flat = np.concatenate([order.reshape(-1), mapping.reshape(-1)]).astype(np.int32)
-    if plan_host is not None:
-        plan_host[:flat.size].copy_(torch.from_numpy(flat))
-        plan = plan_host[:flat.size].to(dev, non_blocking=True)
-    else:
-        plan = torch.from_numpy(flat).to(dev)
+    plan = torch.from_numpy(flat).to(dev)
     order_d, map_d = plan[:K], plan[K:]
     refined = torch.empty((H * W,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -293,9 +292,8 @@ def _match_device(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, dev,
     return refined, keep
 
 
-def _order_needs_host(dev) -> bool:
-    """Reads and clears the sticky ordering flag of this stream (synchronises)."""
-    status = _status_word(dev)
+def _take_order_flag(status: torch.Tensor) -> bool:
+    """Reads and clears the sticky ordering flag in a stream's status word (synchronises)."""
     flagged = int(status.item()) != 0
     if flagged:
         status.zero_()
@@ -306,12 +304,8 @@ def _finish_block(dev):
     """End of a block of frames whose per-frame checks were deferred (the frame-parallel runner): the clustering status
     (uoc_ms_check) and the ordering flag of every stream of `dev`."""
     _check_clustering(dev)
-    flagged = False
-    for key, status in _order_status.items():
-        if key[:2] == (dev.type, dev.index) and int(status.item()) != 0:
-            status.zero_()
-            flagged = True
-    if flagged:
+    flags = [_take_order_flag(status) for key, status in _order_status.items() if key[:2] == (dev.type, dev.index)]
+    if any(flags):
         raise HostOrderNeeded("a frame had NaN ROI sort keys with >= 64 ROIs: re-run with the ROI ordering on the host")
 
 
@@ -328,7 +322,7 @@ def _match_host_order(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, 
 def _match(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, dev):
     """labels_crop_i32 [K, S*S] int32 (device) -> refined int32 [H*W] (device), keep table (device)."""
     refined, keep = _match_device(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, dev, want_keep=True)
-    if _order_needs_host(dev):
+    if _take_order_flag(_status_word(dev)):
         return _match_host_order(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, dev)
     return refined, keep
 
@@ -364,7 +358,7 @@ def test_sample(sample, network, network_crop):
     return _run_frame(sample, network, network_crop, DEPTH_FILTER)
 
 
-FORCE_HOST_ORDER = os.environ.get("UOC_HOST_ORDER", "0") == "1"      # True: ROI ordering on the host (rounds 1-5; the fallback for NaN keys with >= 64 ROIs; A/B)
+FORCE_HOST_ORDER = os.environ.get("UOC_HOST_ORDER", "0") == "1"      # True: ROI ordering on the host (the fallback for NaN keys with >= 64 ROIs; A/B)
 
 
 class HostOrderNeeded(_native.NativeError):
@@ -372,240 +366,155 @@ class HostOrderNeeded(_native.NativeError):
     caller re-runs with FORCE_HOST_ORDER (runner.run_sharded does)."""
 
 
-class FrameJob:
-    """One frame on its way through the two-stage path, cut at the ONE point where the host needs a small result from
-    the device (the number of ROIs, which sizes the stage-2 launches):
+def _upload(samples, dev):
+    """The images of `samples` as one batch on the device -> (image [N,3,H,W] float32, XYZ images [N,3,H,W] or None when the
+    configuration does not use depth, :236-239).  Raw samples (uint8 BGR + uint16 depth) are prepared on the device
+    (io.prepare_on_device); when all are raw and of one size, straight into the batched buffers."""
+    from ..io import prepare_on_device
+    if all("image_u8" in sm for sm in samples) and len({tuple(sm["depth_u16"].shape) for sm in samples}) == 1:
+        Hs, Ws = samples[0]["depth_u16"].shape
+        image = torch.empty((len(samples), 3, Hs, Ws), dtype=torch.float32, device=dev)
+        xyz = torch.empty((len(samples), 3, Hs, Ws), dtype=torch.float32, device=dev)
+        for f, sm in enumerate(samples):
+            prepare_on_device(sm, dev, out=(image[f], xyz[f]))
+        return image, (xyz if uses_depth() else None)
+    # non_blocking is a no-op for pageable host memory (the runtime stages it synchronously) and asynchronous for
+    # pinned memory; asking the tensor (`is_pinned()`) costs a driver query per call, so just always pass it
+    pin = lambda t: t.to(dev, non_blocking=True)
+    images, depths = [], []
+    for sm in samples:
+        if "image_u8" in sm:
+            sm = dict(sm, **prepare_on_device(sm, dev))
+        images.append(pin(sm["image_color"]).float())
+        if uses_depth():
+            depths.append(pin(sm["depth"]).float())
+    batch = lambda ts: (torch.cat(ts) if len(ts) > 1 else ts[0]).contiguous()
+    return batch(images), (batch(depths) if depths else None)
 
-        stage1  embed, cluster, depth filter + ROI table          -> async D2H of the table
-        stage2  (needs K) crop, embed + cluster the K crops, match statistics, ROI order + renumbering + paste (device)
 
-    Round 6: the second cut of rounds 1-5 (statistics to the host, Python's sorted, plan back to the device) is gone —
-    uoc_roi_match orders on the device.  With host_order=True (FORCE_HOST_ORDER) the old cut is back as stage3.
-    `_run_frame` runs the stages back to back; the pipelined runner keeps several FrameGroupJobs in flight.  Results do
-    not depend on the interleaving: every job draws its first seeds from its own `rng`."""
+def _stage1_launches(network, image, depth, firsts, thr, label=None, refine=None):
+    """Stage 1 of the N images of `image`, queued on the current stream: embed (:247), cluster from the first-seed indices
+    `firsts`, depth filter (:250-252; thr None = none) — fused with the ROI table build for the first `refine` items
+    (default: all), one filter-only call for the rest.  -> labels [N, H*W] int32, the ROI tables of the refined items."""
+    dev = _device()
+    N, _, H, W = image.shape
+    R = N if refine is None else refine
+    features = _detach_keep_planes(network(image, label, depth))
+    labels, _ = _cluster(features, firsts)
+    zptr = lambda f: ctypes.c_void_p(depth.data_ptr() + ((3 * f + 2) * H * W) * 4 if thr is not None else 0)   # z plane of item f
+    tables = [_build_rois(labels[f], zptr(f), H, W, dev, thr if thr is not None else 0.0) for f in range(R)]
+    if R < N and thr is not None:
+        L, ws = _native.lib(), _ws(dev)
+        with torch.cuda.device(dev):
+            _native.check(L.uoc_filter_labels_depth(_native.ptr(labels[R:]), zptr(R), 3 * H * W, N - R, H, W, float(thr),
+                                                    _native.ptr(ws), ws.numel(), _native.stream_ptr(dev)),
+                          "uoc_filter_labels_depth")
+    return labels, tables
 
-    def __init__(self, sample, network, network_crop, depth_threshold, rng=None, host_order=None):
-        self.sample, self.network, self.network_crop = sample, network, network_crop
-        self.depth_threshold, self.rng = depth_threshold, rng
-        self.host_order = FORCE_HOST_ORDER if host_order is None else host_order
-        self.K = 0
-        self.labels = self.refined = None
 
-    def stage1(self):
-        require_supported()
-        dev = self.dev = _device()
-        sample = self.sample
-        if "image_u8" in sample:  # raw uint8 / uint16 sample: input preparation runs on the device (io.prepare_on_device)
-            from ..io import prepare_on_device
-            sample = dict(sample, **prepare_on_device(sample, dev))
-        # non_blocking is a no-op for pageable host memory (the runtime stages it synchronously) and asynchronous for
-        # pinned memory; asking the tensor (`is_pinned()`) costs a driver query per call, so just always pass it
-        pin = lambda t: t.to(dev, non_blocking=True)
-        self.image = image = pin(sample["image_color"]).float().contiguous()
-        self.depth = depth = pin(sample["depth"]).float().contiguous() if uses_depth() else None     # :236-239
-        if depth is None:
-            self.depth_threshold = None                                                           # :250 `if depth is not None`
-        thr = self.depth_threshold
-        label = sample["label"].to(dev) if "label" in sample else None
-        B, _, H, W = image.shape
-        self.B, self.H, self.W = B, H, W
+def _match_frames(parts, tables, Ks, H, W, dev, host_order=False):
+    """match_label_crop of every frame with ROIs, from the clustered crop batch `parts` = (labels_crop, mask, depth_crop):
+    -> per frame the refined map [H, W] int32, or None.  host_order: _match_host_order (synchronises) for _match_device."""
+    match = _match_host_order if host_order else _match_device
+    off = np.concatenate([[0], np.cumsum(Ks)]).astype(int)
+    refined = [None] * len(Ks)
+    for f, K in enumerate(Ks):
+        if K > 0:
+            labels_crop, mask, dep = (p[off[f]:off[f + 1]] if p is not None else None for p in parts)
+            refined[f] = match(labels_crop, mask, dep, tables[f], K, H, W, dev)[0].view(H, W)
+    return refined
 
-        features = _detach_keep_planes(self.network(image, label, depth))          # :247
-        labels, _ = _cluster_device(features, num_seeds=100, rng=self.rng)         # [B, H*W] int32 on the device
-        self.labels = labels
 
-        # depth filter (:250-252) fused with the ROI table build for item 0; other items filter only
-        zptr = ctypes.c_void_p(depth.data_ptr() + 2 * H * W * 4) if thr is not None else ctypes.c_void_p(0)
-        self.table = _build_rois(labels[0], zptr, H, W, dev, thr if thr is not None else 0.0)
-        if B > 1 and thr is not None:
-            L = _native.lib()
-            ws = _ws(dev)
-            z1 = ctypes.c_void_p(depth.data_ptr() + (3 * H * W + 2 * H * W) * 4)
-            with torch.cuda.device(dev):
-                _native.check(L.uoc_filter_labels_depth(_native.ptr(labels[1:]), z1, 3 * H * W, B - 1, H, W, float(thr),
-                                                        _native.ptr(ws), ws.numel(), _native.stream_ptr(dev)),
-                              "uoc_filter_labels_depth")
-        if self.network_crop is not None:
-            self.host = _mirror(dev)
-            self.host.table.copy_(self.table, non_blocking=True)
-            self.host.table_ready.record(torch.cuda.current_stream(dev))
-
-    def _set_refined(self, refined):
-        dev, H, W, B = self.dev, self.H, self.W, self.B
-        out = refined.view(1, H, W)
-        if B > 1:    # match_label_crop returns zeros_like(initial_masks) with only item 0 painted (:153,:176-177)
-            full = torch.zeros((B, H, W), dtype=refined.dtype, device=dev)
-            full[0] = out[0]
-            out = full
-        self.refined = out
-
-    def stage2(self):
-        if self.network_crop is None:
-            return
-        dev, H, W = self.dev, self.H, self.W
-        self.host.table_ready.synchronize()
-        self.table_host = _native.RoiTable.from_buffer_copy(self.host.table.numpy().tobytes())
-        K = self.K = int(self.table_host.K)
-        if K == 0:
-            return
-        rgb_crop, mask_crop, depth_crop = _crop(self.image, self.depth, self.labels[0], self.table, K, H, W, dev)
-        features_crop = _detach_keep_planes(self.network_crop(rgb_crop, mask_crop, depth_crop))     # :259
-        self.labels_crop, _ = _cluster_device(features_crop, rng=self.rng)      # K fields, one launch set
-        self.has_depth = depth_crop is not None
-        self.mask_crop, self.depth_crop = mask_crop, depth_crop       # kept for the host-order fallback
-        if not self.host_order:
-            refined, _ = _match_device(self.labels_crop, mask_crop, depth_crop, self.table, K, H, W, dev)
-            self._set_refined(refined)
-            return
-        stats = _match_stats(self.labels_crop, mask_crop, depth_crop, K, dev)
-        self.host.stats[:stats.numel()].copy_(stats, non_blocking=True)
-        self.host.stats_ready.record(torch.cuda.current_stream(dev))
-
-    def stage3(self):
-        if self.network_crop is None or self.K == 0 or not self.host_order:
-            return
-        dev, H, W, K = self.dev, self.H, self.W, self.K
-        self.host.stats_ready.synchronize()
-        refined = _paste(self.labels_crop, self.table, self.table_host, self.host.stats, self.has_depth, K, H, W, dev,
-                         plan_host=self.host.plan)
-        self._set_refined(refined)
-
-    def redo_with_host_order(self):
-        """The device ordering flagged this frame (NaN keys, >= 64 ROIs): order on the host from the same crop labels."""
-        refined, _ = _match_host_order(self.labels_crop, self.mask_crop, self.depth_crop, self.table, self.K, self.H, self.W, self.dev)
-        self._set_refined(refined)
-
-    def result_device(self):
-        """(labels [B,H,W] int32, refined [B,H,W] int32 or None), on the device."""
-        return self.labels.view(self.B, self.H, self.W), self.refined
+def _stage2_launches(network_crop, image, depth, labels, tables, Ks, firsts, host_order=False):
+    """Stage 2 of the frames whose ROI tables are `tables` (Ks: their ROI counts, not all 0), queued on the current stream:
+    the crops of all frames as ONE batch of sum(Ks) through one network_crop forward (:259) and one clustering launch set
+    (firsts: sum(Ks) first-seed indices), then match_label_crop per frame.
+    -> per frame the refined map [H, W] int32 or None, and the crop batch (labels_crop, mask, depth_crop) that a redo of
+    the match with the ROI ordering on the host starts from."""
+    dev = _device()
+    _, _, H, W = image.shape
+    rgb, mask, dep = _crop_buffers(sum(Ks), depth is not None, dev)
+    a = 0
+    for f, K in enumerate(Ks):
+        _crop(image[f], depth[f] if depth is not None else None, labels[f], tables[f], K, H, W, dev,
+              out=(rgb[a:a + K], mask[a:a + K], dep[a:a + K] if dep is not None else None))
+        a += K
+    features_crop = _detach_keep_planes(network_crop(rgb, mask, dep))
+    parts = (_cluster(features_crop, firsts)[0], mask, dep)
+    return _match_frames(parts, tables, Ks, H, W, dev, host_order), parts
 
 
 class FrameGroupJob:
-    """N independent single-image frames through the two-stage path as ONE set of launches per stage (the frame-parallel
-    runner's unit of work): both stage-1 embeddings in one network forward (batch N), both clusterings in one launch
-    set, and the crops of all N frames in one stage-2 forward (batch K_1 + ... + K_N).  Twice the pixels / Winograd
-    tiles per launch is what the convolution kernels need to fill 256 CUs with full-height tiles.  Every
-    frame keeps its own ROI table, RNG and output; label maps are bit-identical to one-frame-at-a-time processing (the
-    kernels' per-output summation order does not depend on the batch).  Same stages as FrameJob."""
+    """Frames on their way through the two-stage path as ONE set of launches per stage, cut at the ONE point where the host
+    needs a small result from the device (the ROI counts, which size the stage-2 launches):
 
-    def __init__(self, samples, network, network_crop, depth_threshold, rngs, host_order=None):
+        stage1  upload, embed, cluster, depth filter + ROI tables              -> async D2H of the tables
+        stage2  (needs K) crop, embed + cluster the crops, match: statistics, ROI order + renumbering + paste (device)
+
+    The launches themselves are _stage1_launches / _stage2_launches (fcn/graph_replay.py replays the same two functions);
+    the job owns what they do not: uploads, RNG draws, the table read and its event, the results.
+
+    `samples` is either N single-image samples, each with its own RNG (`rngs`) — the frame-parallel runner's unit of work:
+    all stage-1 embeddings in one network forward (batch N), all clusterings in one launch set, and the crops of all N
+    frames in one stage-2 forward (batch K_1 + ... + K_N).  Twice the pixels / Winograd tiles per launch is what the
+    convolution kernels need to fill 256 CUs with full-height tiles.  Every frame keeps its own ROI table, RNG
+    and output; label maps are bit-identical to one-frame-at-a-time processing (the kernels' per-output summation order
+    does not depend on the batch), and do not depend on how jobs in flight interleave.
+    Or it is ONE sample (`_run_frame`), possibly a batch of B images that share one RNG (rngs=None: the global NumPy RNG,
+    like the reference): every item is clustered and depth-filtered, only item 0 is refined (:247-261).
+
+    Round 6: the second cut of rounds 1-5 (statistics to the host, Python's sorted, plan back to the device) is gone —
+    uoc_roi_match orders on the device.  With host_order=True (FORCE_HOST_ORDER) stage 2 orders on the host, synchronously
+    (_match_host_order): a correctness fallback, not a schedule."""
+
+    def __init__(self, samples, network, network_crop, depth_threshold, rngs=None, host_order=None):
         self.samples, self.network, self.network_crop = list(samples), network, network_crop
-        self.depth_threshold, self.rngs = depth_threshold, list(rngs)
+        self.depth_threshold = depth_threshold
+        self.rngs = list(rngs) if rngs is not None else [np.random]
         self.host_order = FORCE_HOST_ORDER if host_order is None else host_order
-        self.N = len(self.samples)
-        self.K = [0] * self.N
-        self.refined = [None] * self.N
+        self.R = len(self.samples)               # refined items: every single-image frame, or item 0 of the one sample
+        self.K = [0] * self.R
+        self.refined = [None] * self.R
 
     def stage1(self):
         require_supported()
         dev = self.dev = _device()
-        N = self.N
-        # non_blocking is a no-op for pageable host memory (the runtime stages it synchronously) and asynchronous for
-        # pinned memory; asking the tensor (`is_pinned()`) costs a driver query per call, so just always pass it
-        pin = lambda t: t.to(dev, non_blocking=True)
-        if all("image_u8" in sm for sm in self.samples) and len({tuple(sm["depth_u16"].shape) for sm in self.samples}) == 1:
-            # raw samples (uint8 BGR + uint16 depth): asynchronous uploads, prepared on the device straight into the launch
-            # set's batched inputs
-            from ..io import prepare_on_device
-            Hs, Ws = self.samples[0]["depth_u16"].shape
-            image = torch.empty((N, 3, Hs, Ws), dtype=torch.float32, device=dev)
-            xyz = torch.empty((N, 3, Hs, Ws), dtype=torch.float32, device=dev)
-            for f, sm in enumerate(self.samples):
-                prepare_on_device(sm, dev, out=(image[f], xyz[f]))
-            self.image = image
-            self.depth = depth = xyz if uses_depth() else None
-        else:
-            images, depths = [], []
-            for sm in self.samples:
-                if "image_u8" in sm:
-                    from ..io import prepare_on_device
-                    sm = dict(sm, **prepare_on_device(sm, dev))
-                images.append(pin(sm["image_color"]).float())
-                if uses_depth():
-                    depths.append(pin(sm["depth"]).float())
-            self.image = image = (torch.cat(images) if N > 1 else images[0]).contiguous()
-            self.depth = depth = ((torch.cat(depths) if N > 1 else depths[0]).contiguous()) if depths else None
-        thr = self.depth_threshold if depth is not None else None
-        assert image.shape[0] == N, "FrameGroupJob takes single-image samples"
-        _, _, H, W = image.shape
-        self.H, self.W = H, W
-        features = _detach_keep_planes(self.network(image, None, depth))
-        firsts = [self.rngs[f].randint(0, H * W) for f in range(N)]          # mean_shift.py:155, one draw per frame
-        self.labels = labels = _cluster_fields(features, firsts)             # [N, H*W] int32
-        self.tables = []
-        for f in range(N):
-            zptr = ctypes.c_void_p(depth.data_ptr() + ((3 * f + 2) * H * W) * 4) if thr is not None else ctypes.c_void_p(0)
-            self.tables.append(_build_rois(labels[f], zptr, H, W, dev, thr if thr is not None else 0.0))
+        self.image, self.depth = image, depth = _upload(self.samples, dev)
+        N, _, H, W = image.shape
+        self.N, self.H, self.W = N, H, W
+        assert N == self.R or self.R == 1, "several samples in one FrameGroupJob must be single-image samples"
+        if len(self.rngs) == 1:
+            self.rngs = self.rngs * N            # the items of one sample draw from one RNG, in item order
+        thr = self.depth_threshold if depth is not None else None                                 # :250 `if depth is not None`
+        label = self.samples[0]["label"].to(dev) if self.R == 1 and "label" in self.samples[0] else None
+        firsts = [self.rngs[f].randint(0, H * W) for f in range(N)]          # mean_shift.py:155, one draw per field
+        self.labels, self.tables = _stage1_launches(self.network, image, depth, firsts, thr, label, refine=self.R)
         if self.network_crop is not None:
-            self.host = _mirror(dev, N)
-            for f in range(N):
+            self.host = _mirror(dev, self.R)
+            for f in range(self.R):
                 self.host.tables[f].copy_(self.tables[f], non_blocking=True)
             self.host.table_ready.record(torch.cuda.current_stream(dev))
 
     def stage2(self):
         if self.network_crop is None:
             return
-        dev, H, W, N = self.dev, self.H, self.W, self.N
         S = cfg.TRAIN.SYN_CROP_SIZE
         self.host.table_ready.synchronize()
-        self.table_host = [_native.RoiTable.from_buffer_copy(self.host.tables[f].numpy().tobytes()) for f in range(N)]
-        self.K = [int(t.K) for t in self.table_host]
-        Kt = sum(self.K)
-        if Kt == 0:
+        self.K = [int(_native.RoiTable.from_buffer_copy(self.host.tables[f].numpy().tobytes()).K) for f in range(self.R)]
+        if sum(self.K) == 0:
             return
-        self.off = np.concatenate([[0], np.cumsum(self.K)]).astype(int)
-        rgb = torch.empty((Kt, 3, S, S), dtype=torch.float32, device=dev)
-        dep = torch.empty((Kt, 3, S, S), dtype=torch.float32, device=dev) if self.depth is not None else None
-        mask = torch.empty((Kt, S, S), dtype=torch.float32, device=dev)
-        L = _native.lib()
-        for f in range(N):
-            if self.K[f] == 0:
-                continue
-            a, b = self.off[f], self.off[f + 1]
-            with torch.cuda.device(dev):
-                rc = L.uoc_roi_crop(_native.ptr(self.image[f]), _native.ptr(self.depth[f]) if dep is not None else None,
-                                    _native.ptr(self.labels[f]), H, W, _native.ptr(self.tables[f]), self.K[f], S,
-                                    _native.ptr(rgb[a:b]), _native.ptr(dep[a:b]) if dep is not None else None,
-                                    _native.ptr(mask[a:b]), _native.stream_ptr(dev))
-            _native.check(rc, "uoc_roi_crop")
-        features_crop = _detach_keep_planes(self.network_crop(rgb, mask, dep))
-        firsts = [self.rngs[f].randint(0, S * S) for f in range(N) for _ in range(self.K[f])]   # K_f draws per frame, in order
-        self.labels_crop = _cluster_fields(features_crop, firsts)              # [Kt, S*S]
-        self.has_depth = dep is not None
-        for f in range(N):
-            if self.K[f] == 0:
-                continue
-            a, b = self.off[f], self.off[f + 1]
-            if not self.host_order:
-                refined, _ = _match_device(self.labels_crop[a:b], mask[a:b], dep[a:b] if dep is not None else None,
-                                           self.tables[f], self.K[f], H, W, dev)
-                self.refined[f] = refined.view(H, W)
-                continue
-            stats = _match_stats(self.labels_crop[a:b], mask[a:b], dep[a:b] if dep is not None else None, self.K[f], dev)
-            self.host.stats_all[f, :stats.numel()].copy_(stats, non_blocking=True)
-        # host ordering: the statistics are on their way to the host.  Device ordering: the same event marks "stage 2 has
-        # run" — the runner frees the slot only then (see pending_event)
-        self.host.stats_ready.record(torch.cuda.current_stream(dev))
-        if not self.host_order:
-            self.labels_crop = self.image = self.depth = None
+        firsts = [self.rngs[f].randint(0, S * S) for f in range(self.R) for _ in range(self.K[f])]   # K_f draws per frame, in order
+        self.refined, self.parts = _stage2_launches(self.network_crop, self.image, self.depth, self.labels, self.tables,
+                                                    self.K, firsts, self.host_order)
+        self.host.stage2_done.record(torch.cuda.current_stream(self.dev))      # the runner frees the slot only then (pending_event)
 
-    def stage3(self):
-        if self.network_crop is None or sum(self.K) == 0 or not self.host_order:
-            return
-        dev, H, W = self.dev, self.H, self.W
-        self.host.stats_ready.synchronize()
-        for f in range(self.N):
-            if self.K[f] == 0:
-                continue
-            a, b = self.off[f], self.off[f + 1]
-            refined = _paste(self.labels_crop[a:b], self.tables[f], self.table_host[f], self.host.stats_all[f], self.has_depth,
-                             self.K[f], H, W, dev, plan_host=self.host.plans[f])
-            self.refined[f] = refined.view(H, W)
-        self.labels_crop = self.image = self.depth = None
+    def redo_with_host_order(self):
+        """The device ordering flagged a frame (NaN keys, >= 64 ROIs): order on the host from the same crop labels."""
+        self.refined = _match_frames(self.parts, self.tables, self.K, self.H, self.W, self.dev, host_order=True)
 
     def pending_event(self, state):
-        """The event the next stage waits for (state 1: the ROI tables have landed on the host; state 2: stage 2 has run —
-        with host ordering that is the arrival of the match statistics), or None if there is nothing to wait for.
+        """The event the next step waits for (state 1: the ROI tables have landed on the host; state 2: stage 2 has run),
+        or None if there is nothing to wait for.
         State 2 is a wait although the device ordering needs nothing from the device any more: a stream that is handed its
         next job's stage 1 while this job's stage 2 is still queued puts that job's sampling kernel into the per-device event
         chain (csrc/meanshift.hip) AHEAD of the other streams' stage-2 sampling kernels, which then wait behind this
@@ -614,50 +523,48 @@ class FrameGroupJob:
             return None
         if state == 1:
             return self.host.table_ready
-        return self.host.stats_ready if sum(self.K) > 0 else None
+        return self.host.stage2_done if sum(self.K) > 0 else None
 
     def final_maps(self):
         """Per frame: the refined map if stage 2 produced one, else the stage-1 map ([H,W] int32, device)."""
-        return [self.refined[f] if self.refined[f] is not None else self.labels[f].view(self.H, self.W) for f in range(self.N)]
+        return [self.refined[f] if self.refined[f] is not None else self.labels[f].view(self.H, self.W) for f in range(self.R)]
 
-
-def _cluster_fields(features, firsts):
-    """Clusters the B fields of `features` [B,C,h,w] with the given first-seed indices -> int32 labels [B, h*w]."""
-    labels, _ = cluster_batch(_kernel_layout(features), firsts, KAPPA, 100, MAX_ITERS, 2 * cfg.TRAIN.EMBEDDING_ALPHA)
-    return labels
+    def result_device(self):
+        """Of the job of one sample: (labels [B,H,W] int32, refined [B,H,W] int32 or None), on the device."""
+        refined = self.refined[0]
+        if refined is not None:      # match_label_crop returns zeros_like(initial_masks) with only item 0 painted (:153,:176-177)
+            refined = refined.view(1, self.H, self.W)
+            if self.N > 1:
+                full = torch.zeros((self.N, self.H, self.W), dtype=refined.dtype, device=self.dev)
+                full[0] = refined[0]
+                refined = full
+        return self.labels.view(self.N, self.H, self.W), refined
 
 
 def _run_frame_graphed(sample, network, network_crop, depth_threshold, checked):
     """The frame as hipGraph replays (fcn/graph_replay.py) when the call qualifies — cfg.TEST.GRAPH_REPLAY, a single-image
     sample, SEGNET networks, and not the first call of this (networks, size, configuration) combination — else None and
-    the caller runs the eager FrameJob.  Same label maps either way (tests/test_graph_replay_gpu.py)."""
-    from . import graph_replay as GR
+    the caller runs the eager FrameGroupJob.  Same label maps either way (tests/test_graph_replay_gpu.py)."""
+    from . import graph_replay as GR        # (it imports this module)
     if FORCE_HOST_ORDER or not getattr(cfg.TEST, "GRAPH_REPLAY", False) or "label" in sample:
         return None
     from ..networks.SEG import SEGNET
     if not isinstance(network, SEGNET) or not (network_crop is None or isinstance(network_crop, SEGNET)):
         return None
+    if "image_u8" not in sample and (sample["image_color"].dim() != 4 or sample["image_color"].shape[0] != 1):
+        return None
     require_supported()
     dev = _device()
-    if "image_u8" in sample:
-        from ..io import prepare_on_device
-        sample = dict(sample, **prepare_on_device(sample, dev))
-    image = sample["image_color"]
-    if image.dim() != 4 or image.shape[0] != 1:
-        return None
+    image, depth = _upload([sample], dev)
     _, _, H, W = image.shape
-    has_depth = uses_depth()
-    thr = depth_threshold if has_depth else None
-    gf = GR.frame_for(network, network_crop, H, W, dev, thr)
+    gf = GR.frame_for(network, network_crop, H, W, dev, depth_threshold if depth is not None else None)
     if gf is None:
         return None
-    image = image.to(dev, non_blocking=True).float()
-    depth = sample["depth"].to(dev, non_blocking=True).float() if has_depth else None
     labels, refined, K, redo = gf.run(image, depth, None)
     LAST_FRAME_STATS["rois"] = K
     if checked:
         _check_clustering(dev)              # synchronises
-        if K > 0 and gf.order_flagged():
+        if K > 0 and _take_order_flag(gf.status):
             refined = redo()
     return labels, refined
 
@@ -674,14 +581,13 @@ def _run_frame(sample, network, network_crop, depth_threshold, return_device=Fal
     if graphed is not None:
         labels, out_label_refined = graphed
     else:
-        job = FrameJob(sample, network, network_crop, depth_threshold)
+        job = FrameGroupJob([sample], network, network_crop, depth_threshold)
         job.stage1()
         job.stage2()
-        job.stage3()
-        LAST_FRAME_STATS["rois"] = job.K
+        LAST_FRAME_STATS["rois"] = job.K[0]
         if checked:
             _check_clustering(job.dev)          # synchronises
-            if job.K > 0 and not job.host_order and _order_needs_host(job.dev):
+            if job.K[0] > 0 and not job.host_order and _take_order_flag(_status_word(job.dev)):
                 job.redo_with_host_order()
         labels, out_label_refined = job.result_device()
     if return_device:

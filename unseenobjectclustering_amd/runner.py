@@ -6,6 +6,9 @@ tools/test_images.py:199).
 
 Sharding-independent results: the NumPy RNG that picks the first mean-shift seed
 (mean_shift.py:155) is re-seeded per frame from the GLOBAL frame index.
+
+On one GPU, _run_block_pipelined keeps several fcn.test_dataset.FrameGroupJob in flight, one per stream; a job has two
+steps (stage1, stage2) with one small device->host read between them.
 """
 from __future__ import annotations
 
@@ -204,7 +207,7 @@ def _run_block_pipelined(frame_fn, lo: int, hi: int, block: torch.Tensor, device
     nxt = lo
     group = max(1, int(getattr(frame_fn, "frames_per_launch", 1)))
     poll = os.environ.get("UOC_PIPE_POLL", "1") != "0"
-    slots = [None] * depth          # per stream: None or [idx, job, state]; state 1 = waits for the tables, 2 = for the statistics
+    slots = [None] * depth          # per stream: None or [idx, job, state]; state 1 = waits for the tables, 2 = waits for stage 2 to have run
     done_counts = {}
 
     plan = deque(launch_set_sizes(hi - lo, group, depth, os.environ.get("UOC_PIPE_TAIL", PIPE_TAIL_DEFAULT) != "0"))
@@ -224,8 +227,8 @@ def _run_block_pipelined(frame_fn, lo: int, hi: int, block: torch.Tensor, device
         return n
 
     def advance(slot, block_host):
-        """Moves the slot's job one stage on if its pending device->host read has completed (or, with block_host, waits
-        for it).  Returns True if something was issued."""
+        """Moves the slot's job one step on if the event it waits for has completed (or, with block_host, waits for it).
+        Returns True if something was issued."""
         idx, job, state = slots[slot]
         ev = job.pending_event(state)
         if ev is not None:
@@ -239,7 +242,6 @@ def _run_block_pipelined(frame_fn, lo: int, hi: int, block: torch.Tensor, device
                 slots[slot][2] = 2
                 if job.pending_event(2) is not None:      # the slot is freed when stage 2 has run (FrameGroupJob.pending_event)
                     return True
-            job.stage3()
             for i, m in zip(idx, job.final_maps()):       # int32 [H, W] (contiguous) -> the uint8 row of the block
                 with torch.cuda.device(device):
                     _native.check(L.uoc_labels_to_u8(_native.ptr(m), m.numel(), _native.ptr(block[i - lo]),
