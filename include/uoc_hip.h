@@ -366,6 +366,40 @@ int uoc_track_step(const int32_t *d_labels, int B, int H, int W, int q, int max_
 
 
 /* ------------------------------------------------------------------------------------------
+ * Spatially connected components of a label map (no reference counterpart): the clustering never
+ * asks whether the pixels of one id touch each other; this step does.  L is [B][H][W] int32 with H*W below 2^31.
+ *
+ * A pixel is foreground when 1 <= L <= 127; every other value (negative ids, 128, 255) is background.  connectivity is
+ * 4 or 8.  A component is a maximal set of foreground pixels of ONE frame that carry the SAME id and are connected
+ * through neighbours of that id; pixels of different ids or frames never join.  Of a component: root = its smallest
+ * raster index y*W + x, area = its pixel count, src = its raw id.  siblings(b, i) = the number of components of raw id
+ * i in frame b, the small ones included.  A component is small when area < min_area (min_area >= 1); small components
+ * become background.
+ *
+ * Mode ALL: the non-small components of a frame, in ascending root order, get the new ids 1, 2, ..., 127; those beyond
+ * the 127th become background and count as dropped.  table[b][k] = {src, area, root, siblings(b, src)} for new id k.
+ * Mode LARGEST: per raw id the non-small component of largest area (ties: the smaller root) keeps the raw id; the id's
+ * other non-small components become background and count as dropped.  table[b][i] = {i, area, root, siblings(b, i)}
+ * for raw id i.
+ * Both: unused table rows and row 0 are zero; counts[b] = {found, small, kept, dropped}, found = small + kept +
+ * dropped; out is int32 in 0..127 and must not alias L.  All arithmetic is integer and every choice is over a strict
+ * total order: the result is defined exactly and does not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_CC_ALL 0
+#define UOC_CC_LARGEST 1
+
+/* 0 for a bad shape. */
+size_t uoc_cc_workspace_bytes(int B, int H, int W);
+/* d_labels, d_out [B][H*W] int32 (distinct buffers); d_table [B][128][4] and d_ws 16-byte aligned; d_counts [B][4].
+ * Returns UOC_EINVAL before any device work for null pointers, d_out == d_labels, a connectivity other than 4 or 8,
+ * min_area < 1, an unknown mode, a bad shape or a workspace below uoc_cc_workspace_bytes(B, H, W).  Six (LARGEST) or
+ * seven (ALL) launches on `stream`, one fewer when the frame is a single 32x32 tile; no host read, nothing
+ * synchronises, no state is kept between calls. */
+int uoc_cc_split(const int32_t *d_labels, int B, int H, int W, int connectivity, int min_area, int mode, int32_t *d_out,
+                 int32_t *d_table, int32_t *d_counts, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

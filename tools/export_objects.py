@@ -5,6 +5,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
     python tools/export_objects.py --imgdir tests/golden/demo --out objs/ [--max-points 2048]
                                    [--pretrained ckpt.pth --pretrained_crop crop.pth] [--cfg experiments/cfgs/<experiment>.yml]
                                    [--track [--track-min-iou 0.3] [--track-max-age 5]]
+                                   [--components {all,largest} [--min-area 1]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -15,6 +16,12 @@ With --track the frames are taken as one stream in file order: every final label
 (unseenobjectclustering_amd/tracking.py) and the objects are extracted from the TRACKED map, so `label` is the track slot
 an object keeps from frame to frame, `label_map` the tracked map, `raw_label_map` the segmentation's own numbering and
 `track_uid` the stream-wide object number of every row.
+
+With --components the final label map is first split into its spatially connected pieces on the device
+(unseenobjectclustering_amd/components.py): `largest` keeps the largest piece of every id and drops the rest (speckle),
+`all` renumbers every piece of at least --min-area pixels 1..127 (look-alike objects that shared an id come apart).  The
+order is segmentation, split, --track if given, extract_objects; `component_src`, `component_area` and
+`component_siblings` give per row the raw id the piece came from, its pixels and the number of pieces that id had.
 """
 import argparse
 import glob
@@ -31,6 +38,7 @@ import torch  # noqa: E402
 from test_images import load_weights  # noqa: E402
 from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
+from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 
@@ -52,6 +60,9 @@ def main():
     ap.add_argument("--track", action="store_true", help="stable ids across the frames (taken in file order)")
     ap.add_argument("--track-min-iou", type=float, default=0.3)
     ap.add_argument("--track-max-age", type=int, default=5)
+    ap.add_argument("--components", choices=["all", "largest"], default=None,
+                    help="split the label map into connected components first (off by default)")
+    ap.add_argument("--min-area", type=int, default=1, help="components below this many pixels become background")
     args = ap.parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
@@ -73,7 +84,13 @@ def main():
         sample = uio.read_sample(fc, fd, cam)
         out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
         final = out_refined if out_refined is not None else out_label
-        track_uid = raw_map = None
+        track_uid = raw_map = comp = None
+        if args.components is not None:
+            split, table, _ = split_components(final[0].to(cfg.device), connectivity=8, min_area=args.min_area,
+                                               mode=args.components)
+            if tracker is None:
+                objs = extract_objects(split, sample["depth"][:1].to(cfg.device), max_points_per_object=args.max_points)
+            comp, final = table[0], split[None].cpu()
         if tracker is not None:
             raw_map = final[0].numpy().astype(np.int32)
             tracked = tracker.update(final[0].to(cfg.device))
@@ -84,6 +101,14 @@ def main():
         rec["label_map"] = final[0].numpy().astype(np.int32)
         if tracker is not None:
             rec["raw_label_map"], rec["track_uid"] = raw_map, track_uid
+        if comp is not None:           # per row: the component its pixels came from (through the tracker's lut when tracking)
+            ids = objs.label.long()
+            if tracker is not None:    # track slot -> the split map's id
+                inverse = torch.zeros(128, dtype=torch.int64, device=cfg.device)
+                inverse[tracker.lut[0].long()] = torch.arange(128, device=cfg.device)
+                ids = inverse[ids]
+            rows = comp[ids].cpu().numpy()
+            rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")

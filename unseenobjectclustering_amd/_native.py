@@ -104,6 +104,10 @@ def _declare(lib):
     lib.uoc_track_reset.restype = c_int
     lib.uoc_track_step.argtypes = [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]
     lib.uoc_track_step.restype = c_int
+    lib.uoc_cc_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.uoc_cc_workspace_bytes.restype = c_size_t
+    lib.uoc_cc_split.argtypes = [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
+    lib.uoc_cc_split.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -141,7 +145,8 @@ EXPORTED_SYMBOLS = (
     "uoc_net_forward", "uoc_net_set_split_precision", "uoc_conv2d_nhwc", "uoc_conv2d_nhwc_algo",
     "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
-    "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
+    "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -173,6 +178,9 @@ TRACK_SLOTS = 128               # slot 0 is never a track
 TRACK_HEADER_WORDS = 1024       # int32 words of a stream's state before its contingency scratch (include/uoc_hip.h)
 TRACK_META_WORD = 640           # ... of which words 640, 641, 642 = uids handed out, step, dropped
 TRACK_CONT_WORDS = 128 * 128
+CC_ALL, CC_LARGEST = 0, 1      # include/uoc_hip.h: UOC_CC_ALL / UOC_CC_LARGEST, the mode argument of uoc_cc_split
+CC_MODES = {"all": CC_ALL, "largest": CC_LARGEST}
+CC_FIELDS = ("src", "area", "root", "siblings")        # the columns of uoc_cc_split's table
 OBJECTS_MAX_ATTR = 8        # include/uoc_hip.h: UOC_OBJECTS_MAX_ATTR
 
 
