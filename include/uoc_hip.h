@@ -400,6 +400,67 @@ int uoc_cc_split(const int32_t *d_labels, int B, int H, int W, int connectivity,
 
 
 /* ------------------------------------------------------------------------------------------
+ * Support plane and object heights above it (no reference counterpart): the dominant plane of
+ * the background pixels of a frame, and every object measured against it.  d_labels [B][H][W] int32 and d_xyz
+ * [B][3][H][W] fp32 metres as for uoc_objects; H*W below 2^31.
+ *
+ * A. Candidates (integers, exact).  A pixel is a candidate when its label is NOT in 1..127, x, y, z are finite, z > 0
+ * and q_c = (int) rintf(c * 1000.0f) (fp32 product, round half to even) has |q_c| <= 32767 for c = x, y, z.  M = the
+ * candidates of the frame, listed in raster order.  M < 3: no plane.
+ * B. Hypotheses (integers, exact).  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * in uint32.  For h = 0..num_hyp-1 and k = 0, 1, 2: i_k = (uint64(mix(seed ^ ((3h+k) * 0x9E3779B9))) * M) >> 32 (the
+ * frame index is not hashed), p_k = q of candidate i_k, n = (p1-p0) x (p2-p0) in int64, g = max |n_c|,
+ * s = max(0, bitlength(g) - 30), n'_c = sign(n_c) * (|n_c| >> s).  n' = 0: score(h) = -1.  Else L = floor(sqrt(n'.n'))
+ * exactly and score(h) = #candidates q with |n'.(q - p0)| <= tau_mm * L.  Winner: largest score, ties to the lowest h;
+ * every score -1: no plane.
+ * C. Refinement (fp64, fixed summation order, one round).  Over the winner's inliers (the integer test of B) and their
+ * original fp32 points: centroid c, population covariance, eigen-decomposition; normal = the unit eigenvector of the
+ * smallest eigenvalue, d = -normal.c, both negated when d < 0 (the camera is on the positive side); d == 0: the
+ * component of normal of largest magnitude is positive (ties: lowest index).  u = the normalised projection of (1,0,0)
+ * onto the plane ((0,1,0) when that projection is shorter than 1e-6), v = normal x u.
+ * D. Objects.  For every id 1..127 over its valid points (uoc_objects' rule), t = normal.p + d, (a, b) =
+ * ((p-c).u, (p-c).v) in fp64: see uoc_plane_object.  Without a plane every field below but `candidates` is 0.
+ * Bitwise reproducible; frame b's outputs do not depend on the other frames of the batch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct uoc_plane {
+  int32_t found;       /* 1 when a plane was fitted                                                              */
+  int32_t candidates;  /* M                                                                                      */
+  int32_t inliers;     /* the winner's score                                                                     */
+  int32_t hyp;         /* the winning h                                                                          */
+  float normal[3];     /* refined unit normal                                                                    */
+  float d;             /* refined offset: normal.p + d = 0                                                       */
+  float centroid[3];   /* centroid c of the inliers                                                              */
+  float eig[3];        /* eigenvalues of the inliers' covariance, descending                                     */
+  float rms;           /* sqrt(eig[2]): rms distance of the inliers from the plane                               */
+  float u[3];          /* in-plane axes                                                                          */
+  float v[3];
+} uoc_plane;
+
+typedef struct uoc_plane_object {
+  int32_t count;       /* valid points of the id; 0: every other field is 0                                      */
+  float height_min;    /* min t                                                                                  */
+  float height_max;    /* max t                                                                                  */
+  float foot[2];       /* mean of (a, b)                                                                         */
+  float cov2[3];       /* population covariance of (a, b): aa, ab, bb                                            */
+  float axis[2];       /* unit major axis e of cov2 in the (u, v) frame (closed-form 2x2 eigen-solve, fp64); its
+                          component of larger magnitude is positive (ties: index 0); eigen-gap 0: (1, 0)           */
+  float half[3];       /* half extents (max - min) / 2 of r.e, r.e' and t, r = (a, b) - foot, e' = (-e[1], e[0])  */
+  float center[3];     /* upright box centre: c + (foot + m0 e + m1 e') in (u, v) + m2 normal, m = (max + min) / 2 */
+} uoc_plane_object;
+
+/* 0 for a bad shape or num_hyp outside 1..1024. */
+size_t uoc_plane_workspace_bytes(int B, int H, int W, int num_hyp);
+/* num_hyp in 1..1024, tau_mm in 1..1000.  d_planes [B], d_objs [B][128], d_height (nullable) [B][H][W]: t as fp32 at
+ * every pixel with a valid point (object or background), NaN elsewhere and in a frame without a plane.  d_ws 16-byte
+ * aligned.  Returns UOC_EINVAL before any device work for null pointers, bad ranges, a bad shape or a workspace below
+ * uoc_plane_workspace_bytes(B, H, W, num_hyp).  Launches on `stream`; no host read, nothing synchronises, no state is
+ * kept between calls. */
+int uoc_support_plane(const int32_t *d_labels, const float *d_xyz, int B, int H, int W, int num_hyp, int tau_mm,
+                      uint32_t seed, uoc_plane *d_planes, uoc_plane_object *d_objs, float *d_height, void *d_ws,
+                      size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

@@ -6,6 +6,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--pretrained ckpt.pth --pretrained_crop crop.pth] [--cfg experiments/cfgs/<experiment>.yml]
                                    [--track [--track-min-iou 0.3] [--track-max-age 5]]
                                    [--components {all,largest} [--min-area 1]]
+                                   [--plane [--min-height M]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -22,6 +23,12 @@ With --components the final label map is first split into its spatially connecte
 `all` renumbers every piece of at least --min-area pixels 1..127 (look-alike objects that shared an id come apart).  The
 order is segmentation, split, --track if given, extract_objects; `component_src`, `component_area` and
 `component_siblings` give per row the raw id the piece came from, its pixels and the number of pieces that id had.
+
+With --plane the support plane of the exported label map is fitted on the device (unseenobjectclustering_amd/support.py):
+`plane_found`, `plane_candidates`, `plane_inliers`, `plane_hyp`, `plane_normal`, `plane_d`, `plane_centroid`, `plane_eig`,
+`plane_rms`, `plane_u`, `plane_v` describe it, and per row `height_min`, `height_max`, `foot`, `cov2`, `upright_axis`,
+`upright_half`, `upright_center` give the object's height above it and its upright box.  --min-height M adds `standing`
+per row: whether the object's top is at least M metres above the plane.
 """
 import argparse
 import glob
@@ -40,10 +47,24 @@ from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
+from unseenobjectclustering_amd.support import fit_plane, standing_objects  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
           "obb_center", "obb_half", "offsets", "points", "pixel_index")
+PLANE_KEYS = ("found", "candidates", "inliers", "hyp", "normal", "d", "centroid", "eig", "rms", "u", "v")
+OBJECT_KEYS = {"height_min": "height_min", "height_max": "height_max", "foot": "foot", "cov2": "cov2", "axis": "upright_axis",
+               "half": "upright_half", "center": "upright_center"}
+
+
+def plane_arrays(fitted, ids, min_height=None):
+    """The --plane arrays of one frame: the plane of frame 0 of `fitted` and, per exported object (ids = its labels), the
+    height and upright-box fields."""
+    rec = {"plane_" + k: getattr(fitted, k)[0].cpu().numpy() for k in PLANE_KEYS}
+    rec.update({name: getattr(fitted, k)[0][ids].cpu().numpy() for k, name in OBJECT_KEYS.items()})
+    if min_height is not None:
+        rec["standing"] = standing_objects(fitted, min_height)[0][ids].cpu().numpy()
+    return rec
 
 
 def main():
@@ -63,6 +84,8 @@ def main():
     ap.add_argument("--components", choices=["all", "largest"], default=None,
                     help="split the label map into connected components first (off by default)")
     ap.add_argument("--min-area", type=int, default=1, help="components below this many pixels become background")
+    ap.add_argument("--plane", action="store_true", help="fit the support plane and add heights and upright boxes")
+    ap.add_argument("--min-height", type=float, default=None, help="with --plane: add `standing` (top at least this high, metres)")
     args = ap.parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
@@ -109,6 +132,9 @@ def main():
                 ids = inverse[ids]
             rows = comp[ids].cpu().numpy()
             rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
+        if args.plane:
+            fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
+            rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")

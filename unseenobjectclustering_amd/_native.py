@@ -108,6 +108,10 @@ def _declare(lib):
     lib.uoc_cc_workspace_bytes.restype = c_size_t
     lib.uoc_cc_split.argtypes = [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
     lib.uoc_cc_split.restype = c_int
+    lib.uoc_plane_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.uoc_plane_workspace_bytes.restype = c_size_t
+    lib.uoc_support_plane.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32, P, P, P, P, c_size_t, P]
+    lib.uoc_support_plane.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -146,7 +150,7 @@ EXPORTED_SYMBOLS = (
     "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
-    "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -166,6 +170,23 @@ class UocObject(ctypes.Structure):
 
 
 OBJECT_BYTES = ctypes.sizeof(UocObject)
+
+
+class UocPlane(ctypes.Structure):
+    """Mirror of uoc_plane (include/uoc_hip.h): one per frame."""
+    _fields_ = [("found", c_int32), ("candidates", c_int32), ("inliers", c_int32), ("hyp", c_int32), ("normal", c_float * 3),
+                ("d", c_float), ("centroid", c_float * 3), ("eig", c_float * 3), ("rms", c_float), ("u", c_float * 3),
+                ("v", c_float * 3)]
+
+
+class UocPlaneObject(ctypes.Structure):
+    """Mirror of uoc_plane_object (include/uoc_hip.h): one per (frame, id)."""
+    _fields_ = [("count", c_int32), ("height_min", c_float), ("height_max", c_float), ("foot", c_float * 2),
+                ("cov2", c_float * 3), ("axis", c_float * 2), ("half", c_float * 3), ("center", c_float * 3)]
+
+
+PLANE_MAX_HYP = 1024            # include/uoc_hip.h: num_hyp in 1..1024, tau_mm in 1..1000
+PLANE_MAX_TAU_MM = 1000
 
 
 class UocTrack(ctypes.Structure):
@@ -196,7 +217,11 @@ def lib():
         # ("no ROCm-capable device is detected").  Importing torch before dlopen guarantees sharing.
         import torch  # noqa: F401
         l = ctypes.CDLL(LIB_PATH)
-        _declare(l)
+        try:
+            _declare(l)
+        except AttributeError as e:          # a library built from an older tree: no quiet fall-back, rebuild it
+            raise NativeError(f"{LIB_PATH} lacks a symbol of include/uoc_hip.h ({e}): rebuild it with "
+                              "`python -m unseenobjectclustering_amd.build`") from e
         _lib = l
         import atexit
         atexit.register(l.uoc_shutdown)

@@ -31,6 +31,11 @@ enum KernelClass {
   KC_WINO4_INPUT,
   KC_WINO4_GEMM,
   KC_WINO4_OUTPUT,
+  KC_PLANE_CAND,     // support plane: candidate compaction
+  KC_PLANE_HYP,      // hypothesis table
+  KC_PLANE_SCORE,    // hypothesis scoring and the argmax
+  KC_PLANE_REFINE,   // fp64 refinement over the winner's inliers
+  KC_PLANE_OBJECTS,  // heights and upright boxes
   KC_COUNT
 };
 
