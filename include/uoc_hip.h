@@ -461,6 +461,59 @@ int uoc_support_plane(const int32_t *d_labels, const float *d_xyz, int B, int H,
 
 
 /* ------------------------------------------------------------------------------------------
+ * Object relations of a frame: contact, occlusion and pick order (no reference counterpart).
+ * d_labels [B][H][W] int32 and d_xyz [B][3][H][W] fp32 metres as for uoc_objects, of which only channel 2 (z) is read;
+ * H*W below 2^29.  Integers only.
+ *
+ * Ids.  id(p) = L when 1 <= L <= 127, else 0 (the background rule of uoc_objects, uoc_track_step and uoc_cc_split).
+ * Id 0 takes part in the pair tables.
+ * Depth.  valid(p) when z is finite and 0 < z <= 65.0f; then zq(p) = (int) rintf(z * 1000.0f) (fp32 product, round
+ * half to even).
+ * Neighbour pairs.  connectivity 4: for every pixel p = (x, y) the pairs (p, (x+1, y)) and (p, (x, y+1)) that lie
+ * inside the frame; connectivity 8: also (p, (x+1, y+1)) and (p, (x-1, y+1)).  Every unordered pair of neighbouring
+ * pixels is visited once; pairs never cross frames.
+ * Tables.  For a pair (p, r) with a = id(p), b = id(r), a != b: border[a][b] += 1 and border[b][a] += 1.  When both
+ * pixels are valid and |zq(p) - zq(r)| < gap_mm: touch[a][b] += 1 and touch[b][a] += 1.  When both are valid and the
+ * gap is >= gap_mm: front[n][f] += 1 with n the id of the pixel of smaller zq and f the other id.  A pair with an
+ * invalid pixel counts in border only.  d_pairs [B][3][128][128] int32 holds the planes UOC_REL_BORDER, UOC_REL_TOUCH
+ * and UOC_REL_FRONT; the diagonals are 0.
+ * Relations, ids 1..127 only.  An id is present when it has at least one pixel.  a occludes b when front[a][b] >=
+ * min_pairs and front[a][b] > front[b][a]; a touches b when touch[a][b] >= min_pairs.
+ * Layers.  Round r = 1, 2, ... gives layer r to every present id that has no layer yet and whose occluders all have a
+ * layer below r; the first round that layers nothing ends the peeling, and the ids left over (occlusion cycles and
+ * what lies below them) get layer -1.
+ * Every count is a sum of ones and every choice is over a strict total order: the result is defined exactly and does
+ * not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_REL_BORDER 0
+#define UOC_REL_TOUCH 1
+#define UOC_REL_FRONT 2
+
+typedef struct uoc_relation_object {   /* one per (frame, id); all zero for id 0 and for an absent id */
+  int32_t pixels;     /* pixels with the id                                                                      */
+  int32_t edge;       /* of which in row 0, row H-1, column 0 or column W-1, each counted once                    */
+  int32_t border;     /* sum over b != a of border[a][b], b = 0 included                                          */
+  int32_t border_bg;  /* border[a][0]                                                                             */
+  int32_t hidden;     /* front[0][a]: unlabelled matter in front of the object                                    */
+  int32_t n_touch;    /* ids in 1..127 that touch a                                                               */
+  int32_t n_above;    /* ids in 1..127 that occlude a                                                             */
+  int32_t n_below;    /* ids in 1..127 that a occludes                                                            */
+  int32_t layer;      /* peeling round, or -1                                                                     */
+  int32_t free;       /* 1 when present, n_above == 0, hidden < min_pairs and edge == 0                           */
+  int32_t order;      /* 1-based rank among the present ids by (layer, -1 after every positive layer; then id)    */
+} uoc_relation_object;
+
+/* 0 for a bad shape. */
+size_t uoc_relations_workspace_bytes(int B, int H, int W);
+/* connectivity 4 or 8, gap_mm in 1..65535, min_pairs >= 1.  d_pairs [B][3][128][128] int32, d_objs [B][128]; d_ws
+ * 16-byte aligned.  Returns UOC_EINVAL before any device work for null pointers, bad ranges, a bad shape (B outside
+ * 1..65535, H*W not below 2^29) or a workspace below uoc_relations_workspace_bytes(B, H, W).  Two memsets and two
+ * launches on `stream`; no host read, nothing synchronises, no state is kept between calls. */
+int uoc_relations(const int32_t *d_labels, const float *d_xyz, int B, int H, int W, int connectivity, int gap_mm,
+                  int min_pairs, int32_t *d_pairs, uoc_relation_object *d_objs, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

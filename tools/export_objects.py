@@ -7,6 +7,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--track [--track-min-iou 0.3] [--track-max-age 5]]
                                    [--components {all,largest} [--min-area 1]]
                                    [--plane [--min-height M]]
+                                   [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -29,6 +30,12 @@ With --plane the support plane of the exported label map is fitted on the device
 `plane_rms`, `plane_u`, `plane_v` describe it, and per row `height_min`, `height_max`, `foot`, `cov2`, `upright_axis`,
 `upright_half`, `upright_center` give the object's height above it and its upright box.  --min-height M adds `standing`
 per row: whether the object's top is at least M metres above the plane.
+
+With --relations the relations of the objects of the exported label map (the tracked or split one when --track or
+--components is given: those are ordinary label maps) are computed on the device (unseenobjectclustering_amd/relations.py,
+8-connected pixel pairs): per row `layer`, `free`, `order`, `n_above` and `edge`, and `front` / `touch`, the K x K
+sub-matrices of the pair tables over the exported objects in row order (front[i][j]: pairs where row i is nearer than
+row j by at least --relations-gap metres; touch[i][j]: pairs closer than that).  --relations-min-pairs pairs make a relation.
 """
 import argparse
 import glob
@@ -47,6 +54,7 @@ from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
+from unseenobjectclustering_amd.relations import relate  # noqa: E402
 from unseenobjectclustering_amd.support import fit_plane, standing_objects  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 
@@ -64,6 +72,17 @@ def plane_arrays(fitted, ids, min_height=None):
     rec.update({name: getattr(fitted, k)[0][ids].cpu().numpy() for k, name in OBJECT_KEYS.items()})
     if min_height is not None:
         rec["standing"] = standing_objects(fitted, min_height)[0][ids].cpu().numpy()
+    return rec
+
+
+RELATION_KEYS = ("layer", "free", "order", "n_above", "edge")
+
+
+def relation_arrays(related, ids):
+    """The --relations arrays of one frame: per exported object (ids = its labels) the record fields of RELATION_KEYS,
+    and the front / touch tables of frame 0 of `related` restricted to those objects."""
+    rec = {k: getattr(related, k)[0][ids].cpu().numpy() for k in RELATION_KEYS}
+    rec.update({k: getattr(related, k)[0][ids][:, ids].cpu().numpy() for k in ("front", "touch")})
     return rec
 
 
@@ -86,6 +105,9 @@ def main():
     ap.add_argument("--min-area", type=int, default=1, help="components below this many pixels become background")
     ap.add_argument("--plane", action="store_true", help="fit the support plane and add heights and upright boxes")
     ap.add_argument("--min-height", type=float, default=None, help="with --plane: add `standing` (top at least this high, metres)")
+    ap.add_argument("--relations", action="store_true", help="add layers, pick order and the front / touch tables of the objects")
+    ap.add_argument("--relations-gap", type=float, default=0.015, help="depth step (metres) that puts a pixel in front of its neighbour")
+    ap.add_argument("--relations-min-pairs", type=int, default=8, help="pixel pairs that make a relation")
     args = ap.parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
@@ -135,6 +157,10 @@ def main():
         if args.plane:
             fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
+        if args.relations:
+            related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
+                             connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)
+            rec.update(relation_arrays(related, objs.label.long()))
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")

@@ -112,6 +112,10 @@ def _declare(lib):
     lib.uoc_plane_workspace_bytes.restype = c_size_t
     lib.uoc_support_plane.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32, P, P, P, P, c_size_t, P]
     lib.uoc_support_plane.restype = c_int
+    lib.uoc_relations_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.uoc_relations_workspace_bytes.restype = c_size_t
+    lib.uoc_relations.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]
+    lib.uoc_relations.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -150,7 +154,8 @@ EXPORTED_SYMBOLS = (
     "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
-    "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
+    "uoc_relations_workspace_bytes", "uoc_relations", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -185,6 +190,14 @@ class UocPlaneObject(ctypes.Structure):
                 ("cov2", c_float * 3), ("axis", c_float * 2), ("half", c_float * 3), ("center", c_float * 3)]
 
 
+class UocRelationObject(ctypes.Structure):
+    """Mirror of uoc_relation_object (include/uoc_hip.h): one per (frame, id)."""
+    _fields_ = [(name, c_int32) for name in ("pixels", "edge", "border", "border_bg", "hidden", "n_touch", "n_above", "n_below",
+                                             "layer", "free", "order")]
+
+
+REL_BORDER, REL_TOUCH, REL_FRONT = 0, 1, 2      # include/uoc_hip.h: UOC_REL_*, the planes of uoc_relations' d_pairs
+REL_MAX_GAP_MM = 65535
 PLANE_MAX_HYP = 1024            # include/uoc_hip.h: num_hyp in 1..1024, tau_mm in 1..1000
 PLANE_MAX_TAU_MM = 1000
 

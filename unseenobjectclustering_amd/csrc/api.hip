@@ -27,7 +27,7 @@ int EnvInt::get() {
 }  // namespace uoc
 
 extern "C" {
-int uoc_version(void) { return 102; }
+int uoc_version(void) { return 103; }
 int uoc_is_dev_build(void) {
   return 0;
 }

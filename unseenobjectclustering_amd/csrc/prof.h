@@ -36,6 +36,8 @@ enum KernelClass {
   KC_PLANE_SCORE,    // hypothesis scoring and the argmax
   KC_PLANE_REFINE,   // fp64 refinement over the winner's inliers
   KC_PLANE_OBJECTS,  // heights and upright boxes
+  KC_REL_PAIRS,      // object relations: memsets and the pair tables
+  KC_REL_DERIVE,     // relations, layers, order
   KC_COUNT
 };
 

@@ -18,7 +18,8 @@ static const char *kNames[KC_COUNT] = {
     "net_misc",          "head",             "fps_step",         "hc_iter",         "hc_finalize",
     "seed_cc",           "assign",           "relabel",          "roi",
     "wino4_input",       "wino4_gemm",       "wino4_output",
-    "plane_candidates",  "plane_hypotheses", "plane_score",      "plane_refine",    "plane_objects"};
+    "plane_candidates",  "plane_hypotheses", "plane_score",      "plane_refine",    "plane_objects",
+    "relations_pairs",   "relations_derive"};
 
 struct Rec {
   int kc;
