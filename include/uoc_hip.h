@@ -514,6 +514,57 @@ int uoc_relations(const int32_t *d_labels, const float *d_xyz, int B, int H, int
 
 
 /* ------------------------------------------------------------------------------------------
+ * Table occupancy and placement: free space on the support plane (no reference counterpart).
+ * d_labels [B][H][W] int32 and d_xyz [B][3][H][W] fp32 metres as for uoc_objects; d_planes [B] as uoc_support_plane
+ * writes them, or filled in by the caller; H*W below 2^31.  Every output is an integer.
+ *
+ * F. The frame in integers, S = 16384.  A plane record is used when found == 1, every component of normal, u, v is
+ * finite with magnitude <= 2, d is finite with |d| <= 1000 and qc_c = (int) rintf(centroid[c] * 1000.0f) (fp32 product)
+ * has |qc_c| <= 32767; any other record is a frame without a plane.  N_c = (int) rint((double) normal[c] * 16384.0),
+ * U_c, V_c likewise from u, v, D = (int64) rint((double) d * 16384000.0): each one correctly rounded operation (the
+ * double products are exact).  d_frame [B][16] int64 = N[3], D, U[3], V[3], qc[3], 1, 0, 0.  A frame without a plane has
+ * a zero frame record, all-zero state / owner / dist2 / counts, and every query answered (-1, -1, 0, 0).
+ * P. Points.  A pixel takes part when x, y, z are finite, z > 0 and q_c = (int) rintf(c * 1000.0f) has |q_c| <= 32767
+ * for c = x, y, z (uoc_support_plane's rule A without its label condition).  id(p) = L when 1 <= L <= 127, else 0.
+ * In int64: T = N.q + D (height above the plane in mm * 2^14), A = U.(q - qc), Bv = V.(q - qc).  Bound: |N_c|, |U_c|,
+ * |V_c| <= 32768 and |q_c - qc_c| <= 65534, so |A|, |Bv|, |N.q| <= 3 * 32768 * 65534 < 2^33, and |D| < 2^34.
+ * i = floor(A / (cell_mm * S)) + G/2 and j = floor(Bv / (cell_mm * S)) + G/2, floor towards minus infinity.  A point
+ * with i or j outside [0, G) adds one to `outside` and is otherwise ignored.  Else, with id = id(p):
+ *   T < -tau_mm*S: ignored;  else id != 0 or T > h_obs_mm*S: obstacle, n_obs[i][j] += 1, owner[i][j] = max(owner, id);
+ *   else T <= tau_mm*S: table, n_table[i][j] += 1;  else ignored.
+ * C. Cells.  state = 2 (obstacle) when n_obs >= min_pts, else 1 (table) when n_table >= min_pts, else 0 (unknown).
+ * owner is 0 unless state is 2.  cells[a], a = 1..127: the obstacle cells whose owner is a.
+ * E. Clearance.  A cell is blocking when its state is 2, or 0 with unknown_blocks set; every cell outside the grid is
+ * blocking.  dist2[i][j] = the smallest (i-i')^2 + (j-j')^2 over the blocking cells (i', j'), the outside ones
+ * included: the exact squared Euclidean distance transform, 0 on blocking cells, at most (G/2)^2.
+ * Q. Queries (need2, ai, aj, mode), the same for every frame; the candidates are the cells of state 1.  mode 0
+ * (widest): the candidate of largest dist2, ties to the lowest i*G + j; answer (i, j, dist2, dist2 >= need2).  mode 1
+ * (nearest): among the candidates with dist2 >= need2 the smallest (i-ai)^2 + (j-aj)^2, ties to the larger dist2, then
+ * to the lowest i*G + j; answer (i, j, dist2, 1).  No candidate: (-1, -1, 0, 0).
+ * Every count is a sum of ones and every choice is over a strict total order: the result is defined exactly and does
+ * not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_PLACE_MAX_QUERIES 16
+#define UOC_PLACE_WIDEST 0
+#define UOC_PLACE_NEAREST 1
+
+/* 0 for a bad shape (B outside 1..65535, H*W not below 2^31) or a bad G. */
+size_t uoc_placement_workspace_bytes(int B, int H, int W, int G);
+/* G a multiple of 8 in 8..512; cell_mm, tau_mm in 1..1000; h_obs_mm in 0..1000; min_pts in 1..65535; unknown_blocks 0
+ * or 1; Q in 0..16.  h_queries: a HOST array [Q][4] int32 (nullable when Q == 0), read before the call returns:
+ * need2 in 0..2^30, ai and aj in -4096..4095, mode 0 or 1.  d_state, d_owner, d_dist2 [B][G][G] int32; d_counts
+ * [B][128] int32, word 0 = outside, words 1..127 = cells; d_frame [B][16] int64; d_answers [B][Q][4] int32 (nullable
+ * when Q == 0); d_ws 16-byte aligned.  Returns UOC_EINVAL before any device work for null pointers, bad ranges, a bad
+ * shape or a workspace below uoc_placement_workspace_bytes(B, H, W, G); a rejected call writes nothing.  Three
+ * memsets and three launches on `stream`, a fourth when Q > 0; no host read of device memory, nothing synchronises,
+ * no state is kept between calls. */
+int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *d_planes, int B, int H, int W, int G,
+                  int cell_mm, int h_obs_mm, int tau_mm, int min_pts, int unknown_blocks, const int32_t *h_queries, int Q,
+                  int32_t *d_state, int32_t *d_owner, int32_t *d_dist2, int32_t *d_counts, int64_t *d_frame,
+                  int32_t *d_answers, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

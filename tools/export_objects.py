@@ -8,6 +8,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--components {all,largest} [--min-area 1]]
                                    [--plane [--min-height M]]
                                    [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
+                                   [--placement RADIUS_M [--grid 256] [--cell-mm 10]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -36,6 +37,13 @@ With --relations the relations of the objects of the exported label map (the tra
 8-connected pixel pairs): per row `layer`, `free`, `order`, `n_above` and `edge`, and `front` / `touch`, the K x K
 sub-matrices of the pair tables over the exported objects in row order (front[i][j]: pairs where row i is nearer than
 row j by at least --relations-gap metres; touch[i][j]: pairs closer than that).  --relations-min-pairs pairs make a relation.
+
+With --placement RADIUS_M the free space on the support plane of the exported label map (the tracked or split one
+likewise) is computed on the device (unseenobjectclustering_amd/placement.py) on a grid of --grid x --grid cells of
+--cell-mm millimetres: `place_state` (0 unknown, 1 table, 2 obstacle) and `place_dist2` (squared clearance in cells), the
+--grid x --grid maps; `place_widest_cell` = (i, j, dist2, ok), the table cell with the most room and whether a disc of
+RADIUS_M metres fits there ((-1, -1, 0, 0) without a table cell), and `place_widest_xyz`, that cell's centre in camera
+coordinates (NaN without one).  The plane is fitted for it whether or not --plane is given.
 """
 import argparse
 import glob
@@ -54,6 +62,7 @@ from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
+from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
 from unseenobjectclustering_amd.relations import relate  # noqa: E402
 from unseenobjectclustering_amd.support import fit_plane, standing_objects  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
@@ -86,6 +95,16 @@ def relation_arrays(related, ids):
     return rec
 
 
+def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm):
+    """The --placement arrays of one frame: the grid maps and the widest spot for a disc of `radius` metres."""
+    cell = cell_mm / 1000.0
+    placed = free_space(labels, xyz, fitted, grid=grid, cell=cell, queries=[(need2(radius, cell), 0, 0, WIDEST)])
+    ans = placed.answers[0, 0].cpu().numpy()
+    spot = cell_to_camera(placed, 0, ans[0], ans[1]) if ans[0] >= 0 else np.full(3, np.nan)
+    return {"place_state": placed.state[0].cpu().numpy(), "place_dist2": placed.dist2[0].cpu().numpy(),
+            "place_widest_cell": ans, "place_widest_xyz": spot.astype(np.float64)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpu", type=int, default=0)
@@ -108,6 +127,10 @@ def main():
     ap.add_argument("--relations", action="store_true", help="add layers, pick order and the front / touch tables of the objects")
     ap.add_argument("--relations-gap", type=float, default=0.015, help="depth step (metres) that puts a pixel in front of its neighbour")
     ap.add_argument("--relations-min-pairs", type=int, default=8, help="pixel pairs that make a relation")
+    ap.add_argument("--placement", type=float, default=None, metavar="RADIUS_M",
+                    help="add the free space on the support plane and the widest spot for a disc of this radius (metres)")
+    ap.add_argument("--grid", type=int, default=256, help="with --placement: cells per side (a multiple of 8 in 8..512)")
+    ap.add_argument("--cell-mm", type=int, default=10, help="with --placement: cell size in millimetres")
     args = ap.parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
@@ -154,9 +177,13 @@ def main():
                 ids = inverse[ids]
             rows = comp[ids].cpu().numpy()
             rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
-        if args.plane:
+        if args.plane or args.placement is not None:
             fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
+        if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
+        if args.placement is not None:
+            rec.update(placement_arrays(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
+                                        fitted, args.placement, args.grid, args.cell_mm))
         if args.relations:
             related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
                              connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)

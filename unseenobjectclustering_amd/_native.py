@@ -116,6 +116,10 @@ def _declare(lib):
     lib.uoc_relations_workspace_bytes.restype = c_size_t
     lib.uoc_relations.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]
     lib.uoc_relations.restype = c_int
+    lib.uoc_placement_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.uoc_placement_workspace_bytes.restype = c_size_t
+    lib.uoc_placement.argtypes = [P, P, P] + [c_int] * 9 + [P, c_int, P, P, P, P, P, P, P, c_size_t, P]
+    lib.uoc_placement.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -155,7 +159,7 @@ EXPORTED_SYMBOLS = (
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
     "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
-    "uoc_relations_workspace_bytes", "uoc_relations", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -200,6 +204,13 @@ REL_BORDER, REL_TOUCH, REL_FRONT = 0, 1, 2      # include/uoc_hip.h: UOC_REL_*, 
 REL_MAX_GAP_MM = 65535
 PLANE_MAX_HYP = 1024            # include/uoc_hip.h: num_hyp in 1..1024, tau_mm in 1..1000
 PLANE_MAX_TAU_MM = 1000
+PLACE_WIDEST, PLACE_NEAREST = 0, 1              # include/uoc_hip.h: UOC_PLACE_*, the mode of a placement query
+PLACE_MAX_QUERIES = 16
+PLACE_MAX_GRID = 512                            # grid: a multiple of 8 in 8..512
+PLACE_MAX_MM = 1000                             # cell_mm, tau_mm in 1..1000, h_obs_mm in 0..1000
+PLACE_MAX_MIN_PTS = 65535
+PLACE_MAX_ANCHOR = 4096                         # a query's anchor cell lies in -4096..4095
+PLACE_SCALE = 16384                             # S of the integer frame
 
 
 class UocTrack(ctypes.Structure):

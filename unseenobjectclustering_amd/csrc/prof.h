@@ -38,6 +38,8 @@ enum KernelClass {
   KC_PLANE_OBJECTS,  // heights and upright boxes
   KC_REL_PAIRS,      // object relations: memsets and the pair tables
   KC_REL_DERIVE,     // relations, layers, order
+  KC_PLACE_RASTER,     // placement: memsets and the top-down raster of the points
+  KC_PLACE_TRANSFORM,  // cells, the distance transform and the queries
   KC_COUNT
 };
 

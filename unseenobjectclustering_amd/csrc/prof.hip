@@ -19,7 +19,8 @@ static const char *kNames[KC_COUNT] = {
     "seed_cc",           "assign",           "relabel",          "roi",
     "wino4_input",       "wino4_gemm",       "wino4_output",
     "plane_candidates",  "plane_hypotheses", "plane_score",      "plane_refine",    "plane_objects",
-    "relations_pairs",   "relations_derive"};
+    "relations_pairs",   "relations_derive",
+    "placement_raster",  "placement_transform"};
 
 struct Rec {
   int kc;

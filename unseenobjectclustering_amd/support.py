@@ -36,7 +36,8 @@ OBJECT_FIELDS = tuple(_OBJECT)
 class PlaneResult:
     """Device tensors.  Per frame: found, candidates, inliers, hyp [B] int32; normal, centroid, eig, u, v [B,3]; d, rms [B].
     Per (frame, id): count [B,128] int32; height_min, height_max [B,128]; foot, axis [B,128,2]; cov2, half, center
-    [B,128,3].  height: [B,H,W] (NaN where there is no valid point) with height_map=True, else None."""
+    [B,128,3].  height: [B,H,W] (NaN where there is no valid point) with height_map=True, else None.  records: the
+    uoc_plane records themselves, [B,21] int32 (what placement.free_space reads in place)."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -101,7 +102,8 @@ def fit_plane(labels, xyz, num_hyp=256, tau=0.010, seed=1, height_map=False) -> 
     planes, objs, height = plane_records(lab, xyz.to(torch.float32).contiguous(), num_hyp, tau_mm, seed, height_map)
     fields = {k: _view(planes, _PLANE, k, k in PLANE_INT_FIELDS) for k in PLANE_FIELDS}
     fields.update({k: _view(objs, _OBJECT, k, k == "count") for k in OBJECT_FIELDS})
-    return PlaneResult(height=height, num_hyp=int(num_hyp), tau_mm=tau_mm, seed=int(seed) & 0xFFFFFFFF, **fields)
+    return PlaneResult(height=height, num_hyp=int(num_hyp), tau_mm=tau_mm, seed=int(seed) & 0xFFFFFFFF, records=planes,
+                       **fields)
 
 
 def standing_objects(result, min_height):
