@@ -565,6 +565,57 @@ int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *
 
 
 /* ------------------------------------------------------------------------------------------
+ * Grasp candidates: a parallel-jaw fit on the table grid (no reference counterpart).
+ * d_state, d_owner [B][G][G] int32 as uoc_placement writes them, G a multiple of 8 in 8..512.  Top-down grasps only:
+ * the gripper closes along a direction in the plane, the fingers come down on the table.  Every output is an integer.
+ *
+ * D. Directions, S = 16384.  h_dirs: a HOST array [A][2] int32 of closing directions (Cx_k, Cy_k) in units of 1/S, every
+ * component in [-S, S]; the Python wrapper fills it with rint(cos(pi k / A) S), rint(sin(pi k / A) S) in float64.  No
+ * kernel calls a trigonometric function.  Parameters, in cells: A in 1..32 directions; M in 0..8, the lateral offsets
+ * m = -M..M; Wmax in 1..64, the largest opening; gap in 0..4, the clearance between a finger and the object; F in 1..8,
+ * the finger thickness; Hp in 0..4, the pad half-length; unknown_blocks 0 or 1.
+ * K. Cells.  A cell whose state is outside 0..2, or whose state is 2 with an owner outside 1..127, counts as unknown.
+ * A. Anchor.  For id a in 1..127: n_a = the cells with state == 2 and owner == a, Si, Sj the sums of their indices.
+ * n_a == 0: the id is absent.  Else, in int64, ax = (S (2 Si + n_a)) / (2 n_a) and ay likewise from Sj, floor division:
+ * the centroid of the cell centres in units of 1/S cell.
+ * S. Samples.  X = ax + t Cx_k - l Cy_k, Y = ay + t Cy_k + l Cx_k, cell (X >> 14, Y >> 14) with arithmetic shifts
+ * (floor).  Class of a sample relative to a: OUT when the cell is outside [0, G)^2; OWN: state 2 and owner a; OTHER:
+ * state 2 and another owner in 1..127; FREE: state 1, or state 0 when unknown_blocks == 0; UNKNOWN: everything else.
+ * C. Candidate (k, m).  The pad strip is the lines l = m-Hp .. m+Hp; the search range is t = -R..R, R = 2 Wmax.  The
+ * first code that applies:
+ *   -1 (MISS)     no OWN sample in the strip over the search range; tlo = 0
+ *   -2 (WIDE)     tlo / thi = the smallest / largest t of an OWN sample over the whole strip, w = thi - tlo + 1 > Wmax
+ *   -3 (PINCHED)  an OTHER or OUT sample in the strip for t in [tlo, thi]
+ *   -4 (BLOCKED)  a sample that is not FREE in the strip for t in [tlo-gap-F, tlo-1] or [thi+1, thi+gap+F] (these t may
+ *                 lie beyond -R..R; the sample formula applies there, too)
+ *   w  (>= 1)     otherwise
+ * d_cand [B][128][A][2M+1][2] int32 = (code, tlo); the rows of id 0 and of absent ids are all zero.
+ * B. Best.  d_best [B][128][8] int32 = (ok, k, m, tlo, w, ax, ay, n_ok), n_ok = the candidates with a positive code.
+ * The winner is the maximum of the 32-bit key 1 + (((M-|m|) << 24) | ((Wmax-w) << 16) | ((A-1-k) << 8) | (m >= 0)):
+ * nearest to the centroid, then narrowest, then lowest k, then +m before -m; a strict total order over (k, m).
+ * Without a candidate of positive code: (0, -1, 0, 0, 0, ax, ay, 0).  Absent id and id 0: all zero.  A frame whose
+ * state is all zero (a frame without a plane) has all-zero outputs.
+ * Every count is a sum of ones and every choice is over a strict total order: the result is defined exactly and does
+ * not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_GRASP_MAX_DIRS 32
+#define UOC_GRASP_MISS (-1)
+#define UOC_GRASP_WIDE (-2)
+#define UOC_GRASP_PINCHED (-3)
+#define UOC_GRASP_BLOCKED (-4)
+
+/* 0 for B outside 1..65535, a bad G, A outside 1..32 or M outside 0..8. */
+size_t uoc_grasp_workspace_bytes(int B, int G, int A, int M);
+/* Ranges as in D above.  h_dirs is read before the call returns.  d_ws 16-byte aligned.  Returns UOC_EINVAL before any
+ * device work for null pointers, bad ranges or a workspace below uoc_grasp_workspace_bytes(B, G, A, M); a rejected call
+ * writes nothing, the workspace included.  One memset and two launches on `stream`; no host read of device memory,
+ * nothing synchronises, no state is kept between calls. */
+int uoc_grasp(const int32_t *d_state, const int32_t *d_owner, int B, int G, const int32_t *h_dirs, int A, int M, int Wmax,
+              int gap, int F, int Hp, int unknown_blocks, int32_t *d_cand, int32_t *d_best, void *d_ws, size_t ws_bytes,
+              void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

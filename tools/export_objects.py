@@ -9,6 +9,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--plane [--min-height M]]
                                    [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
                                    [--placement RADIUS_M [--grid 256] [--cell-mm 10]]
+                                   [--grasp MAX_OPEN_M [--grasp-angles 16] [--grasp-offsets 2]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -44,6 +45,13 @@ likewise) is computed on the device (unseenobjectclustering_amd/placement.py) on
 --grid x --grid maps; `place_widest_cell` = (i, j, dist2, ok), the table cell with the most room and whether a disc of
 RADIUS_M metres fits there ((-1, -1, 0, 0) without a table cell), and `place_widest_xyz`, that cell's centre in camera
 coordinates (NaN without one).  The plane is fitted for it whether or not --plane is given.
+
+With --grasp MAX_OPEN_M the parallel-jaw grasp candidates of the exported objects are computed on the device
+(unseenobjectclustering_amd/grasp.py) on the --grid x --grid grid of the placement stage, which runs for it with its
+defaults whether or not --placement is given, for a gripper that opens to MAX_OPEN_M metres: per row `grasp_best` =
+(ok, k, m, tlo, w, ax, ay, n_ok) and `grasp_cand`, the (code, tlo) of every direction and lateral offset; and the pose
+of the best candidate, `grasp_center` and `grasp_axis` (camera coordinates; NaN for a row without a candidate),
+`grasp_width` and `grasp_opening` (metres; NaN likewise).  `grasp_dirs` is the direction table.
 """
 import argparse
 import glob
@@ -61,6 +69,7 @@ from test_images import load_weights  # noqa: E402
 from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
+from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
 from unseenobjectclustering_amd.relations import relate  # noqa: E402
@@ -81,6 +90,24 @@ def plane_arrays(fitted, ids, min_height=None):
     rec.update({name: getattr(fitted, k)[0][ids].cpu().numpy() for k, name in OBJECT_KEYS.items()})
     if min_height is not None:
         rec["standing"] = standing_objects(fitted, min_height)[0][ids].cpu().numpy()
+    return rec
+
+
+GRASP_KEYS = ("grasp_best", "grasp_cand", "grasp_dirs", "grasp_center", "grasp_axis", "grasp_width", "grasp_opening")
+
+
+def grasp_arrays(grasped, ids):
+    """The --grasp arrays of one frame: per exported object (ids = its labels) the best record, the candidate table and
+    the pose of the best candidate of frame 0 of `grasped`."""
+    ids = [int(a) for a in ids]
+    rec = {"grasp_best": grasped.best[0][ids].cpu().numpy(), "grasp_cand": grasped.cand[0][ids].cpu().numpy(),
+           "grasp_dirs": np.asarray(grasped.dirs, np.int32)}
+    poses = [pose(grasped, 0, a) for a in ids]
+    nan3 = np.full(3, np.nan)
+    rec["grasp_center"] = np.array([p.center if p else nan3 for p in poses], np.float64).reshape(len(ids), 3)
+    rec["grasp_axis"] = np.array([p.axis if p else nan3 for p in poses], np.float64).reshape(len(ids), 3)
+    rec["grasp_width"] = np.array([p.width_m if p else np.nan for p in poses], np.float64)
+    rec["grasp_opening"] = np.array([p.opening_m if p else np.nan for p in poses], np.float64)
     return rec
 
 
@@ -105,7 +132,7 @@ def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm):
             "place_widest_cell": ans, "place_widest_xyz": spot.astype(np.float64)}
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--imgdir", required=True)
@@ -131,7 +158,15 @@ def main():
                     help="add the free space on the support plane and the widest spot for a disc of this radius (metres)")
     ap.add_argument("--grid", type=int, default=256, help="with --placement: cells per side (a multiple of 8 in 8..512)")
     ap.add_argument("--cell-mm", type=int, default=10, help="with --placement: cell size in millimetres")
-    args = ap.parse_args()
+    ap.add_argument("--grasp", type=float, default=None, metavar="MAX_OPEN_M",
+                    help="add the parallel-jaw grasp candidates of the objects for a gripper that opens this far (metres)")
+    ap.add_argument("--grasp-angles", type=int, default=16, help="with --grasp: closing directions over half a turn (1..32)")
+    ap.add_argument("--grasp-offsets", type=int, default=2, help="with --grasp: lateral offsets to either side, in cells (0..8)")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
     if network_mode() != "RGBD_ADD":
@@ -177,13 +212,18 @@ def main():
                 ids = inverse[ids]
             rows = comp[ids].cpu().numpy()
             rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
-        if args.plane or args.placement is not None:
+        if args.plane or args.placement is not None or args.grasp is not None:
             fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
         if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
         if args.placement is not None:
             rec.update(placement_arrays(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
                                         fitted, args.placement, args.grid, args.cell_mm))
+        if args.grasp is not None:
+            placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
+                                grid=args.grid, cell=args.cell_mm / 1000.0)
+            grasped = candidates(placed, angles=args.grasp_angles, offsets=args.grasp_offsets, max_open=args.grasp)
+            rec.update(grasp_arrays(grasped, objs.label.long().cpu().tolist()))
         if args.relations:
             related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
                              connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)

@@ -120,6 +120,10 @@ def _declare(lib):
     lib.uoc_placement_workspace_bytes.restype = c_size_t
     lib.uoc_placement.argtypes = [P, P, P] + [c_int] * 9 + [P, c_int, P, P, P, P, P, P, P, c_size_t, P]
     lib.uoc_placement.restype = c_int
+    lib.uoc_grasp_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.uoc_grasp_workspace_bytes.restype = c_size_t
+    lib.uoc_grasp.argtypes = [P, P, c_int, c_int, P] + [c_int] * 7 + [P, P, P, c_size_t, P]
+    lib.uoc_grasp.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -159,7 +163,8 @@ EXPORTED_SYMBOLS = (
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
     "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
-    "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
+    "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -211,6 +216,14 @@ PLACE_MAX_MM = 1000                             # cell_mm, tau_mm in 1..1000, h_
 PLACE_MAX_MIN_PTS = 65535
 PLACE_MAX_ANCHOR = 4096                         # a query's anchor cell lies in -4096..4095
 PLACE_SCALE = 16384                             # S of the integer frame
+GRASP_MISS, GRASP_WIDE, GRASP_PINCHED, GRASP_BLOCKED = -1, -2, -3, -4      # include/uoc_hip.h: UOC_GRASP_*, a candidate's code
+GRASP_SCALE = 16384                             # S of the direction table and of the anchor
+GRASP_MAX_DIRS = 32                             # A in 1..32
+GRASP_MAX_OFFSETS = 8                           # M in 0..8
+GRASP_MAX_OPEN = 64                             # Wmax in 1..64 cells
+GRASP_MAX_GAP = 4                               # gap in 0..4 cells
+GRASP_MAX_FINGER = 8                            # F in 1..8 cells
+GRASP_MAX_PAD = 4                               # Hp in 0..4 cells
 
 
 class UocTrack(ctypes.Structure):

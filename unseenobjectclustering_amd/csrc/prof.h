@@ -40,6 +40,8 @@ enum KernelClass {
   KC_REL_DERIVE,     // relations, layers, order
   KC_PLACE_RASTER,     // placement: memsets and the top-down raster of the points
   KC_PLACE_TRANSFORM,  // cells, the distance transform and the queries
+  KC_GRASP_MOMENTS,     // grasp candidates: the memset and the per-id moments
+  KC_GRASP_CANDIDATES,  // the class table, the candidates and the best record
   KC_COUNT
 };
 

@@ -20,7 +20,8 @@ static const char *kNames[KC_COUNT] = {
     "wino4_input",       "wino4_gemm",       "wino4_output",
     "plane_candidates",  "plane_hypotheses", "plane_score",      "plane_refine",    "plane_objects",
     "relations_pairs",   "relations_derive",
-    "placement_raster",  "placement_transform"};
+    "placement_raster",  "placement_transform",
+    "grasp_moments",     "grasp_candidates"};
 
 struct Rec {
   int kc;
