@@ -616,6 +616,59 @@ int uoc_grasp(const int32_t *d_state, const int32_t *d_owner, int B, int G, cons
 
 
 /* ------------------------------------------------------------------------------------------
+ * Elevation map: object tops and stacking spots on the table grid (no reference counterpart).
+ * d_labels [B][H][W] int32 and d_xyz [B][3][H][W] fp32 metres as for uoc_placement; d_frame [B][16] int64 exactly as
+ * uoc_placement wrote it, or filled in by the caller; G, cell_mm and tau_mm as given to uoc_placement make the two grids
+ * coincide cell for cell.  H*W below 2^31.  S = 16384.  Every output is an integer.
+ *
+ * F. Frame.  A record is used when word 13 is 1, words 0..2 (N) and 4..9 (U, V) have magnitude <= 32768, |word 3| (D)
+ * <= 2^34 and words 10..12 (qc) have magnitude <= 32767, which keeps the int64 bounds of uoc_placement's step P for
+ * caller-supplied records; any other record is a frame without a plane: elev all UOC_ELEV_NONE; owner, pts, near, dist2,
+ * info all zero; every row of tops (0, 0, -1, -1, 0, 0, 0, 0); every answer (-1, -1, 0, 0).
+ * P. Points.  uoc_placement's rule P unchanged: participation, q, T, A, Bv, i, j with floor division, id(p).  A point
+ * outside the grid adds 1 to `outside`; a point with T < -tau_mm*S is ignored.  A kept point has hq = min(T >> 14, 32767)
+ * (arithmetic shift: a floor, T = -1 gives -1), key = hq + 1024 (in 24..33791) and word = (key << 7) | id.
+ * H. Cells, first pass.  pts[c] = the kept points of cell c, top[c] = their largest word: the highest point, ties to the
+ * larger id.  pts > 0: elev[c] = (top >> 7) - 1024, owner[c] = top & 127; else elev[c] = UOC_ELEV_NONE, owner[c] = 0.
+ * N. Cells, second pass over the same points.  near[c] = the kept points with key >= (top[c] >> 7) - step_mm; a cell is
+ * solid when near >= min_pts (a lone mixed pixel above a surface makes its cell not solid, not a false top).
+ * L. Level.  Cells outside the grid are not solid.  A cell c is blocking when it is not solid, or when one of its four
+ * edge neighbours c' is not solid, has owner(c') != owner(c) or |elev(c) - elev(c')| > step_mm: a level region has one
+ * owner and climbs at most step_mm per cell.  The cells on the grid's border are always blocking.
+ * E. Clearance.  dist2 = the exact squared Euclidean distance transform to the nearest blocking cell, the cells outside
+ * the grid included, as uoc_placement's step E: 0 on blocking cells, at most (G/2)^2.
+ * T. d_tops [B][128][8] int32, id a = 0..127 (0: the table and whatever is unlabelled) = (cells, level, i, j, dist2,
+ * elev_at, elev_max, elev_mean): cells = the solid cells owned by a; level = those that are not blocking; (i, j) = the
+ * level cell of largest dist2, ties to the lowest i*G + j, elev_at its elev ((-1, -1), dist2 = elev_at = 0 when level ==
+ * 0); elev_max = the largest elev over the solid cells (0 when cells == 0); elev_mean = floor(sum / level) towards minus
+ * infinity of the int64 sum of elev over the level cells (0 when level == 0).
+ * Q. Queries (need2, id, hmin_mm, hmax_mm), the same for every frame.  The candidates are the cells that are not
+ * blocking with hmin <= elev <= hmax and owner == id (id in 0..127), or owner >= 1 (id == -1: any object, never the
+ * table).  Answer (i, j, dist2, dist2 >= need2) of the candidate of largest dist2, ties to the lowest i*G + j; without a
+ * candidate (-1, -1, 0, 0).
+ * I. d_info [B][4] int32 = (found, outside, the cells with pts > 0, the solid cells).
+ * Every count is a sum of ones and every choice is over a strict total order: the result is defined exactly and does
+ * not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_ELEV_MAX_QUERIES 16
+#define UOC_ELEV_NONE (-32768)
+
+/* 0 for a bad shape (B outside 1..65535, H*W not below 2^31) or a bad G. */
+size_t uoc_elevation_workspace_bytes(int B, int H, int W, int G);
+/* G a multiple of 8 in 8..512; cell_mm, tau_mm, step_mm in 1..1000; min_pts in 1..65535; Q in 0..16.  h_queries: a HOST
+ * array [Q][4] int32 (nullable when Q == 0), read before the call returns: need2 in 0..2^30, id in -1..127, hmin_mm and
+ * hmax_mm in -32768..32767.  d_elev, d_owner, d_pts, d_near, d_dist2 [B][G][G] int32; d_tops [B][128][8] int32; d_info
+ * [B][4] int32; d_answers [B][Q][4] int32 (nullable when Q == 0); d_ws 16-byte aligned.  Returns UOC_EINVAL before any
+ * device work for null pointers, bad ranges, a bad shape, a workspace below uoc_elevation_workspace_bytes(B, H, W, G) or
+ * one that is not 16-byte aligned; a rejected call writes nothing, the workspace included.  Four memsets and five
+ * launches on `stream`; no host read of device memory, nothing synchronises, no state is kept between calls. */
+int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_frame, int B, int H, int W, int G,
+                  int cell_mm, int tau_mm, int step_mm, int min_pts, const int32_t *h_queries, int Q, int32_t *d_elev,
+                  int32_t *d_owner, int32_t *d_pts, int32_t *d_near, int32_t *d_dist2, int32_t *d_tops, int32_t *d_info,
+                  int32_t *d_answers, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

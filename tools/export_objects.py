@@ -10,6 +10,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
                                    [--placement RADIUS_M [--grid 256] [--cell-mm 10]]
                                    [--grasp MAX_OPEN_M [--grasp-angles 16] [--grasp-offsets 2]]
+                                   [--elevation STEP_M [--elevation-min-pts 2]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -52,6 +53,14 @@ defaults whether or not --placement is given, for a gripper that opens to MAX_OP
 (ok, k, m, tlo, w, ax, ay, n_ok) and `grasp_cand`, the (code, tlo) of every direction and lateral offset; and the pose
 of the best candidate, `grasp_center` and `grasp_axis` (camera coordinates; NaN for a row without a candidate),
 `grasp_width` and `grasp_opening` (metres; NaN likewise).  `grasp_dirs` is the direction table.
+
+With --elevation STEP_M the elevation map of the frame is computed on the device (unseenobjectclustering_amd/elevation.py)
+on the --grid x --grid grid of the placement stage, which runs for it with its defaults whether or not --placement is
+given; cells that climb at most STEP_M metres from one to the next and hold --elevation-min-pts points near their top are
+level.  Per row `top_cells` and `top_level`, the object's solid and level cells; `top_cell` = (i, j), the level cell with
+the most room ((-1, -1) without one), `top_clear_m`, the distance from there to the nearest cell that is not level,
+`top_height_m`, its height above the plane, and `top_xyz`, its centre lifted onto the top, camera coordinates (NaN
+without a level cell).  With --placement RADIUS_M also `top_fits`: whether a disc of RADIUS_M metres fits there.
 """
 import argparse
 import glob
@@ -69,6 +78,7 @@ from test_images import load_weights  # noqa: E402
 from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
+from unseenobjectclustering_amd.elevation import heights, spot  # noqa: E402
 from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
@@ -108,6 +118,24 @@ def grasp_arrays(grasped, ids):
     rec["grasp_axis"] = np.array([p.axis if p else nan3 for p in poses], np.float64).reshape(len(ids), 3)
     rec["grasp_width"] = np.array([p.width_m if p else np.nan for p in poses], np.float64)
     rec["grasp_opening"] = np.array([p.opening_m if p else np.nan for p in poses], np.float64)
+    return rec
+
+
+ELEVATION_KEYS = ("top_cells", "top_level", "top_cell", "top_clear_m", "top_height_m", "top_xyz")
+
+
+def elevation_arrays(raised, ids, radius=None):
+    """The --elevation arrays of one frame: per exported object (ids = its labels) the row of tops of frame 0 of `raised`
+    and its widest level spot; with a radius (metres) also whether a disc of that radius fits there."""
+    ids = [int(a) for a in ids]
+    tops = raised.tops[0][ids].cpu().numpy().reshape(len(ids), 8)
+    spots = [spot(raised, 0, a) for a in ids]
+    rec = {"top_cells": tops[:, 0].copy(), "top_level": tops[:, 1].copy(), "top_cell": tops[:, 2:4].copy(),
+           "top_clear_m": np.array([s.clearance_m if s else np.nan for s in spots], np.float64),
+           "top_height_m": np.array([s.height_m if s else np.nan for s in spots], np.float64),
+           "top_xyz": np.array([s.xyz if s else np.full(3, np.nan) for s in spots], np.float64).reshape(len(ids), 3)}
+    if radius is not None:
+        rec["top_fits"] = (tops[:, 1] > 0) & (tops[:, 4] >= need2(radius, raised.cell_mm / 1000.0))
     return rec
 
 
@@ -162,6 +190,9 @@ def build_parser():
                     help="add the parallel-jaw grasp candidates of the objects for a gripper that opens this far (metres)")
     ap.add_argument("--grasp-angles", type=int, default=16, help="with --grasp: closing directions over half a turn (1..32)")
     ap.add_argument("--grasp-offsets", type=int, default=2, help="with --grasp: lateral offsets to either side, in cells (0..8)")
+    ap.add_argument("--elevation", type=float, default=None, metavar="STEP_M",
+                    help="add the tops of the objects on the elevation map; cells climbing at most this far (metres) are level")
+    ap.add_argument("--elevation-min-pts", type=int, default=2, help="with --elevation: points near a cell's top that make it solid")
     return ap
 
 
@@ -212,7 +243,7 @@ def main():
                 ids = inverse[ids]
             rows = comp[ids].cpu().numpy()
             rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
-        if args.plane or args.placement is not None or args.grasp is not None:
+        if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None:
             fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
         if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
@@ -224,6 +255,12 @@ def main():
                                 grid=args.grid, cell=args.cell_mm / 1000.0)
             grasped = candidates(placed, angles=args.grasp_angles, offsets=args.grasp_offsets, max_open=args.grasp)
             rec.update(grasp_arrays(grasped, objs.label.long().cpu().tolist()))
+        if args.elevation is not None:
+            placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
+                                grid=args.grid, cell=args.cell_mm / 1000.0)
+            raised = heights(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), placed,
+                             step=args.elevation, min_pts=args.elevation_min_pts)
+            rec.update(elevation_arrays(raised, objs.label.long().cpu().tolist(), args.placement))
         if args.relations:
             related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
                              connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)

@@ -124,6 +124,10 @@ def _declare(lib):
     lib.uoc_grasp_workspace_bytes.restype = c_size_t
     lib.uoc_grasp.argtypes = [P, P, c_int, c_int, P] + [c_int] * 7 + [P, P, P, c_size_t, P]
     lib.uoc_grasp.restype = c_int
+    lib.uoc_elevation_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.uoc_elevation_workspace_bytes.restype = c_size_t
+    lib.uoc_elevation.argtypes = [P, P, P] + [c_int] * 8 + [P, c_int] + [P] * 9 + [c_size_t, P]
+    lib.uoc_elevation.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -164,7 +168,7 @@ EXPORTED_SYMBOLS = (
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
     "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
     "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
-    "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -224,6 +228,8 @@ GRASP_MAX_OPEN = 64                             # Wmax in 1..64 cells
 GRASP_MAX_GAP = 4                               # gap in 0..4 cells
 GRASP_MAX_FINGER = 8                            # F in 1..8 cells
 GRASP_MAX_PAD = 4                               # Hp in 0..4 cells
+ELEV_NONE = -32768                              # include/uoc_hip.h: UOC_ELEV_NONE, the elev of a cell without a point
+ELEV_MAX_QUERIES = 16                           # UOC_ELEV_MAX_QUERIES
 
 
 class UocTrack(ctypes.Structure):

@@ -1,0 +1,563 @@
+// Elevation map: object tops and stacking spots on the table grid (include/uoc_hip.h, uoc_elevation).
+// From the label map, the XYZ planes and the integer frame record of uoc_placement: per cell of the same G x G grid the
+// height of the highest point above the plane (elev), its id (owner), the point counts (pts, near), the exact squared
+// Euclidean distance to the nearest cell that is not level (dist2), a per-id table of tops and the answers to up to 16
+// queries.  Integers only.
+//
+// Four memsets (the top words and the accumulators in the workspace, d_pts, d_near, d_info) and five launches:
+//   point_kernel<.., 1>  grid (pixel chunks of CHUNK, frames), 4 waves; a wave owns SUB consecutive pixels.  A lane owns 4
+//                   consecutive pixels per turn (one int4 and three float4 loads) when H*W is a multiple of 4 and the
+//                   pointers are 16-byte aligned, else one pixel.  A kept point is (cell, word), word = (key << 7) | id.
+//                   Per DISTINCT cell of the wave's 256 (64) pixels: ballot + popcount for the count, shuffles for the
+//                   maximum word, then one atomicAdd to pts and one atomicMax to top.
+//   point_kernel<.., 2>  the same traversal; top is complete (kernel boundary).  A point with key >= (top >> 7) - step_mm
+//                   is a near point; one atomicAdd of the combined count per distinct cell.
+//   cell_kernel     grid (strips of 32 columns, frames): elev, owner, solid and blocking from the four edge neighbours
+//                   (their words come from global memory: the strip with its halo at G = 512 does not fit in LDS), the
+//                   counters of info; then g[i][j] = the distance along i to the nearest blocking cell of column j, the
+//                   virtual cells at i = -1 and i = G included: 8 row segments per column scanned up and down, the carry
+//                   between segments through LDS.  g goes to d_dist2.
+//   row_kernel      grid (rows, frames): dist2[i][j] = min over j' of (j-j')^2 + g[i][j']^2 with the virtual columns at
+//                   -1 and G, the plain minimum over the row from LDS, in place.  Per id the counts, the key of the widest
+//                   level cell, the largest elev and the sum of elev: combined per wave over its distinct owners (ballot
+//                   and shuffles), per block in LDS, per frame by integer atomics; per query one 64-bit key per candidate,
+//                   the maximum per wave by shuffles, per block through LDS, per frame by atomicMax.
+//   answer_kernel   one block per frame: the accumulators into the rows of tops, the keys into answers.
+//
+// Determinism: integer adds and maxima commute; a minimum commutes; the keys are strict total orders (the cell index is
+// part of the key), so no result depends on the order in which lanes, waves or blocks arrive.  Nothing of frame b
+// depends on the other frames of the batch.
+//
+// Key of "widest" (0: no candidate).  dist2 <= (G/2)^2 = 2^16, idx = i*G + j < 2^18:
+//   ((dist2 + 1) << 18) | (0x3FFFF - idx)
+#include "common.h"
+#include "prof.h"
+
+#include <limits.h>
+
+namespace uoc {
+namespace {
+
+constexpr int NL = 128;             // ids 0..127; 0 is the table and whatever is unlabelled
+constexpr int WAVES = 4;
+constexpr int SUB = 1024;           // pixels per wave
+constexpr int CHUNK = WAVES * SUB;  // pixels per block
+constexpr int SCALE = 16384;        // S
+constexpr int MAX_G = 512;
+constexpr int MAX_Q = UOC_ELEV_MAX_QUERIES;
+constexpr int NFR = 16;             // int64 words of a frame record
+constexpr int STRIP = 32;           // columns per block of the column pass
+constexpr int SEGS = 8;             // row segments per column: STRIP * SEGS threads
+constexpr int ROW_THREADS = 256;
+constexpr int IDX_MASK = 0x3FFFF;
+constexpr int KEY_BIAS = 1024;      // key = hq + 1024 >= 24: a word of 0 means "no point"
+constexpr int HQ_MAX = 32767;
+
+static_assert(MAX_G * MAX_G <= IDX_MASK + 1, "a cell index must fit the key's low 18 bits");
+static_assert((MAX_G / 2) * (MAX_G / 2) < (1 << 17), "dist2 must fit 17 bits of the key");
+static_assert(STRIP * SEGS == 256 && MAX_G % SEGS == 0, "column pass layout");
+static_assert(((HQ_MAX + KEY_BIAS) << 7 | (NL - 1)) > 0, "a word is a positive int");
+
+struct Frame {
+  int N[3], U[3], V[3], qc[3];
+  long long D;
+  int found;
+};
+
+struct Queries {
+  int v[MAX_Q][4];  // need2, id, hmin_mm, hmax_mm
+};
+
+__device__ __forceinline__ bool within(long long v, long long lim) { return v >= -lim && v <= lim; }
+
+// Step F.  Wave-uniform: every thread reads the same record.
+__device__ __forceinline__ Frame load_frame(const long long *__restrict__ F) {
+  Frame f;
+  bool ok = F[13] == 1 && within(F[3], 1ll << 34);
+  for (int k = 0; k < 3; ++k)
+    ok = ok && within(F[k], 32768) && within(F[4 + k], 32768) && within(F[7 + k], 32768) && within(F[10 + k], 32767);
+  for (int k = 0; k < 3; ++k) {
+    f.N[k] = ok ? (int)F[k] : 0;
+    f.U[k] = ok ? (int)F[4 + k] : 0;
+    f.V[k] = ok ? (int)F[7 + k] : 0;
+    f.qc[k] = ok ? (int)F[10 + k] : 0;
+  }
+  f.D = ok ? F[3] : 0;
+  f.found = ok ? 1 : 0;
+  return f;
+}
+
+__device__ __forceinline__ long long floor_div(long long a, long long c) {  // c > 0
+  const long long q = a / c;
+  return q - ((a - q * c) < 0 ? 1 : 0);
+}
+
+// Step P of one pixel: cell (-1: not kept) and word; returns true when the point lies outside the grid.
+__device__ __forceinline__ bool project(const Frame &f, int cell_div, int t_low, int G, int l, float x, float y, float z,
+                                        int &cell, int &word) {
+  cell = -1;
+  word = 0;
+  if (!(isfinite(x) && isfinite(y) && isfinite(z) && z > 0.f)) return false;
+  const float rx = rintf(x * 1000.0f), ry = rintf(y * 1000.0f), rz = rintf(z * 1000.0f);
+  if (!(fabsf(rx) <= 32767.f && fabsf(ry) <= 32767.f && fabsf(rz) <= 32767.f)) return false;
+  const int qx = (int)rx, qy = (int)ry, qz = (int)rz;
+  const int dx = qx - f.qc[0], dy = qy - f.qc[1], dz = qz - f.qc[2];
+  const long long A = (long long)f.U[0] * dx + (long long)f.U[1] * dy + (long long)f.U[2] * dz;
+  const long long Bv = (long long)f.V[0] * dx + (long long)f.V[1] * dy + (long long)f.V[2] * dz;
+  const long long i = floor_div(A, cell_div) + G / 2, j = floor_div(Bv, cell_div) + G / 2;
+  if ((unsigned long long)i >= (unsigned long long)G || (unsigned long long)j >= (unsigned long long)G) return true;
+  const long long T = (long long)f.N[0] * qx + (long long)f.N[1] * qy + (long long)f.N[2] * qz + f.D;
+  if (T < t_low) return false;
+  const long long hq = min(T >> 14, (long long)HQ_MAX);  // arithmetic shift: a floor; hq >= -tau_mm >= -1000
+  const int id = ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0;
+  cell = (int)i * G + (int)j;
+  word = (((int)hq + KEY_BIAS) << 7) | id;
+  return false;
+}
+
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, __shfl_xor(v, sft));
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, (unsigned long long)__shfl_xor((long long)v, sft));
+  return v;
+}
+
+// Every distinct cell >= 0 among the K slots of the wave's lanes is handed to `emit` once, by one lane, with the number
+// of (lane, slot) places that hold it and the largest of their values w.  Every lane of the wave must call this.
+template <int K, bool MAXW, typename Emit>
+__device__ __forceinline__ void wave_distinct(int (&e)[K], const int (&w)[K], int lane, Emit emit) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    unsigned long long rem = __ballot(e[j] >= 0);
+    while (rem) {
+      const int first = __ffsll((long long)rem) - 1;
+      const int c = __builtin_amdgcn_readlane(e[j], first);
+      int total = 0, mine = 0;
+#pragma unroll
+      for (int k = j; k < K; ++k) {
+        const bool hit = e[k] == c;
+        const unsigned long long m = __ballot(hit);
+        total += __popcll(m);
+        if (k == j) rem &= ~m;
+        if (hit) {
+          e[k] = -1;
+          mine = max(mine, w[k]);
+        }
+      }
+      if constexpr (MAXW) mine = wave_max(mine);
+      if (lane == first) emit(c, total, mine);
+    }
+  }
+}
+
+// ---- 1, 2. the point passes ---------------------------------------------------------------------------------------------
+template <bool VEC, int PASS>
+__global__ __launch_bounds__(256) void point_kernel(const int *__restrict__ labels, const float *__restrict__ xyz,
+                                                    const long long *__restrict__ frame, long long n, int G, int cell_div,
+                                                    int t_low, int step_mm, int *__restrict__ top, int *__restrict__ pts,
+                                                    int *__restrict__ near, int *__restrict__ info) {
+  constexpr int K = VEC ? 4 : 1;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, b = blockIdx.y;
+  const Frame f = load_frame(frame + (size_t)b * NFR);
+  if (!f.found) return;  // uniform per frame
+  const int *L = labels + (size_t)b * n;
+  const float *X = xyz + (size_t)b * 3 * n;
+  const size_t cells = (size_t)G * G;
+  int *TOP = top + (size_t)b * cells, *PTS = pts + (size_t)b * cells, *NEAR = near + (size_t)b * cells;
+  const long long p0 = (long long)c * CHUNK + (long long)w * SUB;
+  int outside = 0;
+  for (int it = 0; it < SUB / (64 * K); ++it) {
+    const long long base = p0 + (long long)it * 64 * K;
+    if (base >= n) break;  // uniform per wave
+    const long long p = base + (long long)lane * K;
+    int e[K], wd[K];
+    bool out[K];
+    if constexpr (VEC) {
+      int4 l4 = make_int4(0, 0, 0, 0);
+      float4 x4 = make_float4(0.f, 0.f, 0.f, 0.f), y4 = x4, z4 = x4;  // z = 0: no point
+      if (p < n) {  // n is a multiple of 4: the four pixels are inside together
+        l4 = *reinterpret_cast<const int4 *>(L + p);
+        x4 = *reinterpret_cast<const float4 *>(X + p);
+        y4 = *reinterpret_cast<const float4 *>(X + n + p);
+        z4 = *reinterpret_cast<const float4 *>(X + 2 * n + p);
+      }
+      out[0] = project(f, cell_div, t_low, G, l4.x, x4.x, y4.x, z4.x, e[0], wd[0]);
+      out[1] = project(f, cell_div, t_low, G, l4.y, x4.y, y4.y, z4.y, e[1], wd[1]);
+      out[2] = project(f, cell_div, t_low, G, l4.z, x4.z, y4.z, z4.z, e[2], wd[2]);
+      out[3] = project(f, cell_div, t_low, G, l4.w, x4.w, y4.w, z4.w, e[3], wd[3]);
+    } else {
+      int l = 0;
+      float x = 0.f, y = 0.f, z = 0.f;
+      if (p < n) {
+        l = L[p];
+        x = X[p];
+        y = X[n + p];
+        z = X[2 * n + p];
+      }
+      out[0] = project(f, cell_div, t_low, G, l, x, y, z, e[0], wd[0]);
+    }
+    if constexpr (PASS == 1) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) outside += __popcll(__ballot(out[k]));
+      wave_distinct<K, true>(e, wd, lane, [&](int cell, int total, int word) {
+        atomicAdd(&PTS[cell], total);
+        atomicMax(&TOP[cell], word);
+      });
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (e[k] >= 0 && (wd[k] >> 7) < (TOP[e[k]] >> 7) - step_mm) e[k] = -1;
+      wave_distinct<K, false>(e, wd, lane, [&](int cell, int total, int) { atomicAdd(&NEAR[cell], total); });
+    }
+  }
+  if (PASS == 1 && lane == 0 && outside) atomicAdd(&info[(size_t)b * 4 + 1], outside);
+}
+
+// ---- 3. cells and the column pass ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(STRIP *SEGS) void cell_kernel(const int *__restrict__ top, const int *__restrict__ pts,
+                                                           const int *__restrict__ near, const long long *__restrict__ frame,
+                                                           int G, int step_mm, int min_pts, int *__restrict__ elev,
+                                                           int *__restrict__ owner, int *__restrict__ g_out,
+                                                           int *__restrict__ info) {
+  __shared__ unsigned short s[MAX_G][STRIP];  // bit 15: blocking; after the upward scan the low bits hold the distance up
+  __shared__ int s_first[SEGS][STRIP], s_last[SEGS][STRIP];
+  __shared__ int s_cnt[2];
+  const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y, j0 = blockIdx.x * STRIP;
+  const bool found = load_frame(frame + (size_t)b * NFR).found != 0;
+  const size_t off = (size_t)b * G * G;
+  if (tid < 2) s_cnt[tid] = 0;
+  __syncthreads();
+  int known = 0, solid = 0;
+  for (int idx = tid; idx < G * STRIP; idx += STRIP * SEGS) {
+    const int i = idx / STRIP, jj = idx % STRIP, j = j0 + jj;
+    if (j >= G) continue;
+    const size_t a = off + (size_t)i * G + j;
+    const int t = top[a], np = pts[a];
+    const bool sol = found && near[a] >= min_pts;  // near <= pts: a solid cell has a point
+    elev[a] = np > 0 ? (t >> 7) - KEY_BIAS : UOC_ELEV_NONE;
+    owner[a] = np > 0 ? (t & (NL - 1)) : 0;
+    known += np > 0;
+    solid += sol;
+    bool blk = !sol || i == 0 || j == 0 || i == G - 1 || j == G - 1;
+    if (!blk) {  // the four edge neighbours lie inside the grid
+      const int d[4] = {-G, G, -1, 1};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int t2 = top[a + d[k]];
+        const bool ok = near[a + d[k]] >= min_pts && ((t2 ^ t) & (NL - 1)) == 0 && abs((t2 >> 7) - (t >> 7)) <= step_mm;
+        blk = blk || !ok;
+      }
+    }
+    s[i][jj] = blk ? 0x8000u : 0u;
+  }
+  known = wave_sum(known);
+  solid = wave_sum(solid);
+  if (lane == 0) {
+    atomicAdd(&s_cnt[0], known);
+    atomicAdd(&s_cnt[1], solid);
+  }
+  __syncthreads();
+  if (tid < 2 && s_cnt[tid]) atomicAdd(&info[(size_t)b * 4 + 2 + tid], s_cnt[tid]);
+  if (blockIdx.x == 0 && tid == 2) info[(size_t)b * 4] = found ? 1 : 0;
+  const int jj = tid % STRIP, seg = tid / STRIP, rows = G / SEGS, r0 = seg * rows, r1 = r0 + rows;
+  const bool col = j0 + jj < G;
+  {  // the first and the last blocking row of the segment
+    int first = INT_MAX, last = -1;
+    if (col)
+      for (int i = r0; i < r1; ++i)
+        if (s[i][jj] & 0x8000u) {
+          if (first == INT_MAX) first = i;
+          last = i;
+        }
+    s_first[seg][jj] = first;
+    s_last[seg][jj] = last;
+  }
+  __syncthreads();
+  if (!col) return;
+  int up = -1, down = G;  // the virtual blocking cells
+  for (int k = seg - 1; k >= 0; --k)
+    if (s_last[k][jj] >= 0) {
+      up = s_last[k][jj];
+      break;
+    }
+  for (int k = seg + 1; k < SEGS; ++k)
+    if (s_first[k][jj] != INT_MAX) {
+      down = s_first[k][jj];
+      break;
+    }
+  for (int i = r0; i < r1; ++i) {  // distance up, at most 512: bits 0..9
+    const unsigned v = s[i][jj];
+    if (v & 0x8000u) up = i;
+    s[i][jj] = (unsigned short)((v & 0x8000u) | (unsigned)(i - up));
+  }
+  for (int i = r1 - 1; i >= r0; --i) {
+    const unsigned v = s[i][jj];
+    if (v & 0x8000u) down = i;
+    g_out[off + (size_t)i * G + j0 + jj] = min((int)(v & 0x7FFFu), down - i);
+  }
+}
+
+// ---- 4. the row pass, the per-id table and the queries -----------------------------------------------------------------
+struct Acc {
+  int *cells, *level, *emax;       // [B][128] each; emax holds elev + KEY_BIAS, 0: none
+  unsigned long long *key, *sum;   // [B][128] each; sum is an int64 in two's complement
+  unsigned long long *qkey;        // [B][MAX_Q]
+};
+
+__global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict__ elev, const int *__restrict__ owner,
+                                                          const int *__restrict__ near, int G, int min_pts, Queries qs, int Q,
+                                                          int *__restrict__ dist2, Acc acc) {
+  __shared__ __attribute__((aligned(16))) int s_g2[MAX_G];
+  __shared__ unsigned long long s_qkey[MAX_Q];
+  __shared__ int s_cells[NL], s_level[NL], s_emax[NL], s_sum[NL];  // a row's sum: at most 512 * 32767
+  __shared__ unsigned long long s_key[NL];
+  const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x, b = blockIdx.y;
+  const size_t off = ((size_t)b * G + i) * G;
+  for (int j = tid; j < G; j += ROW_THREADS) {
+    const int g = dist2[off + j];
+    s_g2[j] = g * g;
+  }
+  if (tid < MAX_Q) s_qkey[tid] = 0ull;
+  if (tid < NL) {
+    s_cells[tid] = s_level[tid] = s_emax[tid] = s_sum[tid] = 0;
+    s_key[tid] = 0ull;
+  }
+  __syncthreads();
+  unsigned long long qkey[MAX_Q];
+#pragma unroll
+  for (int q = 0; q < MAX_Q; ++q) qkey[q] = 0ull;
+  for (int jb = 0; jb < G; jb += ROW_THREADS) {  // uniform: every lane takes part in the ballots and shuffles below
+    const int j = jb + tid;
+    const bool valid = j < G;
+    int best = 0, code = -1, el = 0;
+    if (valid) {
+      best = min((j + 1) * (j + 1), (G - j) * (G - j));  // the virtual columns -1 and G
+      for (int k = 0; k < G; k += 4) {                   // G is a multiple of 8
+        const int4 v = *reinterpret_cast<const int4 *>(&s_g2[k]);
+        const int d = j - k;
+        best = min(best, d * d + v.x);
+        best = min(best, (d - 1) * (d - 1) + v.y);
+        best = min(best, (d - 2) * (d - 2) + v.z);
+        best = min(best, (d - 3) * (d - 3) + v.w);
+      }
+      dist2[off + j] = best;
+      if (near[off + j] >= min_pts) {  // solid
+        code = owner[off + j];
+        el = elev[off + j];
+      }
+    }
+    const bool lvl = code >= 0 && best > 0;  // not blocking: level
+    const unsigned long long wide = lvl ? (((unsigned long long)(best + 1) << 18) | (unsigned long long)(IDX_MASK - (i * G + j))) : 0ull;
+    const int own = code;
+    unsigned long long rem = __ballot(code >= 0);
+    while (rem) {  // per distinct owner of the wave
+      const int first = __ffsll((long long)rem) - 1;
+      const int c = __builtin_amdgcn_readlane(code, first);
+      const bool hit = code == c;
+      const unsigned long long m = __ballot(hit), ml = __ballot(hit && lvl);
+      rem &= ~m;
+      if (hit) code = -1;
+      const int em = wave_max(hit ? el + KEY_BIAS : 0);
+      unsigned long long k64 = 0ull;
+      int sm = 0;
+      if (ml) {  // uniform
+        k64 = wave_max64(hit ? wide : 0ull);
+        sm = wave_sum(hit && lvl ? el : 0);
+      }
+      if (lane == first) {
+        atomicAdd(&s_cells[c], __popcll(m));
+        atomicMax(&s_emax[c], em);
+        if (ml) {
+          atomicAdd(&s_level[c], __popcll(ml));
+          atomicMax(&s_key[c], k64);
+          atomicAdd(&s_sum[c], sm);
+        }
+      }
+    }
+    if (Q > 0 && lvl) {
+#pragma unroll
+      for (int q = 0; q < MAX_Q; ++q) {
+        if (q < Q) {  // uniform
+          const int id = qs.v[q][1];
+          const bool cand = el >= qs.v[q][2] && el <= qs.v[q][3] && (id < 0 ? own >= 1 : own == id);
+          qkey[q] = max(qkey[q], cand ? wide : 0ull);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < MAX_Q; ++q) {
+    if (q < Q) {  // uniform
+      const unsigned long long k64 = wave_max64(qkey[q]);
+      if (lane == 0 && k64) atomicMax(&s_qkey[q], k64);
+    }
+  }
+  __syncthreads();
+  if (tid < Q && s_qkey[tid]) atomicMax(&acc.qkey[(size_t)b * MAX_Q + tid], s_qkey[tid]);
+  if (tid < NL && s_cells[tid]) {
+    const size_t a = (size_t)b * NL + tid;
+    atomicAdd(&acc.cells[a], s_cells[tid]);
+    atomicMax(&acc.emax[a], s_emax[tid]);
+    if (s_level[tid]) {
+      atomicAdd(&acc.level[a], s_level[tid]);
+      atomicMax(&acc.key[a], s_key[tid]);
+      atomicAdd(&acc.sum[a], (unsigned long long)(long long)s_sum[tid]);
+    }
+  }
+}
+
+// ---- 5. the rows of tops and the answers -------------------------------------------------------------------------------
+__global__ __launch_bounds__(NL) void answer_kernel(Acc acc, const int *__restrict__ elev, int G, Queries qs, int Q,
+                                                    int *__restrict__ tops, int *__restrict__ answers) {
+  const int a = threadIdx.x, b = blockIdx.x;
+  const size_t r = (size_t)b * NL + a;
+  const int cells = acc.cells[r], level = acc.level[r];
+  int row[8] = {cells, level, -1, -1, 0, 0, cells ? acc.emax[r] - KEY_BIAS : 0, 0};
+  if (level) {
+    const unsigned long long k64 = acc.key[r];
+    const int idx = IDX_MASK - (int)(k64 & (unsigned long long)IDX_MASK);
+    row[2] = idx / G;
+    row[3] = idx % G;
+    row[4] = (int)(k64 >> 18) - 1;
+    row[5] = elev[(size_t)b * G * G + idx];
+    row[7] = (int)floor_div((long long)acc.sum[r], level);
+  }
+  int *T = tops + r * 8;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) T[k] = row[k];
+  if (a < Q) {
+    const unsigned long long k64 = acc.qkey[(size_t)b * MAX_Q + a];
+    int4 ans = make_int4(-1, -1, 0, 0);
+    if (k64) {
+      const int idx = IDX_MASK - (int)(k64 & (unsigned long long)IDX_MASK);
+      ans.x = idx / G;
+      ans.y = idx % G;
+      ans.z = (int)(k64 >> 18) - 1;
+      ans.w = ans.z >= qs.v[a][0];
+    }
+    int *A = answers + ((size_t)b * Q + a) * 4;
+    A[0] = ans.x;
+    A[1] = ans.y;
+    A[2] = ans.z;
+    A[3] = ans.w;
+  }
+}
+
+bool shape_ok(int B, int H, int W, int G) {
+  return B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX && G >= 8 && G <= MAX_G && G % 8 == 0;
+}
+
+struct Ws {
+  int *top;  // [B][G][G]
+  Acc acc;
+  size_t total;
+};
+Ws carve(void *base, int B, int G) {
+  Ws w;
+  char *p = (char *)base;
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char *q = p ? p + at : nullptr;
+    at += align_up(bytes, 256);
+    return q;
+  };
+  w.top = (int *)take((size_t)B * G * G * sizeof(int));
+  w.acc.cells = (int *)take((size_t)B * NL * sizeof(int));
+  w.acc.level = (int *)take((size_t)B * NL * sizeof(int));
+  w.acc.emax = (int *)take((size_t)B * NL * sizeof(int));
+  w.acc.key = (unsigned long long *)take((size_t)B * NL * sizeof(unsigned long long));
+  w.acc.sum = (unsigned long long *)take((size_t)B * NL * sizeof(unsigned long long));
+  w.acc.qkey = (unsigned long long *)take((size_t)B * MAX_Q * sizeof(unsigned long long));
+  w.total = at;
+  return w;
+}
+
+template <int PASS>
+void launch_points(bool vec, dim3 grid, hipStream_t st, const int32_t *labels, const float *xyz, const long long *frame,
+                   long long n, int G, int cell_div, int t_low, int step_mm, int *top, int *pts, int *near, int *info) {
+  if (vec)
+    hipLaunchKernelGGL((point_kernel<true, PASS>), grid, dim3(256), 0, st, labels, xyz, frame, n, G, cell_div, t_low, step_mm, top,
+                       pts, near, info);
+  else
+    hipLaunchKernelGGL((point_kernel<false, PASS>), grid, dim3(256), 0, st, labels, xyz, frame, n, G, cell_div, t_low, step_mm, top,
+                       pts, near, info);
+}
+
+}  // namespace
+}  // namespace uoc
+
+using namespace uoc;
+
+extern "C" {
+
+size_t uoc_elevation_workspace_bytes(int B, int H, int W, int G) {
+  if (!shape_ok(B, H, W, G)) return 0;
+  return carve(nullptr, B, G).total;
+}
+
+int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_frame, int B, int H, int W, int G, int cell_mm,
+                  int tau_mm, int step_mm, int min_pts, const int32_t *h_queries, int Q, int32_t *d_elev, int32_t *d_owner,
+                  int32_t *d_pts, int32_t *d_near, int32_t *d_dist2, int32_t *d_tops, int32_t *d_info, int32_t *d_answers,
+                  void *d_ws, size_t ws_bytes, void *stream) {
+  UOC_REQUIRE(d_labels && d_xyz && d_frame && d_elev && d_owner && d_pts && d_near && d_dist2 && d_tops && d_info && d_ws,
+              "uoc_elevation: null labels / xyz / frame / elev / owner / pts / near / dist2 / tops / info / workspace");
+  UOC_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX,
+              "uoc_elevation: bad shape B=%d H=%d W=%d (B in 1..65535, H*W below 2^31)", B, H, W);
+  UOC_REQUIRE(G >= 8 && G <= MAX_G && G % 8 == 0, "uoc_elevation: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
+  UOC_REQUIRE(cell_mm >= 1 && cell_mm <= 1000, "uoc_elevation: cell_mm = %d outside [1, 1000]", cell_mm);
+  UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_elevation: tau_mm = %d outside [1, 1000]", tau_mm);
+  UOC_REQUIRE(step_mm >= 1 && step_mm <= 1000, "uoc_elevation: step_mm = %d outside [1, 1000]", step_mm);
+  UOC_REQUIRE(min_pts >= 1 && min_pts <= 65535, "uoc_elevation: min_pts = %d outside [1, 65535]", min_pts);
+  UOC_REQUIRE(Q >= 0 && Q <= MAX_Q, "uoc_elevation: %d queries outside [0, %d]", Q, MAX_Q);
+  UOC_REQUIRE(Q == 0 || (h_queries && d_answers), "uoc_elevation: null queries / answers with Q = %d", Q);
+  Queries qs;
+  for (int q = 0; q < MAX_Q; ++q)
+    for (int k = 0; k < 4; ++k) qs.v[q][k] = q < Q ? h_queries[q * 4 + k] : 0;
+  for (int q = 0; q < Q; ++q) {
+    UOC_REQUIRE(qs.v[q][0] >= 0 && qs.v[q][0] <= (1 << 30), "uoc_elevation: query %d: need2 = %d outside [0, 2^30]", q, qs.v[q][0]);
+    UOC_REQUIRE(qs.v[q][1] >= -1 && qs.v[q][1] < NL, "uoc_elevation: query %d: id = %d outside [-1, 127]", q, qs.v[q][1]);
+    UOC_REQUIRE(qs.v[q][2] >= -32768 && qs.v[q][2] <= 32767 && qs.v[q][3] >= -32768 && qs.v[q][3] <= 32767,
+                "uoc_elevation: query %d: band (%d, %d) outside [-32768, 32767]", q, qs.v[q][2], qs.v[q][3]);
+  }
+  const Ws w = carve(d_ws, B, G);
+  UOC_REQUIRE(ws_bytes >= w.total, "uoc_elevation: workspace %zu < %zu bytes", ws_bytes, w.total);
+  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_elevation: workspace not 16-byte aligned");
+  const long long n = (long long)H * W;
+  const int nch = (int)((n + CHUNK - 1) / CHUNK);
+  const size_t cells = (size_t)B * G * G;
+  const bool vec = n % 4 == 0 && (((uintptr_t)d_labels | (uintptr_t)d_xyz) & 15) == 0;
+  const long long *frame = (const long long *)d_frame;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof(KC_ELEV_RASTER, st, 0.0, (double)B * n * 32.0 + (double)cells * 24.0);
+    UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.total, st));
+    UOC_HIP_CHECK(hipMemsetAsync(d_pts, 0, cells * sizeof(int32_t), st));
+    UOC_HIP_CHECK(hipMemsetAsync(d_near, 0, cells * sizeof(int32_t), st));
+    UOC_HIP_CHECK(hipMemsetAsync(d_info, 0, (size_t)B * 4 * sizeof(int32_t), st));
+    launch_points<1>(vec, dim3(nch, B), st, d_labels, d_xyz, frame, n, G, cell_mm * SCALE, -tau_mm * SCALE, step_mm, w.top, d_pts,
+                     d_near, d_info);
+    launch_points<2>(vec, dim3(nch, B), st, d_labels, d_xyz, frame, n, G, cell_mm * SCALE, -tau_mm * SCALE, step_mm, w.top, d_pts,
+                     d_near, d_info);
+  }
+  {
+    ProfScope prof(KC_ELEV_TRANSFORM, st, (double)cells * G * 3.0, (double)cells * 52.0);
+    hipLaunchKernelGGL(cell_kernel, dim3((G + STRIP - 1) / STRIP, B), dim3(STRIP * SEGS), 0, st, w.top, d_pts, d_near, frame, G,
+                       step_mm, min_pts, d_elev, d_owner, d_dist2, d_info);
+    hipLaunchKernelGGL(row_kernel, dim3(G, B), dim3(ROW_THREADS), 0, st, d_elev, d_owner, d_near, G, min_pts, qs, Q, d_dist2, w.acc);
+    hipLaunchKernelGGL(answer_kernel, dim3(B), dim3(NL), 0, st, w.acc, d_elev, G, qs, Q, d_tops, d_answers);
+  }
+  UOC_LAUNCH_CHECK();
+  return UOC_OK;
+}
+
+}  // extern "C"

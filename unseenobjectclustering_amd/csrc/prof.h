@@ -42,6 +42,8 @@ enum KernelClass {
   KC_PLACE_TRANSFORM,  // cells, the distance transform and the queries
   KC_GRASP_MOMENTS,     // grasp candidates: the memset and the per-id moments
   KC_GRASP_CANDIDATES,  // the class table, the candidates and the best record
+  KC_ELEV_RASTER,     // elevation map: memsets and the two point passes (top, near)
+  KC_ELEV_TRANSFORM,  // cells, level, the distance transform, the per-id table and the queries
   KC_COUNT
 };
 

@@ -21,7 +21,8 @@ static const char *kNames[KC_COUNT] = {
     "plane_candidates",  "plane_hypotheses", "plane_score",      "plane_refine",    "plane_objects",
     "relations_pairs",   "relations_derive",
     "placement_raster",  "placement_transform",
-    "grasp_moments",     "grasp_candidates"};
+    "grasp_moments",     "grasp_candidates",
+    "elevation_raster",  "elevation_transform"};
 
 struct Rec {
   int kc;

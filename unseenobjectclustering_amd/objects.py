@@ -149,7 +149,8 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
 
 
 def segment_objects(sample, network, network_crop, use_refined=True, plane=False, plane_args=None, relations=False,
-                    relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, **kw):
+                    relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, elevation=False,
+                    elevation_args=None, **kw):
     """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
     refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
     maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
@@ -159,7 +160,8 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     come as a further item after it.  placement=True implies plane=True and adds, as the last item, the free space on
     that plane (placement.free_space, placement_args = its keyword arguments).  grasp=True implies placement=True and
     adds, after it, the grasp candidates of the objects on that grid (grasp.candidates, grasp_args = its keyword
-    arguments)."""
+    arguments).  elevation=True implies placement=True and adds, as the last item, the elevation map on that grid
+    (elevation.heights, elevation_args = its keyword arguments)."""
     from . import io as uio
     from .fcn import test_dataset as TD
     dev = TD._device()
@@ -171,7 +173,7 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     xyz = sample["depth"].to(dev)
     src, src_xyz = (refined[:1], xyz[:1]) if use_refined and refined is not None else (labels, xyz)
     objs = extract_objects(src, src_xyz, **kw)
-    placement = placement or grasp
+    placement = placement or grasp or elevation
     plane = plane or placement
     if plane:
         from .support import fit_plane
@@ -185,7 +187,10 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     if grasp:
         from .grasp import candidates
         grasped = candidates(placed, **(grasp_args or {}))
+    if elevation:
+        from .elevation import heights
+        raised = heights(src, src_xyz, placed, **(elevation_args or {}))
     out_label = labels.float().cpu()
     out_refined = refined.float().cpu() if refined is not None else None
     return (out_label, out_refined, objs) + ((fitted,) if plane else ()) + ((related,) if relations else ()) \
-        + ((placed,) if placement else ()) + ((grasped,) if grasp else ())
+        + ((placed,) if placement else ()) + ((grasped,) if grasp else ()) + ((raised,) if elevation else ())
