@@ -669,6 +669,60 @@ int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_
 
 
 /* ------------------------------------------------------------------------------------------
+ * Footprint fitting: oriented put-down poses on the table grid (no reference counterpart).
+ * d_state, d_owner, d_dist2 [B][G][G] int32 as uoc_placement writes them, cell index i*G + j, G a multiple of 8 in
+ * 8..512; d_frame [B][16] int64 as uoc_placement writes it, nullable.  For up to 8 rectangles and up to 32 orientations
+ * over half a turn: in which orientations the rectangle, centred on a cell, lies wholly on free cells.  Every output is
+ * an integer.
+ *
+ * D. Directions: exactly D of uoc_grasp.  S = 16384; h_dirs: a HOST array [A][2] int32 of directions (Cx_k, Cy_k), the
+ * rectangle's long axis, every component in [-S, S]; A in 1..32.  No kernel calls a trigonometric function.
+ * R. Rectangles.  h_rects: a HOST array [F][8] int32, F in 1..8, record f = (HL, HW, ignore, mode, ai, aj, 0, 0): HL, HW
+ * the half length and half width in units of 1/256 cell, each in 0..16384 with HL^2 + HW^2 <= 16384^2; ignore in 0..127
+ * (0: none); mode UOC_FOOT_ROOMIEST or UOC_FOOT_NEAREST; the anchor ai, aj in -4096..4095; words 6 and 7 are 0.  R_f is
+ * the smallest integer with (256 R_f)^2 >= HL^2 + HW^2, at most 64.
+ * K. Cells.  A cell whose state is outside 0..2, or whose state is 2 with an owner outside 1..127, counts as unknown
+ * (K of uoc_grasp).  Cell c is FREE for rectangle f when its state is 1; when it is unknown (state 0 included) and
+ * unknown_blocks == 0; or when its state is 2, ignore >= 1 and owner == ignore (the object being moved does not block
+ * itself).  A cell outside the grid is never FREE.
+ * M. Mask.  M(f,k) = the offsets (di, dj) with |di|, |dj| <= R_f + 1, |di Cx_k + dj Cy_k| <= 64 HL and
+ * |-di Cy_k + dj Cx_k| <= 64 HW: the cells whose centre lies inside the rectangle turned to direction k (64 = S/256;
+ * every product stays below 2^22).  (0,0) is in it, it is symmetric about the centre, and as the intersection of four
+ * half planes with the lattice every row di of it is one span dj_lo..dj_hi or empty.
+ * X. Fit.  d_fits [B][F][G][G] int32: bit k of fits[b][f][i][j] is set iff every cell (i+di, j+dj), (di, dj) in M(f,k),
+ * lies inside the grid and is FREE for f; bits A..31 are 0.  d_count [B][F][32] int32: count[b][f][k] = the cells with
+ * bit k; words A..31 are 0.
+ * B. Best.  d_best [B][F][8] int32 = (ok, i, j, k, dist2, da, poses, cells): poses = the set bits over the frame, cells =
+ * the cells with a non-zero word.  The winner over all set (cell, k) is the maximum of one 64-bit key, with
+ * d = min(max(dist2[cell], 0), 65536), idx = i*G + j, da = (i-ai)^2 + (j-aj)^2 (below 2^26):
+ *   UOC_FOOT_ROOMIEST  ((d + 1) << 23) | ((0x3FFFF - idx) << 5) | (31 - k)
+ *   UOC_FOOT_NEAREST   ((2^27 - 1 - da) << 23) | ((0x3FFFF - idx) << 5) | (31 - k)
+ * both strict total orders: ties to the lowest idx, then the lowest k.  Without a pose (0, -1, -1, -1, 0, 0, 0, 0); with
+ * one ok = 1, dist2 = d of the winning cell and da as above, in both modes.
+ * F. Frames.  With d_frame given, a frame whose word 13 is not 1 is a frame without a plane: all-zero fits and count, the
+ * no-pose best.  With d_frame == NULL every frame is evaluated as it stands.
+ * Every count is a sum of ones and every choice is over a strict total order: the result is defined exactly and does
+ * not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_FOOT_MAX_RECTS 8
+#define UOC_FOOT_MAX_HALF 16384
+#define UOC_FOOT_ROOMIEST 0
+#define UOC_FOOT_NEAREST 1
+
+/* 0 for a bad shape: B outside 1..65535, a bad G, A outside 1..32 or F outside 1..8. */
+size_t uoc_footprint_workspace_bytes(int B, int G, int A, int F);
+/* Ranges as in D and R above; unknown_blocks 0 or 1.  h_dirs and h_rects are read before the call returns and travel as
+ * kernel arguments (256 bytes each): no copy.  d_ws 16-byte aligned.  Returns UOC_EINVAL before any device work for null
+ * pointers other than d_frame, bad ranges, a workspace below uoc_footprint_workspace_bytes(B, G, A, F) or one that is not
+ * 16-byte aligned; uoc_last_error names the argument; a rejected call writes nothing, the workspace included.  Two
+ * memsets (the accumulators, d_count) and four launches on `stream`; no host read of device memory, nothing
+ * synchronises, no state is kept between calls. */
+int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t *d_dist2, const int64_t *d_frame, int B, int G,
+                  const int32_t *h_dirs, int A, const int32_t *h_rects, int F, int unknown_blocks, int32_t *d_fits,
+                  int32_t *d_count, int32_t *d_best, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

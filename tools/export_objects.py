@@ -11,6 +11,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--placement RADIUS_M [--grid 256] [--cell-mm 10]]
                                    [--grasp MAX_OPEN_M [--grasp-angles 16] [--grasp-offsets 2]]
                                    [--elevation STEP_M [--elevation-min-pts 2]]
+                                   [--putdown LENGTH_M WIDTH_M [--putdown-angles 16]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -61,6 +62,14 @@ level.  Per row `top_cells` and `top_level`, the object's solid and level cells;
 the most room ((-1, -1) without one), `top_clear_m`, the distance from there to the nearest cell that is not level,
 `top_height_m`, its height above the plane, and `top_xyz`, its centre lifted onto the top, camera coordinates (NaN
 without a level cell).  With --placement RADIUS_M also `top_fits`: whether a disc of RADIUS_M metres fits there.
+
+With --putdown LENGTH_M WIDTH_M the oriented put-down poses of a LENGTH_M x WIDTH_M rectangle (conservative: inflated by
+0.72 cell) are computed on the device (unseenobjectclustering_amd/footprint.py) on the --grid x --grid grid of the
+placement stage, which runs for it with its defaults whether or not --placement is given, over --putdown-angles
+orientations of half a turn: `putdown_fits` [G,G] int32, bit k set where the rectangle fits along direction k;
+`putdown_count` [32], the cells per direction; `putdown_best` = (ok, i, j, k, dist2, da, poses, cells), the roomiest
+pose; `putdown_center` and `putdown_axis`, that cell's centre and the rectangle's long axis in camera coordinates (NaN
+without a pose).  `putdown_dirs` is the direction table.
 """
 import argparse
 import glob
@@ -79,6 +88,7 @@ from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.elevation import heights, spot  # noqa: E402
+from unseenobjectclustering_amd import footprint  # noqa: E402
 from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
@@ -139,6 +149,18 @@ def elevation_arrays(raised, ids, radius=None):
     return rec
 
 
+PUTDOWN_KEYS = ("putdown_fits", "putdown_count", "putdown_best", "putdown_dirs", "putdown_center", "putdown_axis")
+
+
+def putdown_arrays(fitting):
+    """The --putdown arrays of one frame: rectangle 0 of frame 0 of `fitting` (a footprint.fit result) and its best pose."""
+    p = footprint.pose(fitting, 0, 0)
+    nan3 = np.full(3, np.nan)
+    return {"putdown_fits": fitting.fits[0, 0].cpu().numpy(), "putdown_count": fitting.count[0, 0].cpu().numpy(),
+            "putdown_best": fitting.best[0, 0].cpu().numpy(), "putdown_dirs": np.asarray(fitting.dirs, np.int32),
+            "putdown_center": np.asarray(p.center if p else nan3, np.float64), "putdown_axis": np.asarray(p.axis if p else nan3, np.float64)}
+
+
 RELATION_KEYS = ("layer", "free", "order", "n_above", "edge")
 
 
@@ -193,6 +215,9 @@ def build_parser():
     ap.add_argument("--elevation", type=float, default=None, metavar="STEP_M",
                     help="add the tops of the objects on the elevation map; cells climbing at most this far (metres) are level")
     ap.add_argument("--elevation-min-pts", type=int, default=2, help="with --elevation: points near a cell's top that make it solid")
+    ap.add_argument("--putdown", type=float, nargs=2, default=None, metavar=("LENGTH_M", "WIDTH_M"),
+                    help="add the oriented put-down poses of a rectangle of this length and width (metres) on the table grid")
+    ap.add_argument("--putdown-angles", type=int, default=16, help="with --putdown: orientations over half a turn (1..32)")
     return ap
 
 
@@ -243,7 +268,8 @@ def main():
                 ids = inverse[ids]
             rows = comp[ids].cpu().numpy()
             rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
-        if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None:
+        placed = None                       # the grid of --grasp / --elevation, where one of them computes it: --putdown reuses it
+        if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None or args.putdown is not None:
             fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
         if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
@@ -261,6 +287,12 @@ def main():
             raised = heights(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), placed,
                              step=args.elevation, min_pts=args.elevation_min_pts)
             rec.update(elevation_arrays(raised, objs.label.long().cpu().tolist(), args.placement))
+        if args.putdown is not None:
+            if placed is None:
+                placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
+                                    grid=args.grid, cell=args.cell_mm / 1000.0)
+            rec.update(putdown_arrays(footprint.fit(placed, [footprint.rect(args.putdown[0], args.putdown[1], args.cell_mm)],
+                                                    angles=args.putdown_angles)))
         if args.relations:
             related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
                              connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)

@@ -128,6 +128,10 @@ def _declare(lib):
     lib.uoc_elevation_workspace_bytes.restype = c_size_t
     lib.uoc_elevation.argtypes = [P, P, P] + [c_int] * 8 + [P, c_int] + [P] * 9 + [c_size_t, P]
     lib.uoc_elevation.restype = c_int
+    lib.uoc_footprint_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.uoc_footprint_workspace_bytes.restype = c_size_t
+    lib.uoc_footprint.argtypes = [P, P, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, c_size_t, P]
+    lib.uoc_footprint.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -168,7 +172,8 @@ EXPORTED_SYMBOLS = (
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
     "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
     "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
-    "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation",
+    "uoc_footprint_workspace_bytes", "uoc_footprint", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -230,6 +235,9 @@ GRASP_MAX_FINGER = 8                            # F in 1..8 cells
 GRASP_MAX_PAD = 4                               # Hp in 0..4 cells
 ELEV_NONE = -32768                              # include/uoc_hip.h: UOC_ELEV_NONE, the elev of a cell without a point
 ELEV_MAX_QUERIES = 16                           # UOC_ELEV_MAX_QUERIES
+FOOT_MAX_RECTS = 8                              # include/uoc_hip.h: UOC_FOOT_MAX_RECTS
+FOOT_MAX_HALF = 16384                           # UOC_FOOT_MAX_HALF: a half extent in 1/256 cell, and HL^2 + HW^2 <= its square
+FOOT_ROOMIEST, FOOT_NEAREST = 0, 1              # UOC_FOOT_*: a rectangle's mode
 
 
 class UocTrack(ctypes.Structure):

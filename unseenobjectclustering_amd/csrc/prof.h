@@ -44,6 +44,8 @@ enum KernelClass {
   KC_GRASP_CANDIDATES,  // the class table, the candidates and the best record
   KC_ELEV_RASTER,     // elevation map: memsets and the two point passes (top, near)
   KC_ELEV_TRANSFORM,  // cells, level, the distance transform, the per-id table and the queries
+  KC_FOOT_TABLES,  // footprint fitting: memsets, the mask spans and the runs of free cells
+  KC_FOOT_FIT,     // the fit words, the counts, the keys and the best records
   KC_COUNT
 };
 

@@ -22,7 +22,8 @@ static const char *kNames[KC_COUNT] = {
     "relations_pairs",   "relations_derive",
     "placement_raster",  "placement_transform",
     "grasp_moments",     "grasp_candidates",
-    "elevation_raster",  "elevation_transform"};
+    "elevation_raster",  "elevation_transform",
+    "footprint_tables",  "footprint_fit"};
 
 struct Rec {
   int kc;
