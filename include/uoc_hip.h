@@ -723,6 +723,62 @@ int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t 
 
 
 /* ------------------------------------------------------------------------------------------
+ * Routes: reachability and slide paths on the table grid (no reference counterpart).
+ * d_state, d_owner [B][G][G] int32 as uoc_placement writes them, cell index i*G + j, G a multiple of 8 in 8..512; d_frame
+ * [B][16] int64 as uoc_placement writes it, nullable.  dist2 is not an input: the stage derives clearance itself, so that
+ * an ignored object really is gone.  For up to 8 queries: can a disc get from a source cell to a target cell without
+ * being lifted over anything, at what cost, and along which cells.  Every output is an integer.
+ *
+ * Q. Queries.  h_queries: a HOST array [Q][8] int32, Q in 1..8, record q = (need2, si, sj, ti, tj, ignore, 0, 0): need2 in
+ * 0..4096 the squared radius, in cells, of the disc that travels (the need2 of a placement query); the source (si, sj) in
+ * [0, G); the target (ti, tj) in [0, G), or (-1, -1) for none; ignore in 0..127, the object being moved (0: none); words 6
+ * and 7 are 0.
+ * K. Cells.  A cell whose state is outside 0..2, or whose state is 2 with an owner outside 1..127, counts as unknown (K of
+ * uoc_grasp and uoc_footprint).  Cell c is FREE for query q when its state is 1; when it is unknown (state 0 included)
+ * and unknown_blocks == 0; or when its state is 2, ignore >= 1 and owner == ignore.  A cell outside the grid is never FREE.
+ * P. Passable.  Cell c is PASSABLE for q when c is FREE and every offset (di, dj) with di^2 + dj^2 < need2 lands inside the
+ * grid on a FREE cell.  need2 == 0 has no offset: PASSABLE = FREE.  Every row of the disc is one span.  With ignore == 0
+ * this is "c is not blocking and dist2[c] >= need2" of uoc_placement's step E.
+ * M. Moves.  Eight neighbours in this fixed order: (-1,0), (0,-1), (0,1), (1,0), (-1,-1), (-1,1), (1,-1), (1,1).  An
+ * orthogonal move costs 5, a diagonal move 7.  A move needs both ends PASSABLE; a diagonal move (di, dj) from (i, j) also
+ * needs (i+di, j) and (i, j+dj) PASSABLE (no corner cutting).  A cost is a chamfer length, not a Euclidean one: on an
+ * empty grid cost / 5 lies between 0.98995 and 1.07704 times the Euclidean distance in cells.
+ * C. Cost.  d_cost [B][Q][G][G] int32: the least total cost of moves from the source, 0 at the source; -1 where the cell is
+ * not PASSABLE or not reachable.  A source that is not PASSABLE: -1 everywhere.  cost <= 7 G^2 < 2^21.
+ * A. Closest approach.  With a target, over the reached cells (cost >= 0), the maximum of the 64-bit key
+ *   ((2^19 - 1 - da) << 39) | ((2^21 - 1 - cost) << 18) | (0x3FFFF - idx),  da = (i-ti)^2 + (j-tj)^2 < 2^19, idx = i*G + j:
+ * nearest to the target, then cheapest, then the lowest index; a strict total order.  A reached target wins with da = 0.
+ * W. Path.  d_path [B][Q][P][2] int32, P = max_path in 1..4096.  From the closest-approach cell c, step to the first
+ * neighbour n in M's order for which the move n -> c is allowed and cost[n] + w == cost[c], until the source.  path[0] is
+ * the closest-approach cell; entries up to min(steps, P-1) are written, the rest are (-1, -1); steps is the full number
+ * of moves even when the path is cut short.
+ * I. d_info [B][Q][8] int32 = (src_ok, ok, ci, cj, cost, steps, reached, passable): src_ok = the source is PASSABLE; ok =
+ * the target is given and reached; (ci, cj, cost) the closest-approach cell and its cost; reached and passable count
+ * cells.  Without a target, or with src_ok == 0: (src_ok, 0, -1, -1, 0, 0, reached, passable) and a path of (-1, -1).
+ * F. Frames.  With d_frame given, a frame whose word 13 is not 1 is a frame without a plane: cost all -1, every info
+ * record (0, 0, -1, -1, 0, 0, 0, 0), paths all (-1, -1).  With d_frame == NULL every frame is evaluated as it stands.
+ * The cost field is the unique fixpoint of integer relaxations, the key is a strict total order and the walk back follows
+ * a fixed order: the result is defined exactly and does not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_ROUTES_MAX_QUERIES 8
+#define UOC_ROUTES_MAX_NEED2 4096
+#define UOC_ROUTES_MAX_PATH 4096
+
+/* 0 for a bad shape: B outside 1..65535, a bad G or Q outside 1..8. */
+size_t uoc_routes_workspace_bytes(int B, int G, int Q);
+/* Ranges as in Q above; unknown_blocks 0 or 1; max_path in 1..4096.  h_queries is read before the call returns and travels
+ * as a kernel argument: no copy.  d_ws 16-byte aligned.  Returns UOC_EINVAL before any device work for null pointers other
+ * than d_frame, bad ranges, non-zero words 6 or 7, a bad shape, a workspace below uoc_routes_workspace_bytes(B, G, Q) or
+ * one that is not 16-byte aligned; uoc_last_error names the argument; a rejected call writes nothing, the workspace
+ * included.  One memset and three launches on `stream`; no host read of device memory, nothing synchronises, no state is
+ * kept between calls.  After the call the first B*Q int32 words of the workspace hold the relaxation sweeps each (frame,
+ * query) took: a diagnostic for measurements, not a result. */
+int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_frame, int B, int G, const int32_t *h_queries,
+               int Q, int unknown_blocks, int max_path, int32_t *d_cost, int32_t *d_info, int32_t *d_path, void *d_ws,
+               size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

@@ -70,6 +70,13 @@ orientations of half a turn: `putdown_fits` [G,G] int32, bit k set where the rec
 `putdown_count` [32], the cells per direction; `putdown_best` = (ok, i, j, k, dist2, da, poses, cells), the roomiest
 pose; `putdown_center` and `putdown_axis`, that cell's centre and the rectangle's long axis in camera coordinates (NaN
 without a pose).  `putdown_dirs` is the direction table.
+
+With --route ID RADIUS_M (which needs --placement) the way of object ID, as a disc of RADIUS_M metres that its own cells do
+not block, from the cell of its centre to the widest spot --placement found is computed on the device
+(unseenobjectclustering_amd/routes.py): `route_cost` [G,G] int32, the least cost of sliding there from the source (5 per
+orthogonal, 7 per diagonal move, -1: not reachable); `route_info` = (src_ok, ok, ci, cj, cost, steps, reached, passable);
+`route_path` [n,2] int32, the cells from the source to the goal (empty without a path); `route_xyz` [n,3], their centres
+in camera coordinates, and `route_length_m` (NaN without a path).
 """
 import argparse
 import glob
@@ -89,6 +96,7 @@ from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mo
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.elevation import heights, spot  # noqa: E402
 from unseenobjectclustering_amd import footprint  # noqa: E402
+from unseenobjectclustering_amd import routes  # noqa: E402
 from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
@@ -161,6 +169,19 @@ def putdown_arrays(fitting):
             "putdown_center": np.asarray(p.center if p else nan3, np.float64), "putdown_axis": np.asarray(p.axis if p else nan3, np.float64)}
 
 
+ROUTE_KEYS = ("route_cost", "route_info", "route_path", "route_xyz", "route_length_m")
+
+
+def route_arrays(routed):
+    """The --route arrays of one frame: query 0 of frame 0 of `routed` (a routes.plan result)."""
+    w = routes.waypoints(routed, 0, 0)
+    length = routes.length_m(routed, 0, 0)
+    return {"route_cost": routed.cost[0, 0].cpu().numpy(), "route_info": routed.info[0, 0].cpu().numpy(),
+            "route_path": w.cells.astype(np.int32) if w else np.zeros((0, 2), np.int32),
+            "route_xyz": routes.path_to_camera(routed, 0, 0) if w else np.zeros((0, 3), np.float64),
+            "route_length_m": np.float64(np.nan if length is None else length)}
+
+
 RELATION_KEYS = ("layer", "free", "order", "n_above", "edge")
 
 
@@ -172,10 +193,13 @@ def relation_arrays(related, ids):
     return rec
 
 
-def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm):
-    """The --placement arrays of one frame: the grid maps and the widest spot for a disc of `radius` metres."""
+def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm, keep=None):
+    """The --placement arrays of one frame: the grid maps and the widest spot for a disc of `radius` metres.  keep: a list
+    that receives the placement result (--route goes on from it)."""
     cell = cell_mm / 1000.0
     placed = free_space(labels, xyz, fitted, grid=grid, cell=cell, queries=[(need2(radius, cell), 0, 0, WIDEST)])
+    if keep is not None:
+        keep.append(placed)
     ans = placed.answers[0, 0].cpu().numpy()
     spot = cell_to_camera(placed, 0, ans[0], ans[1]) if ans[0] >= 0 else np.full(3, np.nan)
     return {"place_state": placed.state[0].cpu().numpy(), "place_dist2": placed.dist2[0].cpu().numpy(),
@@ -218,11 +242,28 @@ def build_parser():
     ap.add_argument("--putdown", type=float, nargs=2, default=None, metavar=("LENGTH_M", "WIDTH_M"),
                     help="add the oriented put-down poses of a rectangle of this length and width (metres) on the table grid")
     ap.add_argument("--putdown-angles", type=int, default=16, help="with --putdown: orientations over half a turn (1..32)")
+    ap.add_argument("--route", nargs=2, default=None, metavar=("ID", "RADIUS_M"),
+                    help="with --placement: add the slide path of object ID, as a disc of this radius (metres), to the widest spot")
     return ap
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.route is not None:
+        if args.placement is None:
+            ap.error("--route needs --placement (it routes to the spot that --placement finds)")
+        try:
+            args.route = (int(args.route[0]), float(args.route[1]))
+        except ValueError:
+            ap.error("--route ID RADIUS_M: an integer id and a radius in metres")
+        if not 1 <= args.route[0] <= 127 or args.route[1] < 0:
+            ap.error("--route ID RADIUS_M: ID in 1..127, RADIUS_M not negative")
+    return args
+
+
 def main():
-    args = build_parser().parse_args()
+    args = parse_args()
     if args.cfg_file is not None:
         cfg_from_file(args.cfg_file)
     if network_mode() != "RGBD_ADD":
@@ -274,8 +315,14 @@ def main():
         if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
         if args.placement is not None:
+            kept = []
             rec.update(placement_arrays(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
-                                        fitted, args.placement, args.grid, args.cell_mm))
+                                        fitted, args.placement, args.grid, args.cell_mm, keep=kept))
+            if args.route is not None:
+                spot = rec["place_widest_cell"]
+                query = routes.of_object(kept[0], fitted, 0, args.route[0], (int(spot[0]), int(spot[1])) if spot[0] >= 0 else None,
+                                         radius_m=args.route[1])
+                rec.update(route_arrays(routes.plan(kept[0], [query])))
         if args.grasp is not None:
             placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
                                 grid=args.grid, cell=args.cell_mm / 1000.0)

@@ -46,6 +46,8 @@ enum KernelClass {
   KC_ELEV_TRANSFORM,  // cells, level, the distance transform, the per-id table and the queries
   KC_FOOT_TABLES,  // footprint fitting: memsets, the mask spans and the runs of free cells
   KC_FOOT_FIT,     // the fit words, the counts, the keys and the best records
+  KC_ROUTES_TABLES,  // routes: the memset, the runs of free cells and the passable maps
+  KC_ROUTES_SOLVE,   // the cost fields, the closest approach and the paths
   KC_COUNT
 };
 

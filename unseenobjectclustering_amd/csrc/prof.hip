@@ -23,7 +23,8 @@ static const char *kNames[KC_COUNT] = {
     "placement_raster",  "placement_transform",
     "grasp_moments",     "grasp_candidates",
     "elevation_raster",  "elevation_transform",
-    "footprint_tables",  "footprint_fit"};
+    "footprint_tables",  "footprint_fit",
+    "routes_tables",     "routes_solve"};
 
 struct Rec {
   int kc;

@@ -150,7 +150,7 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
 
 def segment_objects(sample, network, network_crop, use_refined=True, plane=False, plane_args=None, relations=False,
                     relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, elevation=False,
-                    elevation_args=None, footprint=False, footprint_args=None, **kw):
+                    elevation_args=None, footprint=False, footprint_args=None, routes=False, routes_args=None, **kw):
     """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
     refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
     maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
@@ -163,9 +163,13 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     arguments).  elevation=True implies placement=True and adds, as the last item, the elevation map on that grid
     (elevation.heights, elevation_args = its keyword arguments).  footprint=True implies placement=True and adds, after
     the elevation item, the oriented put-down poses of the rectangles footprint_args["rects"] on that grid
-    (footprint.fit, footprint_args = its keyword arguments, `rects` among them)."""
+    (footprint.fit, footprint_args = its keyword arguments, `rects` among them).  routes=True implies placement=True and
+    adds, as the last item, the slide paths of the queries routes_args["queries"] on that grid (routes.plan, routes_args =
+    its keyword arguments, `queries` among them)."""
     if footprint and "rects" not in (footprint_args or {}):
         raise ValueError("segment_objects: footprint=True needs footprint_args with `rects`")
+    if routes and "queries" not in (routes_args or {}):
+        raise ValueError("segment_objects: routes=True needs routes_args with `queries`")
     from . import io as uio
     from .fcn import test_dataset as TD
     dev = TD._device()
@@ -177,7 +181,7 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     xyz = sample["depth"].to(dev)
     src, src_xyz = (refined[:1], xyz[:1]) if use_refined and refined is not None else (labels, xyz)
     objs = extract_objects(src, src_xyz, **kw)
-    placement = placement or grasp or elevation or footprint
+    placement = placement or grasp or elevation or footprint or routes
     plane = plane or placement
     if plane:
         from .support import fit_plane
@@ -197,8 +201,11 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     if footprint:
         from .footprint import fit
         fitting = fit(placed, **footprint_args)
+    if routes:
+        from .routes import plan
+        routed = plan(placed, **routes_args)
     out_label = labels.float().cpu()
     out_refined = refined.float().cpu() if refined is not None else None
     return (out_label, out_refined, objs) + ((fitted,) if plane else ()) + ((related,) if relations else ()) \
         + ((placed,) if placement else ()) + ((grasped,) if grasp else ()) + ((raised,) if elevation else ()) \
-        + ((fitting,) if footprint else ())
+        + ((fitting,) if footprint else ()) + ((routed,) if routes else ())
