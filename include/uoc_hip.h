@@ -779,6 +779,66 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
 
 
 /* ------------------------------------------------------------------------------------------
+ * Label confidence: assignment margins per pixel and per object (no reference counterpart).
+ * The nearest-seed assignment (uoc_ms_assign) picks per pixel the seed of smallest cosine distance; how far the nearest
+ * seed of ANOTHER seed component lies behind it is how close the pixel came to carrying another label.
+ *
+ * M. uoc_ms_confidence.  Layouts of uoc_ms_assign / uoc_ms_cluster_wide: d_X [batch][halves][n][64], d_Z
+ * [batch][halves][m][64], d_seed_labels [batch][m], d_num_unique [batch]; halves 1 or 2, 1 <= m <= 128, 1 <= n <= 2^30.
+ * Per pixel p, with S(p, s) the fp32 MFMA dot product of uoc_ms_assign (same staging, same order):
+ *   d(p, s)  = 0.5f * (1.0f - S(p, s))
+ *   best(p)  = argmin_s d, ties to the lowest s;  c1 = seed_labels[best]
+ *   rival(p) = argmin of d over the seeds with seed_labels[s] != c1, ties to the lowest s; -1 when every seed carries c1
+ *   margin(p) = d(p, rival) - d(p, best) in fp32, >= 0 by construction; 1.0f without a rival (the largest value a
+ *               difference of cosine distances can take)
+ *   labels(p) = seed_labels[best] after the "largest cluster becomes label 0" swap of uoc_ms_assign (only labels in
+ *               range(num_unique) are counted, the first maximum wins, 0 and that label change places)
+ *   second(p) = the same swap applied to seed_labels[rival], or -1
+ *   closest(p) = best(p)
+ * d_labels [batch][n] int32 and d_margin [batch][n] float are required; d_second, d_closest, d_rival [batch][n] int32 are
+ * nullable.  d_labels and d_closest are bit-identical to what uoc_ms_assign writes for the same inputs, for finite rows of
+ * d_X and d_Z and seed labels in 0..127; outside that uoc_ms_assign indexes its tables out of range while this call
+ * writes label 0 for a pixel no seed wins (a NaN row; closest is then INT_MAX) and leaves labels outside 0..127 out of the
+ * histogram.  Minima over a fixed set with index tie-breaks: the result does not depend on launch order or batch.
+ * metric must be UOC_METRIC_COSINE; UOC_METRIC_EUCLIDEAN is not built (the square root near zero needs its own error
+ * analysis) and returns UOC_EINVAL saying so.
+ * Returns UOC_EINVAL before any device work for null required pointers, bad ranges, d_X or d_Z not 16-byte aligned, a
+ * workspace below uoc_ms_confidence_workspace_bytes or not 16-byte aligned, an output that overlaps an input (d_labels
+ * aliasing d_X, ...) or another output; uoc_last_error names the argument; a rejected call writes nothing.  One memset
+ * and two or three launches on `stream`; no host read of device memory, nothing synchronises, no state is kept between
+ * calls.
+ *
+ * P. uoc_conf_paste carries crop-level values into the frame along the paint plan of uoc_roi_match.  d_values_crop
+ * [K][S*S] float; d_labels_crop [K][S*S] int32 and d_table as given to uoc_roi_match; d_plan [K + K*128] int32, the
+ * paint order followed by the id map, exactly as uoc_roi_match writes it; d_out [H*W] float.  A frame pixel gets the
+ * value of the crop pixel whose (mapped, non-zero) label uoc_roi_paste leaves there: the same nearest-resize source
+ * index, and a later ROI of the order overwrites an earlier one.  A pixel that nothing paints is LEFT UNTOUCHED: the
+ * caller pre-fills d_out.  K in 1..127, S in 1..4096, H*W in 1..2^30.  UOC_EINVAL before any device work for null
+ * pointers, bad ranges or a d_out [H*W] that overlaps d_values_crop, d_labels_crop, d_table or d_plan anywhere (the kernel
+ * reads them while it writes); uoc_last_error names the argument.  One launch.
+ *
+ * O. uoc_conf_objects summarises any (label map, value map) pair per id, in integers.  d_labels [B][H*W] int32, d_conf
+ * [B][H*W] float, weak_q in 0..65535.  Per pixel q = 0 when conf is NaN or negative, else min(65535, (int)(conf *
+ * 65536.0f)): the product is exact, the conversion truncates.  d_stats [B][128][4] int64 = (pixels, sum_q, min_q, weak)
+ * for label l in 0..127 (row 0: the background); labels outside 0..127 are ignored; weak counts the pixels with q <
+ * weak_q; min_q = 0 when pixels == 0.  Sums of integers and a minimum: defined exactly, independent of launch order and
+ * batch.  B in 1..65535, H*W in 1..2^30, d_stats 8-byte aligned.  UOC_EINVAL before any device work for null pointers or
+ * bad ranges.  One memset and two launches.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_CONF_MAX_N (1 << 30)
+
+/* 0 for a bad shape: batch outside 1..65535, n outside 1..2^30, m outside 1..128, halves not 1 or 2. */
+size_t uoc_ms_confidence_workspace_bytes(int batch, int n, int m, int halves);
+int uoc_ms_confidence(const float *d_X, int halves, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
+                      const int32_t *d_num_unique, int m, int metric, int32_t *d_labels, float *d_margin,
+                      int32_t *d_second, int32_t *d_closest, int32_t *d_rival, void *d_ws, size_t ws_bytes, void *stream);
+int uoc_conf_paste(const float *d_values_crop, const int32_t *d_labels_crop, const uoc_roi_table *d_table,
+                   const int32_t *d_plan, int K, int S, int H, int W, float *d_out, void *stream);
+int uoc_conf_objects(const int32_t *d_labels, const float *d_conf, int B, int H, int W, int weak_q, int64_t *d_stats,
+                     void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

@@ -12,6 +12,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--grasp MAX_OPEN_M [--grasp-angles 16] [--grasp-offsets 2]]
                                    [--elevation STEP_M [--elevation-min-pts 2]]
                                    [--putdown LENGTH_M WIDTH_M [--putdown-angles 16]]
+                                   [--confidence [WEAK]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -77,6 +78,13 @@ not block, from the cell of its centre to the widest spot --placement found is c
 orthogonal, 7 per diagonal move, -1: not reachable); `route_info` = (src_ok, ok, ci, cj, cost, steps, reached, passable);
 `route_path` [n,2] int32, the cells from the source to the goal (empty without a path); `route_xyz` [n,3], their centres
 in camera coordinates, and `route_length_m` (NaN without a path).
+
+With --confidence [WEAK] the frame goes through the segmentation with the assignment margins alongside
+(unseenobjectclustering_amd/confidence.py; the label maps are the same): `conf_map` [H,W] float32, per pixel how far the
+nearest seed of another cluster lay behind the one that gave the pixel its label (0: a coin toss; 0 also where the two
+stages disagree), and per row, over the pixels of the exported label map (the tracked or split one likewise),
+`conf_mean`, `conf_min` (float64, in steps of 1/65536) and `conf_weak_share`, the share of the object's pixels whose margin
+is below WEAK (default 0.02).  Cosine metric only: under the euclidean opt-in the tool stops with NotImplementedError.
 """
 import argparse
 import glob
@@ -94,6 +102,7 @@ from test_images import load_weights  # noqa: E402
 from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
+from unseenobjectclustering_amd.confidence import summarize  # noqa: E402
 from unseenobjectclustering_amd.elevation import heights, spot  # noqa: E402
 from unseenobjectclustering_amd import footprint  # noqa: E402
 from unseenobjectclustering_amd import routes  # noqa: E402
@@ -182,6 +191,17 @@ def route_arrays(routed):
             "route_length_m": np.float64(np.nan if length is None else length)}
 
 
+CONFIDENCE_KEYS = ("conf_map", "conf_mean", "conf_min", "conf_weak_share")
+
+
+def confidence_arrays(summary, ids, margin):
+    """The --confidence arrays of one frame: the margin map and, per exported object (ids = its labels), the rows of frame
+    0 of `summary` (a confidence.summarize result over the exported label map)."""
+    ids = [int(a) for a in ids]
+    return {"conf_map": margin.cpu().numpy().astype(np.float32), "conf_mean": np.asarray(summary.mean[0][ids], np.float64),
+            "conf_min": np.asarray(summary.min[0][ids], np.float64), "conf_weak_share": np.asarray(summary.weak_share[0][ids], np.float64)}
+
+
 RELATION_KEYS = ("layer", "free", "order", "n_above", "edge")
 
 
@@ -244,12 +264,16 @@ def build_parser():
     ap.add_argument("--putdown-angles", type=int, default=16, help="with --putdown: orientations over half a turn (1..32)")
     ap.add_argument("--route", nargs=2, default=None, metavar=("ID", "RADIUS_M"),
                     help="with --placement: add the slide path of object ID, as a disc of this radius (metres), to the widest spot")
+    ap.add_argument("--confidence", type=float, nargs="?", const=0.02, default=None, metavar="WEAK",
+                    help="add the assignment-margin map and per object its mean, minimum and the share of pixels below WEAK (0.02)")
     return ap
 
 
 def parse_args(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.confidence is not None and not 0.0 <= args.confidence <= 1.0:
+        ap.error("--confidence WEAK: a margin in 0..1")
     if args.route is not None:
         if args.placement is None:
             ap.error("--route needs --placement (it routes to the spot that --placement finds)")
@@ -282,7 +306,12 @@ def main():
     tracker = Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None
     for fc, fd in zip(colors, depths):
         sample = uio.read_sample(fc, fd, cam)
-        out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
+        conf = None
+        if args.confidence is not None:
+            out_label, out_refined, objs, conf = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points,
+                                                                 confidence=True, confidence_args=dict(weak=args.confidence))
+        else:
+            out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
         final = out_refined if out_refined is not None else out_label
         track_uid = raw_map = comp = None
         if args.components is not None:
@@ -344,6 +373,9 @@ def main():
             related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
                              connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)
             rec.update(relation_arrays(related, objs.label.long()))
+        if conf is not None:
+            summary = summarize(torch.from_numpy(rec["label_map"]).to(cfg.device), conf.margin, weak=args.confidence)
+            rec.update(confidence_arrays(summary, objs.label.long().cpu().tolist(), conf.margin))
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")

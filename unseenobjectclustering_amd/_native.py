@@ -136,6 +136,14 @@ def _declare(lib):
     lib.uoc_routes_workspace_bytes.restype = c_size_t
     lib.uoc_routes.argtypes = [P, P, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
     lib.uoc_routes.restype = c_int
+    lib.uoc_ms_confidence_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.uoc_ms_confidence_workspace_bytes.restype = c_size_t
+    lib.uoc_ms_confidence.argtypes = [P, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P, P, c_size_t, P]
+    lib.uoc_ms_confidence.restype = c_int
+    lib.uoc_conf_paste.argtypes = [P, P, P, P, c_int, c_int, c_int, c_int, P, P]
+    lib.uoc_conf_paste.restype = c_int
+    lib.uoc_conf_objects.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P]
+    lib.uoc_conf_objects.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -177,7 +185,8 @@ EXPORTED_SYMBOLS = (
     "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
     "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
     "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation",
-    "uoc_footprint_workspace_bytes", "uoc_footprint", "uoc_routes_workspace_bytes", "uoc_routes", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_footprint_workspace_bytes", "uoc_footprint", "uoc_routes_workspace_bytes", "uoc_routes",
+    "uoc_ms_confidence_workspace_bytes", "uoc_ms_confidence", "uoc_conf_paste", "uoc_conf_objects", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -245,6 +254,8 @@ FOOT_ROOMIEST, FOOT_NEAREST = 0, 1              # UOC_FOOT_*: a rectangle's mode
 ROUTES_MAX_QUERIES = 8                          # include/uoc_hip.h: UOC_ROUTES_MAX_QUERIES
 ROUTES_MAX_NEED2 = 4096                         # UOC_ROUTES_MAX_NEED2: a query's need2 in 0..4096
 ROUTES_MAX_PATH = 4096                          # UOC_ROUTES_MAX_PATH: max_path in 1..4096
+CONF_MAX_N = 1 << 30                            # include/uoc_hip.h: UOC_CONF_MAX_N, pixels per field / frame of the confidence calls
+CONF_ONE = 65536                                # the fixed-point unit of uoc_conf_objects' q
 
 
 class UocTrack(ctypes.Structure):

@@ -8,6 +8,7 @@
 //   connected_components     :41-76    -> seed_cc_kernel         (one wavefront, ballots)
 //   mean_shift_smart_init    :211-227  -> assign_kernel          (fp32 MFMA + row argmin + histogram)
 //                                         + relabel_swap_kernel  (largest cluster <-> label 0)
+//   (no counterpart)                   -> confidence_kernel      (the assignment + the runner-up component and its margin)
 //
 // Data layout: X is pixel-major [batch][n][64] fp32 (256 B per pixel), seeds Z [batch][m][64].
 // All reductions have a fixed order, so results are run-to-run deterministic.
@@ -1590,6 +1591,161 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
   if (tid < NLAB && hist[tid]) atomicAdd(&counts[tid], hist[tid]);
 }
 
+// -------------------------------------------------------------------------------------------
+// Label confidence: the assignment above plus, per pixel, the nearest seed of ANOTHER seed component (the rival) and the
+// margin d(p, rival) - d(p, best) (include/uoc_hip.h).  Cosine metric only.
+// Same staging, MFMA sequence and d = 0.5 (1 - S) as assign_kernel, so best / labels / the histogram are bit-identical
+// (for finite rows and seed labels in 0..127; see the guards at the stores).
+// Running state per pixel slot: the lexicographic minimum (d1, s1) over the seeds seen, its component c1, and the
+// lexicographic minimum (d2, s2) over the seen seeds of a component other than c1; (INFINITY, INT_MAX) = none.
+//   a seed (d, s, c) enters:  it beats (d1, s1)  -> the old best, the minimum over ALL seen seeds, is the minimum over those
+//                             outside c too: it becomes the rival if c != c1, and (d, s, c) the best;
+//                             otherwise it is a rival candidate if c != c1.
+//   two states A < B merge:   best = A's; B's seeds outside A.c1 are led by B's best if B.c1 != A.c1, else by B's rival.
+// Both are exact minima over a fixed set with index tie-breaks: the result does not depend on the merge order.
+// -------------------------------------------------------------------------------------------
+struct ConfState {
+  float d1, d2;
+  int s1, s2, c1;
+};
+__device__ __forceinline__ bool conf_less(float da, int sa, float db, int sb) { return da < db || (da == db && sa < sb); }
+__device__ __forceinline__ void conf_merge(ConfState &a, const ConfState &o) {
+  if (conf_less(o.d1, o.s1, a.d1, a.s1)) {
+    // the other side wins: this side's seeds outside o.c1 are led by its best (c1 differs) or its rival (c1 equal)
+    const bool same = a.c1 == o.c1;
+    const float rd = same ? a.d2 : a.d1;
+    const int rs = same ? a.s2 : a.s1;
+    const bool take = conf_less(rd, rs, o.d2, o.s2);
+    a.d2 = take ? rd : o.d2;
+    a.s2 = take ? rs : o.s2;
+    a.d1 = o.d1;
+    a.s1 = o.s1;
+    a.c1 = o.c1;
+  } else {
+    const bool same = a.c1 == o.c1;
+    const float rd = same ? o.d2 : o.d1;
+    const int rs = same ? o.s2 : o.s1;
+    if (conf_less(rd, rs, a.d2, a.s2)) {
+      a.d2 = rd;
+      a.s2 = rs;
+    }
+  }
+}
+template <int CTRL>
+__device__ __forceinline__ void conf_min_step(ConfState &a) {   // one UOC_MIN_STEP of assign_kernel on the wider state
+  ConfState o;
+  o.d1 = dpp_f<CTRL>(a.d1);
+  o.d2 = dpp_f<CTRL>(a.d2);
+  o.s1 = dpp_i<CTRL>(a.s1);
+  o.s2 = dpp_i<CTRL>(a.s2);
+  o.c1 = dpp_i<CTRL>(a.c1);
+  conf_merge(a, o);
+}
+
+template <int ST, int NH>
+__global__ __launch_bounds__(HC_THREADS) void confidence_kernel(const float *__restrict__ X, int n,
+                                                                const float *__restrict__ Z,
+                                                                const int *__restrict__ seed_labels, int m,
+                                                                int *__restrict__ labels, float *__restrict__ margin,
+                                                                int *__restrict__ second, int *__restrict__ closest,
+                                                                int *__restrict__ rival, int *__restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) float Zs[];  // [NH][ST * 16][ZP]
+  __shared__ int slab[NLAB];
+  __shared__ int hist[NLAB];
+  const int b = blockIdx.y;
+  X += (size_t)b * NH * n * C;
+  Z += (size_t)b * NH * m * C;
+  seed_labels += (size_t)b * m;
+  labels += (size_t)b * n;
+  margin += (size_t)b * n;
+  if (second) second += (size_t)b * n;
+  if (closest) closest += (size_t)b * n;
+  if (rival) rival += (size_t)b * n;
+  counts += (size_t)b * NLAB;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = lane & 15, q = lane >> 4;
+  lds_stage_seeds<ST, NH>(Z, m, tid, Zs);
+  if (tid < NLAB) {
+    slab[tid] = tid < m ? seed_labels[tid] : 0;
+    hist[tid] = 0;
+  }
+  __syncthreads();
+
+  const int ntile = (n + 15) >> 4;
+  for (int tile = blockIdx.x * (HC_THREADS / 64) + wave; tile < ntile; tile += gridDim.x * (HC_THREADS / 64)) {
+    const int pa = tile * 16 + t;
+    float4 xa[NH * 4];
+#pragma unroll
+    for (int v = 0; v < NH * 4; ++v)
+      xa[v] = (pa < n) ? *reinterpret_cast<const float4 *>(X + ((size_t)(v >> 2) * n + pa) * C + 16 * (v & 3) + 4 * q)
+                       : make_float4(0.f, 0.f, 0.f, 0.f);
+    ConfState cs[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cs[r] = ConfState{INFINITY, INFINITY, INT_MAX, INT_MAX, -1};
+#pragma unroll
+    for (int s = 0; s < ST; ++s) {
+      f32x4 S = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int v = 0; v < NH * 4; ++v) {
+        const float4 zb =
+            *reinterpret_cast<const float4 *>(Zs + ((v >> 2) * ST * 16 + 16 * s + t) * ZP + 16 * (v & 3) + 4 * q);
+        S = mfma4(xa[v].x, zb.x, S);
+        S = mfma4(xa[v].y, zb.y, S);
+        S = mfma4(xa[v].z, zb.z, S);
+        S = mfma4(xa[v].w, zb.w, S);
+      }
+      const int seed = 16 * s + t;
+      const int comp = slab[seed];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float d = 0.5f * (1.0f - S[r]);
+        ConfState &c = cs[r];
+        if (seed < m) {
+          if (d < c.d1) {  // s ascends: strict '<' keeps the lowest seed index
+            if (comp != c.c1) {
+              c.d2 = c.d1;
+              c.s2 = c.s1;
+            }
+            c.d1 = d;
+            c.s1 = seed;
+            c.c1 = comp;
+          } else if (comp != c.c1 && d < c.d2) {
+            c.d2 = d;
+            c.s2 = seed;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      conf_min_step<0xB1>(cs[r]);
+      conf_min_step<0x4E>(cs[r]);
+      conf_min_step<0x141>(cs[r]);
+      conf_min_step<0x140>(cs[r]);
+    }
+#define UOC_CONF_PICK(F) ((t == 0) ? cs[0].F : (t == 1) ? cs[1].F : (t == 2) ? cs[2].F : cs[3].F)
+    const int sel = UOC_CONF_PICK(s1), riv = UOC_CONF_PICK(s2);
+    const float d1 = UOC_CONF_PICK(d1), d2 = UOC_CONF_PICK(d2);
+#undef UOC_CONF_PICK
+    const int p = tile * 16 + 4 * q + t;
+    if (t < 4 && p < n) {
+      // No seed won (a NaN row leaves sel = INT_MAX): label 0.  assign_kernel indexes slab[] with that value, out of bounds,
+      // and adds to hist[] unguarded; bit-identity with it is claimed for finite rows and seed labels in 0..127 only.
+      const int lab = (unsigned)sel < (unsigned)NLAB ? slab[sel] : 0;
+      const bool has = (unsigned)riv < (unsigned)NLAB;
+      labels[p] = lab;
+      margin[p] = has ? d2 - d1 : 1.0f;
+      if (second) second[p] = has ? slab[riv] : -1;
+      if (closest) closest[p] = sel;
+      if (rival) rival[p] = has ? riv : -1;
+      if ((unsigned)lab < (unsigned)NLAB) atomicAdd(&hist[lab], 1);
+    }
+  }
+  __syncthreads();
+  if (tid < NLAB && hist[tid]) atomicAdd(&counts[tid], hist[tid]);
+}
+
 // "assign zero to the largest cluster" (mean_shift.py:217-227): only labels in
 // range(num_unique) are counted; first maximum wins; swap 0 <-> label_max.
 __global__ __launch_bounds__(256) void relabel_swap_kernel(int *__restrict__ labels, int n,
@@ -2078,6 +2234,48 @@ static int run_seed_cc(const float *Z, int batch, int m, float eps, int *seed_la
   return UOC_OK;
 }
 
+// ---- label confidence (uoc_ms_confidence) ----
+static size_t confidence_ws_bytes(int batch) { return align_up((size_t)batch * NLAB * sizeof(int), 256); }
+
+template <int ST, int NH>
+static void launch_confidence(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m, int *labels,
+                              float *margin, int *second, int *closest, int *rival, int *counts, hipStream_t st) {
+  int nblk = hc_blocks(batch, n) * 2;     // the grid of launch_assign
+  const int maxb = ((n + 15) / 16 + 3) / 4;
+  if (nblk > maxb) nblk = maxb;
+  const size_t lds = (size_t)NH * ST * 16 * ZP * sizeof(float);
+  static DeviceOnce attr_set;
+  if (!attr_set.done() && lds > 48 * 1024) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&confidence_kernel<ST, NH>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set.mark();
+  }
+  const int outs = 2 + (second ? 1 : 0) + (closest ? 1 : 0) + (rival ? 1 : 0);
+  ProfScope prof(KC_MS_CONFIDENCE, st, 2.0 * batch * m * (double)n * C * NH, 4.0 * batch * ((double)n * C * NH + (double)outs * n));
+  hipLaunchKernelGGL((confidence_kernel<ST, NH>), dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m,
+                     labels, margin, second, closest, rival, counts);
+}
+
+static int run_confidence(const float *X, int nh, int batch, int n, const float *Z, const int *seed_labels,
+                          const int *num_unique, int m, int *labels, float *margin, int *second, int *closest, int *rival,
+                          int *counts, hipStream_t st) {
+  UOC_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)batch * NLAB * sizeof(int), st));
+  dispatch<1, 2>(nh, [&](auto NH) {
+    dispatch<1, 2, 3, 4, 5, 6, 7, 8>((m + 15) / 16, [&](auto ST) {
+      launch_confidence<decltype(ST)::value, decltype(NH)::value>(X, batch, n, Z, seed_labels, m, labels, margin, second, closest, rival, counts, st);
+    });
+  });
+  int rb = (n + 255) / 256;
+  if (rb > 512) rb = 512;
+  {  // the swap of run_assign, on the labels and (the same rule: -1 is neither 0 nor the largest label) on `second`
+    ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n * (second ? 2 : 1));
+    hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, labels, n, counts, num_unique);
+    if (second) hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, second, n, counts, num_unique);
+  }
+  UOC_LAUNCH_CHECK();
+  return UOC_OK;
+}
+
 }  // namespace uoc
 
 using namespace uoc;
@@ -2248,6 +2446,56 @@ int uoc_ms_cluster_wide(const float *d_X, int halves, int batch, int n, int m, f
                         int32_t *d_seed_labels_out, void *d_ws, size_t ws_bytes, void *stream) {
   return uoc_ms_cluster_wide_ex(d_X, halves, batch, n, m, kappa, iters, epsilon, UOC_METRIC_COSINE, d_first_index,
                                 d_labels, d_indices, d_Z_out, d_seed_labels_out, d_ws, ws_bytes, stream);
+}
+
+size_t uoc_ms_confidence_workspace_bytes(int batch, int n, int m, int halves) {
+  if (batch < 1 || batch > 65535 || n < 1 || n > UOC_CONF_MAX_N || m < 1 || m > UOC_MAX_SEEDS || halves < 1 || halves > 2)
+    return 0;
+  return confidence_ws_bytes(batch);
+}
+
+int uoc_ms_confidence(const float *d_X, int halves, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
+                      const int32_t *d_num_unique, int m, int metric, int32_t *d_labels, float *d_margin,
+                      int32_t *d_second, int32_t *d_closest, int32_t *d_rival, void *d_ws, size_t ws_bytes, void *stream) {
+  UOC_REQUIRE(metric != UOC_METRIC_EUCLIDEAN, "uoc_ms_confidence: metric = %d (euclidean) is not built: the margin is "
+              "defined for the cosine metric only", metric);
+  UOC_REQUIRE(metric == UOC_METRIC_COSINE, "uoc_ms_confidence: metric = %d: expected %d (cosine)", metric, UOC_METRIC_COSINE);
+  UOC_REQUIRE(halves == 1 || halves == 2, "uoc_ms_confidence: halves = %d (64-d or 128-d embeddings only)", halves);
+  UOC_REQUIRE(batch >= 1 && batch <= 65535, "uoc_ms_confidence: batch = %d outside [1, 65535]", batch);
+  UOC_REQUIRE(n >= 1 && n <= UOC_CONF_MAX_N, "uoc_ms_confidence: n = %d outside [1, %d]", n, UOC_CONF_MAX_N);
+  UOC_REQUIRE(m >= 1 && m <= UOC_MAX_SEEDS, "uoc_ms_confidence: m = %d outside [1, %d]", m, UOC_MAX_SEEDS);
+  UOC_REQUIRE(d_X != nullptr, "uoc_ms_confidence: d_X is null");
+  UOC_REQUIRE(d_Z != nullptr, "uoc_ms_confidence: d_Z is null");
+  UOC_REQUIRE(d_seed_labels != nullptr, "uoc_ms_confidence: d_seed_labels is null");
+  UOC_REQUIRE(d_num_unique != nullptr, "uoc_ms_confidence: d_num_unique is null");
+  UOC_REQUIRE(d_labels != nullptr, "uoc_ms_confidence: d_labels is null");
+  UOC_REQUIRE(d_margin != nullptr, "uoc_ms_confidence: d_margin is null");
+  UOC_REQUIRE(((uintptr_t)d_X & 15) == 0, "uoc_ms_confidence: d_X is not 16-byte aligned");
+  UOC_REQUIRE(((uintptr_t)d_Z & 15) == 0, "uoc_ms_confidence: d_Z is not 16-byte aligned");
+  UOC_REQUIRE(d_ws != nullptr, "uoc_ms_confidence: d_ws is null");
+  UOC_REQUIRE(ws_bytes >= confidence_ws_bytes(batch), "uoc_ms_confidence: workspace %zu < %zu bytes", ws_bytes,
+              confidence_ws_bytes(batch));
+  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_ms_confidence: workspace not 16-byte aligned");
+  {  // no output may lie on an input (the kernel reads X, Z and the seed labels while it writes)
+    const size_t row = (size_t)batch * n * 4;
+    struct Span { const char *name; const void *p; size_t bytes; };
+    const Span in[4] = {{"d_X", d_X, (size_t)batch * halves * n * C * 4}, {"d_Z", d_Z, (size_t)batch * halves * m * C * 4},
+                        {"d_seed_labels", d_seed_labels, (size_t)batch * m * 4}, {"d_num_unique", d_num_unique, (size_t)batch * 4}};
+    const Span out[5] = {{"d_labels", d_labels, row}, {"d_margin", d_margin, row}, {"d_second", d_second, row},
+                         {"d_closest", d_closest, row}, {"d_rival", d_rival, row}};
+    for (const Span &o : out)
+      for (const Span &i : in) {
+        const uintptr_t a = (uintptr_t)o.p, b = (uintptr_t)i.p;
+        UOC_REQUIRE(o.p == nullptr || a + o.bytes <= b || b + i.bytes <= a, "uoc_ms_confidence: %s aliases the input %s", o.name, i.name);
+      }
+    for (int i = 0; i < 5; ++i)
+      for (int j = i + 1; j < 5; ++j) {
+        const uintptr_t a = (uintptr_t)out[i].p, b = (uintptr_t)out[j].p;
+        UOC_REQUIRE(!a || !b || a + row <= b || b + row <= a, "uoc_ms_confidence: %s overlaps %s", out[i].name, out[j].name);
+      }
+  }
+  return run_confidence(d_X, halves, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, d_margin, d_second, d_closest,
+                        d_rival, (int *)d_ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -48,6 +48,8 @@ enum KernelClass {
   KC_FOOT_FIT,     // the fit words, the counts, the keys and the best records
   KC_ROUTES_TABLES,  // routes: the memset, the runs of free cells and the passable maps
   KC_ROUTES_SOLVE,   // the cost fields, the closest approach and the paths
+  KC_MS_CONFIDENCE,  // label confidence: the assignment with the runner-up component and its margin
+  KC_CONF_GLUE,      // the value paste along the paint plan and the per-id summary
   KC_COUNT
 };
 

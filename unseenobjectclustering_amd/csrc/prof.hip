@@ -24,7 +24,8 @@ static const char *kNames[KC_COUNT] = {
     "grasp_moments",     "grasp_candidates",
     "elevation_raster",  "elevation_transform",
     "footprint_tables",  "footprint_fit",
-    "routes_tables",     "routes_solve"};
+    "routes_tables",     "routes_solve",
+    "ms_confidence",     "conf_glue"};
 
 struct Rec {
   int kc;

@@ -150,7 +150,8 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
 
 def segment_objects(sample, network, network_crop, use_refined=True, plane=False, plane_args=None, relations=False,
                     relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, elevation=False,
-                    elevation_args=None, footprint=False, footprint_args=None, routes=False, routes_args=None, **kw):
+                    elevation_args=None, footprint=False, footprint_args=None, routes=False, routes_args=None, confidence=False,
+                    confidence_args=None, **kw):
     """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
     refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
     maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
@@ -165,7 +166,9 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     the elevation item, the oriented put-down poses of the rectangles footprint_args["rects"] on that grid
     (footprint.fit, footprint_args = its keyword arguments, `rects` among them).  routes=True implies placement=True and
     adds, as the last item, the slide paths of the queries routes_args["queries"] on that grid (routes.plan, routes_args =
-    its keyword arguments, `queries` among them)."""
+    its keyword arguments, `queries` among them).  confidence=True takes the frame through confidence.segment_confidence
+    instead (the same label maps, with the assignment margins alongside; confidence_args = its keyword arguments) and
+    adds its FrameConfidence as the last item of all; cosine metric only (NotImplementedError under the euclidean opt-in)."""
     if footprint and "rects" not in (footprint_args or {}):
         raise ValueError("segment_objects: footprint=True needs footprint_args with `rects`")
     if routes and "queries" not in (routes_args or {}):
@@ -177,7 +180,11 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
         sample = uio.prepare_on_device(sample, dev)
     if sample.get("depth") is None:
         raise _native.NativeError("segment_objects needs the XYZ planes (sample['depth'])")
-    labels, refined = TD._run_frame(sample, network, network_crop, TD.DEPTH_FILTER, return_device=True, checked=True)
+    if confidence:
+        from .confidence import segment_confidence
+        labels, refined, conf = segment_confidence(sample, network, network_crop, return_device=True, **(confidence_args or {}))
+    else:
+        labels, refined = TD._run_frame(sample, network, network_crop, TD.DEPTH_FILTER, return_device=True, checked=True)
     xyz = sample["depth"].to(dev)
     src, src_xyz = (refined[:1], xyz[:1]) if use_refined and refined is not None else (labels, xyz)
     objs = extract_objects(src, src_xyz, **kw)
@@ -208,4 +215,4 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     out_refined = refined.float().cpu() if refined is not None else None
     return (out_label, out_refined, objs) + ((fitted,) if plane else ()) + ((related,) if relations else ()) \
         + ((placed,) if placement else ()) + ((grasped,) if grasp else ()) + ((raised,) if elevation else ()) \
-        + ((fitting,) if footprint else ()) + ((routed,) if routes else ())
+        + ((fitting,) if footprint else ()) + ((routed,) if routes else ()) + ((conf,) if confidence else ())
