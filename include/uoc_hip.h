@@ -839,6 +839,63 @@ int uoc_conf_objects(const int32_t *d_labels, const float *d_conf, int B, int H,
 
 
 /* ------------------------------------------------------------------------------------------
+ * Surface normals: per-pixel normals and object faces (no reference counterpart).
+ * d_xyz [B][3][H][W] fp32 metres; d_labels [B][H][W] int32, nullable; d_planes [B] as uoc_support_plane writes them or
+ * filled in by the caller, nullable.  H*W below 2^31.  Pixels are (row, column).  Everything but d_unit is an integer.
+ *
+ * P. Points.  A pixel is valid when x, y, z are finite, z > 0 and q_c = (int) rintf(c * 16000.0f) (fp32 product, round
+ * half to even) has |q_c| <= 524287 for c = x, y, z: the unit is 1/16 mm, a depth in whole millimetres is represented
+ * exactly.  id(p) = L when 1 <= L <= 127, else 0; without labels every id is 0.
+ * D. Pairs, r = step.  The horizontal pair at pixel m has the ends a = m - (0, r) and b = m + (0, r); it exists when both
+ * ends lie inside the image and are valid, id(a) == id(b), and d = q(b) - q(a) has |d_z| <= 16 jump_mm and |d_x|, |d_y| <=
+ * 16383.  The vertical pair is the same with (r, 0).
+ * T. Tangents, s = window.  For pixel p: TX = the sum of d over the horizontal pairs at the (2s+1)^2 pixels m with
+ * |m - p| <= s in both coordinates whose id(a) == id(p), nX their number; TY, nY likewise over the vertical pairs.
+ * |T_c| <= 81 * 16383 < 2^21.
+ * N. Normal.  p has a normal when it is valid, nX >= min_pairs, nY >= min_pairs and n' != 0, where N = TY x TX in int64
+ * (|N_c| < 2^43; a visible surface of an organised cloud then faces the camera, there is no sign search), k = max(0,
+ * bitlength(max_c |N_c|) - 30) and n'_c = N_c >> k, an arithmetic shift (|n'_c| <= 2^30).  grazing = (n' . (q >> 4) >= 0),
+ * again an arithmetic shift; the sum stays below 2^48.
+ * C. Class, only with a plane record that rule F of uoc_placement accepts; Pq, Uq, Vq are its N, U, V (units of 2^-14,
+ * magnitude <= 32768).  c = n' . Pq (below 2^47), L = floor(sqrt(n' . n')), exact (n' . n' < 2^62).  The first rule that
+ * applies: UOC_NORMAL_UP when c * 16384 >= c_up * L; UOC_NORMAL_DOWN when -c * 16384 >= c_up * L; UOC_NORMAL_SIDE when
+ * |c| * 16384 <= s_side * L; else UOC_NORMAL_OBLIQUE.  Every product stays below 2^61.  Without a plane (d_planes NULL,
+ * or a record that rule F rejects) the class is 0.
+ * Z. Azimuth of a SIDE pixel.  a = n' . Uq, b = n' . Vq; the bin is the k in 0..A-1 with the largest a Cx_k + b Cy_k
+ * (below 2^62), ties to the lowest k.  h_dirs: a HOST array [A][2] int32 of (Cx_k, Cy_k), each component in
+ * [-16384, 16384], A in 1..32.  The bin of any other pixel is 0.  No kernel calls a trigonometric function.
+ * Outputs.  d_n [B][H][W][4] int32 = (n'_x, n'_y, n'_z, info), info = class | grazing << 3 | bin << 8 | nX << 16 |
+ * nY << 24; all zero without a normal.  d_unit [B][3][H][W] fp32, nullable = (float)((double) n'_c / sqrt((double)(n' . n'))),
+ * NaN without a normal.  d_faces [B][128][40] int32, row a = id 0..127 (row 0: the background) = (pixels, with_normal,
+ * up, side, oblique, down, grazing, peak) and the histogram [32] of the azimuth bins of the id's SIDE pixels: pixels
+ * counts every pixel of the id, valid or not, the others count pixels with a normal; peak = the fullest bin, ties to the
+ * lowest, -1 when side == 0.
+ * Every count is a sum of ones and every choice is over a strict total order: the result is defined exactly and does
+ * not depend on launch order or batch.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_NORMAL_UP 1
+#define UOC_NORMAL_SIDE 2
+#define UOC_NORMAL_OBLIQUE 3
+#define UOC_NORMAL_DOWN 4
+#define UOC_NORMALS_MAX_DIRS 32
+#define UOC_NORMALS_FACE_WORDS 40
+
+/* 0 for a bad shape (B outside 1..65535, H*W not below 2^31). */
+size_t uoc_normals_workspace_bytes(int B, int H, int W);
+/* step in 1..8, window in 0..4, jump_mm in 1..1000, min_pairs in 1..(2 window + 1)^2, A in 1..32, c_up and s_side in
+ * 0..2^28 with c_up > s_side (the wrapper: c_up = rint(cos(up_deg) 2^28), s_side = rint(sin(side_deg) 2^28)).  h_dirs is
+ * read before the call returns and travels as a kernel argument.  d_n and d_ws 16-byte aligned.  Returns UOC_EINVAL
+ * before any device work for null d_xyz / d_n / d_faces / h_dirs / d_ws, bad ranges, a bad shape, a d_n that is not
+ * 16-byte aligned, a workspace below uoc_normals_workspace_bytes(B, H, W) or one that is not 16-byte aligned;
+ * uoc_last_error names the argument; a rejected call writes nothing, the workspace included.  One memset (the face
+ * accumulators in the workspace) and two launches on `stream`; no host read of device memory, nothing synchronises, no
+ * state is kept between calls. */
+int uoc_normals(const float *d_xyz, const int32_t *d_labels, const uoc_plane *d_planes, int B, int H, int W, int step,
+                int window, int jump_mm, int min_pairs, const int32_t *h_dirs, int A, int c_up, int s_side, int32_t *d_n,
+                float *d_unit, int32_t *d_faces, void *d_ws, size_t ws_bytes, void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

@@ -13,6 +13,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--elevation STEP_M [--elevation-min-pts 2]]
                                    [--putdown LENGTH_M WIDTH_M [--putdown-angles 16]]
                                    [--confidence [WEAK]]
+                                   [--normals]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -85,6 +86,13 @@ nearest seed of another cluster lay behind the one that gave the pixel its label
 stages disagree), and per row, over the pixels of the exported label map (the tracked or split one likewise),
 `conf_mean`, `conf_min` (float64, in steps of 1/65536) and `conf_weak_share`, the share of the object's pixels whose margin
 is below WEAK (default 0.02).  Cosine metric only: under the euclidean opt-in the tool stops with NotImplementedError.
+
+With --normals the surface normals of the frame are computed on the device (unseenobjectclustering_amd/normals.py) from the
+XYZ planes, the exported label map (the tracked or split one likewise) and its support plane, which is fitted for it
+whether or not --plane is given: `normal` [H,W,3] int32, the integer normal per pixel (zero without one), `normal_info`
+[H,W] int32 = class | grazing << 3 | azimuth bin << 8 | nX << 16 | nY << 24 (class 1 up, 2 side, 3 oblique, 4 down), and
+per row `faces` [40] int32 = (pixels, with_normal, up, side, oblique, down, grazing, peak) and the histogram of the
+object's side pixels over 16 azimuth bins of a full turn in the plane's axes (`plane_u`, `plane_v` of --plane).
 """
 import argparse
 import glob
@@ -105,6 +113,7 @@ from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.confidence import summarize  # noqa: E402
 from unseenobjectclustering_amd.elevation import heights, spot  # noqa: E402
 from unseenobjectclustering_amd import footprint  # noqa: E402
+from unseenobjectclustering_amd import normals  # noqa: E402
 from unseenobjectclustering_amd import routes  # noqa: E402
 from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
@@ -202,6 +211,17 @@ def confidence_arrays(summary, ids, margin):
             "conf_min": np.asarray(summary.min[0][ids], np.float64), "conf_weak_share": np.asarray(summary.weak_share[0][ids], np.float64)}
 
 
+NORMALS_KEYS = ("normal", "normal_info", "faces")
+
+
+def normals_arrays(estimated, ids):
+    """The --normals arrays of one frame: the normals and the info words of frame 0 of `estimated` (a normals.estimate
+    result) and, per exported object (ids = its labels), its row of faces."""
+    ids = [int(a) for a in ids]
+    return {"normal": estimated.n[0].cpu().numpy(), "normal_info": estimated.info[0].cpu().numpy(),
+            "faces": estimated.faces[0][ids].cpu().numpy().reshape(len(ids), normals.FACE_WORDS)}
+
+
 RELATION_KEYS = ("layer", "free", "order", "n_above", "edge")
 
 
@@ -266,6 +286,8 @@ def build_parser():
                     help="with --placement: add the slide path of object ID, as a disc of this radius (metres), to the widest spot")
     ap.add_argument("--confidence", type=float, nargs="?", const=0.02, default=None, metavar="WEAK",
                     help="add the assignment-margin map and per object its mean, minimum and the share of pixels below WEAK (0.02)")
+    ap.add_argument("--normals", action="store_true",
+                    help="add the per-pixel surface normals, their classes against the support plane and the faces of the objects")
     return ap
 
 
@@ -339,7 +361,8 @@ def main():
             rows = comp[ids].cpu().numpy()
             rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
         placed = None                       # the grid of --grasp / --elevation, where one of them computes it: --putdown reuses it
-        if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None or args.putdown is not None:
+        if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None or args.putdown is not None \
+                or args.normals:
             fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
         if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
@@ -376,6 +399,9 @@ def main():
         if conf is not None:
             summary = summarize(torch.from_numpy(rec["label_map"]).to(cfg.device), conf.margin, weak=args.confidence)
             rec.update(confidence_arrays(summary, objs.label.long().cpu().tolist(), conf.margin))
+        if args.normals:
+            estimated = normals.estimate(sample["depth"][0].to(cfg.device), torch.from_numpy(rec["label_map"]).to(cfg.device), fitted)
+            rec.update(normals_arrays(estimated, objs.label.long().cpu().tolist()))
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")

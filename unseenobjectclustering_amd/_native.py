@@ -144,6 +144,10 @@ def _declare(lib):
     lib.uoc_conf_paste.restype = c_int
     lib.uoc_conf_objects.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P]
     lib.uoc_conf_objects.restype = c_int
+    lib.uoc_normals_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.uoc_normals_workspace_bytes.restype = c_size_t
+    lib.uoc_normals.argtypes = [P, P, P] + [c_int] * 7 + [P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
+    lib.uoc_normals.restype = c_int
     lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
     lib.uoc_lzf_decompress.restype = ctypes.c_long
     lib.uoc_prof_enable.argtypes = [c_int]
@@ -186,7 +190,8 @@ EXPORTED_SYMBOLS = (
     "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
     "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation",
     "uoc_footprint_workspace_bytes", "uoc_footprint", "uoc_routes_workspace_bytes", "uoc_routes",
-    "uoc_ms_confidence_workspace_bytes", "uoc_ms_confidence", "uoc_conf_paste", "uoc_conf_objects", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
+    "uoc_ms_confidence_workspace_bytes", "uoc_ms_confidence", "uoc_conf_paste", "uoc_conf_objects",
+    "uoc_normals_workspace_bytes", "uoc_normals", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
 )
 
 
@@ -256,6 +261,9 @@ ROUTES_MAX_NEED2 = 4096                         # UOC_ROUTES_MAX_NEED2: a query'
 ROUTES_MAX_PATH = 4096                          # UOC_ROUTES_MAX_PATH: max_path in 1..4096
 CONF_MAX_N = 1 << 30                            # include/uoc_hip.h: UOC_CONF_MAX_N, pixels per field / frame of the confidence calls
 CONF_ONE = 65536                                # the fixed-point unit of uoc_conf_objects' q
+NORMAL_UP, NORMAL_SIDE, NORMAL_OBLIQUE, NORMAL_DOWN = 1, 2, 3, 4      # include/uoc_hip.h: UOC_NORMAL_*, the class of a normal
+NORMALS_MAX_DIRS = 32                           # UOC_NORMALS_MAX_DIRS: A in 1..32
+NORMALS_FACE_WORDS = 40                         # UOC_NORMALS_FACE_WORDS: eight counters and the histogram per id
 
 
 class UocTrack(ctypes.Structure):

@@ -50,6 +50,8 @@ enum KernelClass {
   KC_ROUTES_SOLVE,   // the cost fields, the closest approach and the paths
   KC_MS_CONFIDENCE,  // label confidence: the assignment with the runner-up component and its margin
   KC_CONF_GLUE,      // the value paste along the paint plan and the per-id summary
+  KC_NORMALS_PIXELS,  // surface normals: the memset and the per-pixel stencil with the face accumulators
+  KC_NORMALS_FACES,   // the rows of the faces table
   KC_COUNT
 };
 

@@ -25,7 +25,8 @@ static const char *kNames[KC_COUNT] = {
     "elevation_raster",  "elevation_transform",
     "footprint_tables",  "footprint_fit",
     "routes_tables",     "routes_solve",
-    "ms_confidence",     "conf_glue"};
+    "ms_confidence",     "conf_glue",
+    "normals_pixels",    "normals_faces"};
 
 struct Rec {
   int kc;

@@ -151,7 +151,7 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
 def segment_objects(sample, network, network_crop, use_refined=True, plane=False, plane_args=None, relations=False,
                     relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, elevation=False,
                     elevation_args=None, footprint=False, footprint_args=None, routes=False, routes_args=None, confidence=False,
-                    confidence_args=None, **kw):
+                    confidence_args=None, normals=False, normals_args=None, **kw):
     """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
     refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
     maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
@@ -168,7 +168,9 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     adds, as the last item, the slide paths of the queries routes_args["queries"] on that grid (routes.plan, routes_args =
     its keyword arguments, `queries` among them).  confidence=True takes the frame through confidence.segment_confidence
     instead (the same label maps, with the assignment margins alongside; confidence_args = its keyword arguments) and
-    adds its FrameConfidence as the last item of all; cosine metric only (NotImplementedError under the euclidean opt-in)."""
+    adds its FrameConfidence as a further item; cosine metric only (NotImplementedError under the euclidean opt-in).
+    normals=True implies plane=True and adds, as the last item of all, the surface normals and object faces of the same
+    maps against that plane (normals.estimate, normals_args = its keyword arguments)."""
     if footprint and "rects" not in (footprint_args or {}):
         raise ValueError("segment_objects: footprint=True needs footprint_args with `rects`")
     if routes and "queries" not in (routes_args or {}):
@@ -189,7 +191,7 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     src, src_xyz = (refined[:1], xyz[:1]) if use_refined and refined is not None else (labels, xyz)
     objs = extract_objects(src, src_xyz, **kw)
     placement = placement or grasp or elevation or footprint or routes
-    plane = plane or placement
+    plane = plane or placement or normals
     if plane:
         from .support import fit_plane
         fitted = fit_plane(src, src_xyz, **(plane_args or {}))
@@ -211,8 +213,12 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     if routes:
         from .routes import plan
         routed = plan(placed, **routes_args)
+    if normals:
+        from .normals import estimate
+        estimated = estimate(src_xyz, src, fitted, **(normals_args or {}))
     out_label = labels.float().cpu()
     out_refined = refined.float().cpu() if refined is not None else None
     return (out_label, out_refined, objs) + ((fitted,) if plane else ()) + ((related,) if relations else ()) \
         + ((placed,) if placement else ()) + ((grasped,) if grasp else ()) + ((raised,) if elevation else ()) \
-        + ((fitting,) if footprint else ()) + ((routed,) if routes else ()) + ((conf,) if confidence else ())
+        + ((fitting,) if footprint else ()) + ((routed,) if routes else ()) + ((conf,) if confidence else ()) \
+        + ((estimated,) if normals else ())
