@@ -461,6 +461,51 @@ int uoc_support_plane(const int32_t *d_labels, const float *d_xyz, int B, int H,
 
 
 /* ------------------------------------------------------------------------------------------
+ * Several planes of a frame's background: shelves, walls and the plane the objects stand on (no reference counterpart;
+ * DESIGN.md section 22).  Sequential extraction: rules A, B and C of uoc_support_plane repeated on what the earlier
+ * planes left.  K = max_planes in 1..8, tau_mm in 1..1000, rem_mm in tau_mm..1000, min_inliers >= 3, num_hyp in
+ * 1..1024, B * K <= 65535.
+ *
+ * R. Rounds (integers, exact).  C_0 = the candidates of rule A in raster order.  Round r = 0..K-1 works on C_r,
+ * M_r = |C_r|: its hypotheses follow rule B on C_r with the seed (seed + r) mod 2^32, the ranks i_k being ranks in C_r,
+ * and its winner W_r = (n', p0, L) follows the same argmax and the same tie rule.
+ * S. Stop.  Extraction stops before round r when M_r < 3, when every score of the round is -1 or when the winning score
+ * is below min_inliers.  count = the rounds that produced a plane.
+ * I. Inliers I_r = {q in C_r : |n'.(q - p0)| <= tau_mm * L}; removed R_r = {q in C_r : |n'.(q - p0)| <= rem_mm * L}.
+ * The fringe R_r \ I_r belongs to no plane, but cannot seed a duplicate of plane r.  The survivors
+ * C_{r+1} = C_r \ R_r keep their raster order.
+ * C'. Refinement.  Rule C per plane over I_r and the original fp32 points, with the same fixed summation order: a
+ * uoc_plane per (frame, r), d_planes [B][K].  `candidates` of slot r is M_r.  Slot `count` (the round that stopped, when
+ * count < K) holds zeros but for candidates = M_count, as a frame without a plane does in uoc_support_plane; the slots
+ * after it are all zero.
+ * D'. Objects.  Rule D against every found plane, d_objs [B][K][128] (nullable); slots past count hold zeros.
+ *
+ * d_index [B][H][W] int32: -2 not a candidate; r in I_r; 16 + r in R_r \ I_r; -1 a candidate that survived every round.
+ * d_count [B] int32.  d_info [B][K]: see uoc_plane_info; zeros past count but for round_candidates of slot `count`.
+ * Round 0 is uoc_support_plane bit for bit: with the same num_hyp, tau_mm and seed, d_planes[b][0] and d_objs[b][0][*]
+ * equal what uoc_support_plane writes, for any K and rem_mm and any min_inliers <= that plane's inliers.
+ * Bitwise reproducible; frame b's outputs do not depend on the other frames of the batch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct uoc_plane_info {
+  int32_t round_candidates;  /* M_r                                                                              */
+  int32_t removed;           /* |R_r|                                                                            */
+  float cos0;                /* normal_r . normal_0, fp64 from the fp64 refinement                               */
+  float offset0;             /* normal_0 . centroid_r + d_0: signed distance of plane r's centroid from plane 0  */
+  float extent[4];           /* min a, max a, min b, max b of I_r, (a, b) = ((p - c_r).u_r, (p - c_r).v_r), fp64 */
+} uoc_plane_info;
+
+/* 0 for a bad shape, num_hyp outside 1..1024, max_planes outside 1..8 or B * max_planes above 65535. */
+size_t uoc_planes_workspace_bytes(int B, int H, int W, int num_hyp, int max_planes);
+/* d_ws 16-byte aligned.  Returns UOC_EINVAL before any device work for null pointers (d_objs alone may be null), bad
+ * ranges, a bad shape or a workspace below uoc_planes_workspace_bytes(B, H, W, num_hyp, max_planes).  Launches on
+ * `stream`; no host read, nothing synchronises, no state is kept between calls. */
+int uoc_support_planes(const int32_t *d_labels, const float *d_xyz, int B, int H, int W, int max_planes, int num_hyp,
+                       int tau_mm, int rem_mm, int min_inliers, uint32_t seed, int32_t *d_count, uoc_plane *d_planes,
+                       uoc_plane_info *d_info, int32_t *d_index, uoc_plane_object *d_objs, void *d_ws, size_t ws_bytes,
+                       void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Object relations of a frame: contact, occlusion and pick order (no reference counterpart).
  * d_labels [B][H][W] int32 and d_xyz [B][3][H][W] fp32 metres as for uoc_objects, of which only channel 2 (z) is read;
  * H*W below 2^29.  Integers only.

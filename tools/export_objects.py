@@ -14,6 +14,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--putdown LENGTH_M WIDTH_M [--putdown-angles 16]]
                                    [--confidence [WEAK]]
                                    [--normals]
+                                   [--planes K [--planes-up X Y Z]]
 
 Writes <frame>_objects.npz per frame: the label map the objects come from (`label_map`), one row per object (`frame`,
 `label`, `pixels`, `count`, `box`, `centroid`, `cov`, `aabb_min`, `aabb_max`, `eigenvalues`, `axes`, `obb_center`,
@@ -93,6 +94,16 @@ whether or not --plane is given: `normal` [H,W,3] int32, the integer normal per 
 [H,W] int32 = class | grazing << 3 | azimuth bin << 8 | nX << 16 | nY << 24 (class 1 up, 2 side, 3 oblique, 4 down), and
 per row `faces` [40] int32 = (pixels, with_normal, up, side, oblique, down, grazing, peak) and the histogram of the
 object's side pixels over 16 azimuth bins of a full turn in the plane's axes (`plane_u`, `plane_v` of --plane).
+
+With --planes K up to K (1..8) planes of the exported label map's background are extracted on the device
+(unseenobjectclustering_amd/support.py, fit_planes): shelves, walls and the plane the objects stand on.  `plane_count`,
+and per plane slot `plane_normal` [K,3], `plane_d`, `plane_inliers`, `plane_cos0` (cosine with plane 0), `plane_offset0`
+(distance of its centroid from plane 0) and `plane_extent` [K,4] (min / max of its inliers along its axes); `plane_index`
+[H,W] int32, the map (-2 not background, k an inlier of plane k, 16 + k its fringe, -1 left over); per row `stands_on`, the
+plane the object stands on (-1: none), and `plane_support`, the plane most objects stand on.  That plane, not the
+dominant one, is then the support plane of --placement, --grasp, --elevation, --putdown and --normals.  --planes-up X Y Z
+gives the direction away from the floor in camera coordinates; without it plane 0 decides which planes are horizontal,
+which is wrong in a view that a wall dominates.  Not together with --plane, whose `plane_*` arrays describe one plane.
 """
 import argparse
 import glob
@@ -119,7 +130,7 @@ from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
 from unseenobjectclustering_amd.relations import relate  # noqa: E402
-from unseenobjectclustering_amd.support import fit_plane, standing_objects  # noqa: E402
+from unseenobjectclustering_amd.support import choose_support, fit_plane, fit_planes, standing_objects, standing_on  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
@@ -136,6 +147,19 @@ def plane_arrays(fitted, ids, min_height=None):
     rec.update({name: getattr(fitted, k)[0][ids].cpu().numpy() for k, name in OBJECT_KEYS.items()})
     if min_height is not None:
         rec["standing"] = standing_objects(fitted, min_height)[0][ids].cpu().numpy()
+    return rec
+
+
+PLANES_KEYS = {"count": "plane_count", "normal": "plane_normal", "d": "plane_d", "inliers": "plane_inliers", "cos0": "plane_cos0",
+               "offset0": "plane_offset0", "extent": "plane_extent", "index": "plane_index"}
+
+
+def planes_arrays(several, ids, up=None):
+    """The --planes arrays of one frame: frame 0 of `several` (a support.fit_planes result), per exported object (ids =
+    its labels) the plane it stands on, and the plane most of them stand on."""
+    rec = {name: getattr(several, k)[0].cpu().numpy() for k, name in PLANES_KEYS.items()}
+    rec["stands_on"] = standing_on(several, 0 if up is None else tuple(up))[0][ids].cpu().numpy()
+    rec["plane_support"] = choose_support(several, up=None if up is None else tuple(up))[0].cpu().numpy()
     return rec
 
 
@@ -288,6 +312,10 @@ def build_parser():
                     help="add the assignment-margin map and per object its mean, minimum and the share of pixels below WEAK (0.02)")
     ap.add_argument("--normals", action="store_true",
                     help="add the per-pixel surface normals, their classes against the support plane and the faces of the objects")
+    ap.add_argument("--planes", type=int, default=None, metavar="K",
+                    help="extract up to K planes (1..8) and add them, the index map and the plane every object stands on")
+    ap.add_argument("--planes-up", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                    help="with --planes: the direction away from the floor, camera coordinates")
     return ap
 
 
@@ -296,6 +324,16 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.confidence is not None and not 0.0 <= args.confidence <= 1.0:
         ap.error("--confidence WEAK: a margin in 0..1")
+    if args.planes is not None:
+        if not 1 <= args.planes <= 8:
+            ap.error("--planes K: K in 1..8")
+        if args.plane:
+            ap.error("--planes and --plane both write plane_* arrays: give one of them")
+    if args.planes_up is not None:
+        if args.planes is None:
+            ap.error("--planes-up needs --planes")
+        if not any(args.planes_up):
+            ap.error("--planes-up X Y Z: not the zero vector")
     if args.route is not None:
         if args.placement is None:
             ap.error("--route needs --placement (it routes to the spot that --placement finds)")
@@ -363,7 +401,13 @@ def main():
         placed = None                       # the grid of --grasp / --elevation, where one of them computes it: --putdown reuses it
         if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None or args.putdown is not None \
                 or args.normals:
-            fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device))
+            fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device)) \
+                if args.planes is None else None
+        if args.planes is not None:
+            several = fit_planes(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
+                                 max_planes=args.planes)
+            rec.update(planes_arrays(several, objs.label.long(), args.planes_up))
+            fitted = several.plane(choose_support(several, up=None if args.planes_up is None else tuple(args.planes_up)))
         if args.plane:
             rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
         if args.placement is not None:

@@ -112,6 +112,10 @@ def _declare(lib):
     lib.uoc_plane_workspace_bytes.restype = c_size_t
     lib.uoc_support_plane.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32, P, P, P, P, c_size_t, P]
     lib.uoc_support_plane.restype = c_int
+    lib.uoc_planes_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.uoc_planes_workspace_bytes.restype = c_size_t
+    lib.uoc_support_planes.argtypes = [P, P] + [c_int] * 8 + [ctypes.c_uint32, P, P, P, P, P, P, c_size_t, P]
+    lib.uoc_support_planes.restype = c_int
     lib.uoc_relations_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.uoc_relations_workspace_bytes.restype = c_size_t
     lib.uoc_relations.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]
@@ -187,6 +191,7 @@ EXPORTED_SYMBOLS = (
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
     "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
+    "uoc_planes_workspace_bytes", "uoc_support_planes",
     "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
     "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation",
     "uoc_footprint_workspace_bytes", "uoc_footprint", "uoc_routes_workspace_bytes", "uoc_routes",
@@ -226,6 +231,12 @@ class UocPlaneObject(ctypes.Structure):
                 ("cov2", c_float * 3), ("axis", c_float * 2), ("half", c_float * 3), ("center", c_float * 3)]
 
 
+class UocPlaneInfo(ctypes.Structure):
+    """Mirror of uoc_plane_info (include/uoc_hip.h): one per (frame, plane)."""
+    _fields_ = [("round_candidates", c_int32), ("removed", c_int32), ("cos0", c_float), ("offset0", c_float),
+                ("extent", c_float * 4)]
+
+
 class UocRelationObject(ctypes.Structure):
     """Mirror of uoc_relation_object (include/uoc_hip.h): one per (frame, id)."""
     _fields_ = [(name, c_int32) for name in ("pixels", "edge", "border", "border_bg", "hidden", "n_touch", "n_above", "n_below",
@@ -236,6 +247,8 @@ REL_BORDER, REL_TOUCH, REL_FRONT = 0, 1, 2      # include/uoc_hip.h: UOC_REL_*, 
 REL_MAX_GAP_MM = 65535
 PLANE_MAX_HYP = 1024            # include/uoc_hip.h: num_hyp in 1..1024, tau_mm in 1..1000
 PLANE_MAX_TAU_MM = 1000
+PLANES_MAX = 8                  # uoc_support_planes: max_planes in 1..8
+PLANES_FRINGE = 16              # its index map: 16 + r marks plane r's removal band outside its inliers
 PLACE_WIDEST, PLACE_NEAREST = 0, 1              # include/uoc_hip.h: UOC_PLACE_*, the mode of a placement query
 PLACE_MAX_QUERIES = 16
 PLACE_MAX_GRID = 512                            # grid: a multiple of 8 in 8..512

@@ -25,6 +25,12 @@
 //   obj_extent_kernel   min / max along the major and minor axis
 //   obj_box_kernel      half extents and centre of the upright box
 //
+// uoc_support_planes repeats hyp / score / select on what the earlier planes left: pselect_kernel (the
+// argmax with the stop rule and both bands of the winner), recount_kernel / rescatter_kernel (the survivors, re-compacted
+// in raster order between two 8-byte lists), then index_kernel (the first plane whose removal band holds a pixel claims
+// it), psum_kernel / pmom_kernel / pfit_kernel (refinement per (frame, plane) over the index map, in the order of the
+// plane_* kernels), pextent_kernel, pinfo_kernel and the six object kernels with (frame, plane) as their batch.
+//
 // Determinism: steps A and B are integer arithmetic and integer atomic adds, which commute.  Every floating-point sum
 // has a fixed order: a lane adds its own pixels in program order, a wave sums its lanes with a fixed DPP tree, a block
 // adds its four waves in wave order, the per-frame kernels add the chunks in chunk order.  No float atomics; min / max
@@ -413,28 +419,19 @@ __global__ __launch_bounds__(256) void plane_mom_kernel(const int *__restrict__ 
   block_sum_store<6>(acc, ws, pmom + ((size_t)b * nch + c) * 6);
 }
 
-__global__ __launch_bounds__(64) void plane_fit_kernel(int nch, const Win *__restrict__ win,
-                                                       const double *__restrict__ psum, const double *__restrict__ pmom,
-                                                       uoc_plane *__restrict__ planes, double *__restrict__ frame) {
-  __shared__ double cs[3], ms[6];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const Win wn = win[b];
-  if (wn.found) {
-    if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)b * nch * 3, nch, tid) / wn.score;
-    if (tid >= 8 && tid < 14) ms[tid - 8] = chunk_sum<6>(pmom + (size_t)b * nch * 6, nch, tid - 8) / wn.score;
-  }
-  __syncthreads();
-  if (tid != 0) return;
+// The uoc_plane record and the fp64 frame F[NFR] of one plane from its centroid cs and centred moments ms (both already
+// divided by the inlier count).  One thread.
+__device__ __forceinline__ void fit_record(int found, int M, int score, int hyp, const double *cs, const double *ms,
+                                           uoc_plane *__restrict__ out, double *__restrict__ F) {
   uoc_plane o;
-  double *F = frame + (size_t)b * NFR;
-  o.found = wn.found;
-  o.candidates = wn.M;
-  o.inliers = wn.score;
-  o.hyp = wn.hyp;
+  o.found = found;
+  o.candidates = M;
+  o.inliers = score;
+  o.hyp = hyp;
   o.d = o.rms = 0.f;
   for (int k = 0; k < 3; ++k) o.normal[k] = o.centroid[k] = o.eig[k] = o.u[k] = o.v[k] = 0.f;
   for (int k = 0; k < NFR; ++k) F[k] = 0.0;
-  if (wn.found) {
+  if (found) {
     double a[3][3] = {{ms[0], ms[1], ms[2]}, {ms[1], ms[3], ms[4]}, {ms[2], ms[4], ms[5]}}, v[3][3];
     jacobi3(a, v);
     double lam[3], vec[3][3];
@@ -472,7 +469,22 @@ __global__ __launch_bounds__(64) void plane_fit_kernel(int nch, const Win *__res
     o.d = (float)d;
     o.rms = (float)sqrt(fmax(lam[2], 0.0));
   }
-  planes[b] = o;
+  *out = o;
+}
+
+__global__ __launch_bounds__(64) void plane_fit_kernel(int nch, const Win *__restrict__ win,
+                                                       const double *__restrict__ psum, const double *__restrict__ pmom,
+                                                       uoc_plane *__restrict__ planes, double *__restrict__ frame) {
+  __shared__ double cs[3], ms[6];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const Win wn = win[b];
+  if (wn.found) {
+    if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)b * nch * 3, nch, tid) / wn.score;
+    if (tid >= 8 && tid < 14) ms[tid - 8] = chunk_sum<6>(pmom + (size_t)b * nch * 6, nch, tid - 8) / wn.score;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  fit_record(wn.found, wn.M, wn.score, wn.hyp, cs, ms, planes + b, frame + (size_t)b * NFR);
 }
 
 // ---- D. objects against the plane ---------------------------------------------------------------------------------------
@@ -502,7 +514,7 @@ __device__ __forceinline__ void inplane_of(const Frame &f, const Pt &q, double &
 }
 
 __global__ __launch_bounds__(256) void obj_sum_kernel(const int *__restrict__ labels, const float *__restrict__ xyz,
-                                                      int n, int nch, const double *__restrict__ frame,
+                                                      int n, int nch, int per, const double *__restrict__ frame,
                                                       int *__restrict__ ocnt, unsigned long long *__restrict__ okey,
                                                       double *__restrict__ osum, float *__restrict__ height) {
   __shared__ int bcnt[NL];
@@ -515,8 +527,8 @@ __global__ __launch_bounds__(256) void obj_sum_kernel(const int *__restrict__ la
   for (int i = tid; i < NL * 2; i += 256) (&bkey[0][0])[i] = 0ull;
   for (int i = tid; i < WAVES * NL * 2; i += 256) (&wsum[0][0][0])[i] = 0.0;
   __syncthreads();
-  const int *L = labels + (size_t)b * n;
-  const float *X = xyz + (size_t)b * 3 * n;
+  const int *L = labels + (size_t)(b / per) * n;  // `per` batch entries (planes) share one image
+  const float *X = xyz + (size_t)(b / per) * 3 * n;
   const int p0 = c * CHUNK + w * SUB;
   for (int it = 0; it < SUB / 64; ++it) {
     const int base = p0 + it * 64;
@@ -577,7 +589,7 @@ __global__ __launch_bounds__(NL) void obj_mean_kernel(int nch, const double *__r
 }
 
 __global__ __launch_bounds__(256) void obj_mom_kernel(const int *__restrict__ labels, const float *__restrict__ xyz,
-                                                      int n, int nch, const double *__restrict__ frame,
+                                                      int n, int nch, int per, const double *__restrict__ frame,
                                                       const double *__restrict__ ofoot, double *__restrict__ omom) {
   __shared__ double foot[NL][2];
   __shared__ double wmom[WAVES][NL][3];
@@ -588,8 +600,8 @@ __global__ __launch_bounds__(256) void obj_mom_kernel(const int *__restrict__ la
   for (int i = tid; i < NL * 2; i += 256) (&foot[0][0])[i] = ofoot[(size_t)b * NL * 2 + i];
   for (int i = tid; i < WAVES * NL * 3; i += 256) (&wmom[0][0][0])[i] = 0.0;
   __syncthreads();
-  const int *L = labels + (size_t)b * n;
-  const float *X = xyz + (size_t)b * 3 * n;
+  const int *L = labels + (size_t)(b / per) * n;  // `per` batch entries (planes) share one image
+  const float *X = xyz + (size_t)(b / per) * 3 * n;
   const int p0 = c * CHUNK + w * SUB;
   for (int it = 0; it < SUB / 64; ++it) {
     const int base = p0 + it * 64;
@@ -671,7 +683,7 @@ __global__ __launch_bounds__(NL) void obj_axis_kernel(int nch, const double *__r
 }
 
 __global__ __launch_bounds__(256) void obj_extent_kernel(const int *__restrict__ labels, const float *__restrict__ xyz,
-                                                         int n, const double *__restrict__ frame,
+                                                         int n, int per, const double *__restrict__ frame,
                                                          const double *__restrict__ ofoot,
                                                          const double *__restrict__ oaxis,
                                                          unsigned long long *__restrict__ okey) {
@@ -687,8 +699,8 @@ __global__ __launch_bounds__(256) void obj_extent_kernel(const int *__restrict__
   }
   for (int i = tid; i < NL * 4; i += 256) (&bext[0][0])[i] = 0ull;
   __syncthreads();
-  const int *L = labels + (size_t)b * n;
-  const float *X = xyz + (size_t)b * 3 * n;
+  const int *L = labels + (size_t)(b / per) * n;  // `per` batch entries (planes) share one image
+  const float *X = xyz + (size_t)(b / per) * 3 * n;
   const int p0 = c * CHUNK + w * SUB;
   for (int it = 0; it < SUB / 64; ++it) {
     const int base = p0 + it * 64;
@@ -745,6 +757,388 @@ __global__ __launch_bounds__(NL) void obj_box_kernel(const double *__restrict__ 
   for (int i = 0; i < 3; ++i) o->center[i] = (float)(f.c[i] + ((a * f.u[i] + bb * f.v[i]) + mid[2] * f.n[i]));
 }
 
+// ==== several planes (uoc_support_planes) ===========================================================
+// Sequential extraction: rounds of hyp / score / select on a candidate list that shrinks by the winner's removal band.
+// M_r and the stop flag live on the device: a stopped frame has M = 0 from then on, so hyp_kernel writes degenerate
+// hypotheses, score_kernel's blocks exit at once and the round's winner is "not found".
+constexpr int MAX_PLANES = 8;
+constexpr int FRINGE = 16;  // index map: FRINGE + r marks the removal band of plane r outside its inliers
+
+struct PWin {  // winner of (frame, round)
+  int found, hyp, score, M;
+  Hyp h;   // inlier band:  |n'.(q - p0)| <= tau * L
+  Hyp hr;  // removal band: |n'.(q - p0)| <= rem * L
+};
+
+__device__ __forceinline__ void unpack_q(const int2 q, int &qx, int &qy, int &qz) {
+  qx = (short)(q.x & 0xffff);
+  qy = q.x >> 16;
+  qz = q.y;
+}
+
+// select_kernel with the stop rule: not found below min_inliers; the winner also carries its removal band.
+__global__ __launch_bounds__(256) void pselect_kernel(int num_hyp, int K, int r, int tau_mm, int rem_mm, int min_inliers,
+                                                      const Hyp *__restrict__ hyp, const unsigned *__restrict__ score,
+                                                      const int *__restrict__ Mv, PWin *__restrict__ win) {
+  __shared__ unsigned long long best[256];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  unsigned long long k = 0ull;
+  for (int h = tid; h < num_hyp; h += 256) {
+    const unsigned long long sc1 = hyp[(size_t)b * num_hyp + h].ok ? (unsigned long long)score[(size_t)b * num_hyp + h] + 1ull : 0ull;
+    k = max(k, (sc1 << 10) | (unsigned long long)(1023 - h));
+  }
+  best[tid] = k;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) best[tid] = max(best[tid], best[tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const unsigned long long top = best[0];
+    const Hyp none{0, 0, 0, 0, -1ll, 0ull};
+    PWin o;
+    o.M = Mv[b];
+    o.found = (top >> 10) != 0ull && (long long)((top >> 10) - 1ull) >= (long long)min_inliers;
+    o.hyp = o.found ? 1023 - (int)(top & 1023ull) : 0;
+    o.score = o.found ? (int)((top >> 10) - 1ull) : 0;
+    o.h = o.found ? hyp[(size_t)b * num_hyp + o.hyp] : none;
+    o.hr = o.h;
+    if (o.found) {
+      const long long L = (long long)(o.h.thr2 / (2ull * (unsigned long long)tau_mm));  // thr2 = 2 * tau * L exactly
+      o.hr.c0 = o.h.c0 + (long long)(rem_mm - tau_mm) * L;                               // rem * L - n'.p0
+      o.hr.thr2 = 2ull * (unsigned long long)rem_mm * (unsigned long long)L;
+    }
+    win[(size_t)b * K + r] = o;
+  }
+}
+
+// Re-compaction of the survivors, pass 1: survivors per wave; a wave owns SUB consecutive list entries.
+__global__ __launch_bounds__(256) void recount_kernel(const int2 *__restrict__ src, const int *__restrict__ Mv, int n,
+                                                      int nch, int K, int r, const PWin *__restrict__ win,
+                                                      int *__restrict__ wcnt) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, b = blockIdx.y;
+  const PWin *wn = win + (size_t)b * K + r;
+  if (!wn->found) return;  // a stopped frame: uniform per block
+  const Hyp hr = wn->hr;
+  const int M = Mv[b];
+  const int2 *S = src + (size_t)b * n;
+  const long long i0 = (long long)c * CHUNK + (long long)w * SUB;
+  int cnt = 0;
+  for (int it = 0; it < SUB / 64; ++it) {
+    const long long base = i0 + it * 64;
+    if (base >= M) break;  // uniform per wave
+    const long long i = base + lane;
+    bool keep = false;
+    if (i < M) {
+      int qx, qy, qz;
+      unpack_q(S[i], qx, qy, qz);
+      keep = !inlier(hr, qx, qy, qz);
+    }
+    cnt += __popcll(__ballot(keep));
+  }
+  if (lane == 0) wcnt[((size_t)b * nch + c) * WAVES + w] = cnt;
+}
+
+// Pass 2: every block sums the wave counts in front of it (integers: any order), then scatters its survivors at their
+// raster-order rank; the last block also writes M_{r+1}.  A stopped frame gets M_{r+1} = 0 and nothing else.
+__global__ __launch_bounds__(256) void rescatter_kernel(const int2 *__restrict__ src, int2 *__restrict__ dst,
+                                                        const int *__restrict__ Mv, int *__restrict__ Mnext, int n,
+                                                        int nch, int K, int r, const PWin *__restrict__ win,
+                                                        const int *__restrict__ wcnt) {
+  __shared__ int part[256];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, b = blockIdx.y;
+  const PWin *wn = win + (size_t)b * K + r;
+  if (!wn->found) {
+    if (c == nch - 1 && tid == 0) Mnext[b] = 0;
+    return;
+  }
+  const Hyp hr = wn->hr;
+  const int M = Mv[b];
+  const int *WC = wcnt + (size_t)b * nch * WAVES;
+  int s = 0;
+  for (int i = tid; i < c * WAVES; i += 256) s += WC[i];
+  part[tid] = s;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) part[tid] += part[tid + st];
+    __syncthreads();
+  }
+  int run = part[0];
+  for (int k = 0; k < w; ++k) run += WC[c * WAVES + k];
+  if (c == nch - 1 && tid == 0) Mnext[b] = part[0] + ((WC[c * WAVES] + WC[c * WAVES + 1]) + (WC[c * WAVES + 2] + WC[c * WAVES + 3]));
+  const int2 *S = src + (size_t)b * n;
+  int2 *D = dst + (size_t)b * n;
+  const long long i0 = (long long)c * CHUNK + (long long)w * SUB;
+  for (int it = 0; it < SUB / 64; ++it) {
+    const long long base = i0 + it * 64;
+    if (base >= M) break;
+    const long long i = base + lane;
+    bool keep = false;
+    int2 q = make_int2(0, 0);
+    if (i < M) {
+      q = S[i];
+      int qx, qy, qz;
+      unpack_q(q, qx, qy, qz);
+      keep = !inlier(hr, qx, qy, qz);
+    }
+    const unsigned long long m = __ballot(keep);
+    if (keep) D[run + lane_rank(m)] = q;  // rank < M_{r+1} <= M_r <= n: pass 1 counted the same survivors
+    run += __popcll(m);
+  }
+}
+
+// The index map: every pixel tests the winners in order, the first whose removal band holds it claims it.
+__global__ __launch_bounds__(256) void index_kernel(const int *__restrict__ labels, const float *__restrict__ xyz, int n,
+                                                    int K, const PWin *__restrict__ win, int *__restrict__ index,
+                                                    int *__restrict__ pcnt) {
+  __shared__ int bcnt[MAX_PLANES];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, b = blockIdx.y;
+  if (tid < MAX_PLANES) bcnt[tid] = 0;
+  __syncthreads();
+  const int *L = labels + (size_t)b * n;
+  const float *X = xyz + (size_t)b * 3 * n;
+  const PWin *WN = win + (size_t)b * K;
+  int *IX = index + (size_t)b * n;
+  const int p0 = c * CHUNK + w * SUB;
+  int cnt[MAX_PLANES];
+#pragma unroll
+  for (int r = 0; r < MAX_PLANES; ++r) cnt[r] = 0;
+  for (int it = 0; it < SUB / 64; ++it) {
+    const int base = p0 + it * 64;
+    if (base >= n) break;
+    const int p = base + lane;
+    const Pt q = load_pt(L, X, n, p);
+    int idx = q.cand ? -1 : -2;
+#pragma unroll
+    for (int r = 0; r < MAX_PLANES; ++r) {
+      if (r < K && WN[r].found) {  // uniform: found planes are the slots 0..count-1
+        const bool claim = q.cand && idx == -1 && inlier(WN[r].hr, q.qx, q.qy, q.qz);
+        if (claim) idx = inlier(WN[r].h, q.qx, q.qy, q.qz) ? r : FRINGE + r;
+        cnt[r] += __popcll(__ballot(claim));
+      }
+    }
+    if (p < n) IX[p] = idx;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < MAX_PLANES; ++r)
+      if (cnt[r]) atomicAdd(&bcnt[r], cnt[r]);
+  }
+  __syncthreads();
+  if (tid < K && bcnt[tid]) atomicAdd(&pcnt[(size_t)b * K + tid], bcnt[tid]);
+}
+
+// Refinement sums of plane r = blockIdx.y % K over the pixels the index map gives to r as inliers: the per-lane, lane
+// tree, wave and chunk order of plane_sum_kernel / plane_mom_kernel, so plane 0 has the bits of uoc_support_plane.
+__global__ __launch_bounds__(256) void psum_kernel(const float *__restrict__ xyz, const int *__restrict__ index, int n,
+                                                   int nch, int K, const PWin *__restrict__ win,
+                                                   double *__restrict__ psum) {
+  __shared__ double ws[WAVES][3];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, by = blockIdx.y, b = by / K, r = by - b * K;
+  if (!win[by].found) return;
+  const float *X = xyz + (size_t)b * 3 * n;
+  const int *IX = index + (size_t)b * n;
+  const int p0 = c * CHUNK + w * SUB;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int it = 0; it < SUB / 64; ++it) {
+    const int base = p0 + it * 64;
+    if (base >= n) break;
+    const int p = base + lane;
+    if (p < n && IX[p] == r) {
+      acc[0] += (double)X[p];
+      acc[1] += (double)X[(size_t)n + p];
+      acc[2] += (double)X[2 * (size_t)n + p];
+    }
+  }
+  block_sum_store<3>(acc, ws, psum + ((size_t)by * nch + c) * 3);
+}
+
+__global__ __launch_bounds__(256) void pmom_kernel(const float *__restrict__ xyz, const int *__restrict__ index, int n,
+                                                   int nch, int K, const PWin *__restrict__ win,
+                                                   const double *__restrict__ psum, double *__restrict__ pmom) {
+  __shared__ double ws[WAVES][6];
+  __shared__ double cs[3];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, by = blockIdx.y, b = by / K, r = by - b * K;
+  const int found = win[by].found, score = win[by].score;
+  if (!found) return;
+  if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)by * nch * 3, nch, tid) / score;
+  __syncthreads();
+  const double c0 = cs[0], c1 = cs[1], c2 = cs[2];
+  const float *X = xyz + (size_t)b * 3 * n;
+  const int *IX = index + (size_t)b * n;
+  const int p0 = c * CHUNK + w * SUB;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int it = 0; it < SUB / 64; ++it) {
+    const int base = p0 + it * 64;
+    if (base >= n) break;
+    const int p = base + lane;
+    if (p < n && IX[p] == r) {
+      const double dx = (double)X[p] - c0, dy = (double)X[(size_t)n + p] - c1, dz = (double)X[2 * (size_t)n + p] - c2;
+      acc[0] += dx * dx;
+      acc[1] += dx * dy;
+      acc[2] += dx * dz;
+      acc[3] += dy * dy;
+      acc[4] += dy * dz;
+      acc[5] += dz * dz;
+    }
+  }
+  block_sum_store<6>(acc, ws, pmom + ((size_t)by * nch + c) * 6);
+}
+
+__global__ __launch_bounds__(64) void pfit_kernel(int nch, const PWin *__restrict__ win, const double *__restrict__ psum,
+                                                  const double *__restrict__ pmom, uoc_plane *__restrict__ planes,
+                                                  double *__restrict__ frame) {
+  __shared__ double cs[3], ms[6];
+  const int tid = threadIdx.x, by = blockIdx.x;
+  const int found = win[by].found, score = win[by].score;
+  if (found) {
+    if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)by * nch * 3, nch, tid) / score;
+    if (tid >= 8 && tid < 14) ms[tid - 8] = chunk_sum<6>(pmom + (size_t)by * nch * 6, nch, tid - 8) / score;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  fit_record(found, win[by].M, score, win[by].hyp, cs, ms, planes + by, frame + (size_t)by * NFR);
+}
+
+// In-plane extents of every plane's inliers through the ordered keys: max a, max -a, max b, max -b.
+__global__ __launch_bounds__(256) void pextent_kernel(const float *__restrict__ xyz, const int *__restrict__ index, int n,
+                                                      int K, const double *__restrict__ frame,
+                                                      unsigned long long *__restrict__ pext) {
+  __shared__ double fr[MAX_PLANES][NFR];
+  __shared__ unsigned long long bext[MAX_PLANES][4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.x, b = blockIdx.y;
+  if (frame[(size_t)b * K * NFR + FR_FOUND] == 0.0) return;  // no plane 0: no plane at all
+  for (int i = tid; i < K * NFR; i += 256) (&fr[0][0])[i] = frame[(size_t)b * K * NFR + i];
+  for (int i = tid; i < MAX_PLANES * 4; i += 256) (&bext[0][0])[i] = 0ull;
+  __syncthreads();
+  const float *X = xyz + (size_t)b * 3 * n;
+  const int *IX = index + (size_t)b * n;
+  const int p0 = c * CHUNK + w * SUB;
+  for (int it = 0; it < SUB / 64; ++it) {
+    const int base = p0 + it * 64;
+    if (base >= n) break;
+    const int p = base + lane;
+    const int idx = p < n ? IX[p] : -2;
+    const bool valid = idx >= 0 && idx < K;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (valid) {
+      x = (double)X[p];
+      y = (double)X[(size_t)n + p];
+      z = (double)X[2 * (size_t)n + p];
+    }
+    unsigned long long rem = __ballot(valid);
+    while (rem) {
+      const int first = __ffsll((long long)rem) - 1;
+      const int r = __builtin_amdgcn_readlane(idx, first);
+      const unsigned long long vm = __ballot(valid && idx == r);
+      rem &= ~vm;
+      const bool gv = (vm >> lane) & 1ull;
+      const double *F = fr[r];
+      const double dx = x - F[FR_C + 0], dy = y - F[FR_C + 1], dz = z - F[FR_C + 2];
+      const double a = (dx * F[FR_U + 0] + dy * F[FR_U + 1]) + dz * F[FR_U + 2];
+      const double bb = (dx * F[FR_V + 0] + dy * F[FR_V + 1]) + dz * F[FR_V + 2];
+      const double ha = wave_max_d(gv ? a : -INFINITY), la = wave_max_d(gv ? -a : -INFINITY);
+      const double hb = wave_max_d(gv ? bb : -INFINITY), lb = wave_max_d(gv ? -bb : -INFINITY);
+      if (lane == 0) {
+        atomicMax(&bext[r][0], dkey(ha));
+        atomicMax(&bext[r][1], dkey(la));
+        atomicMax(&bext[r][2], dkey(hb));
+        atomicMax(&bext[r][3], dkey(lb));
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < K * 4; i += 256) {
+    const unsigned long long v = (&bext[0][0])[i];
+    if (v) atomicMax(&pext[(size_t)b * K * 4 + i], v);
+  }
+}
+
+__global__ __launch_bounds__(64) void pinfo_kernel(int K, const PWin *__restrict__ win, const double *__restrict__ frame,
+                                                   const int *__restrict__ pcnt,
+                                                   const unsigned long long *__restrict__ pext,
+                                                   uoc_plane_info *__restrict__ info, int *__restrict__ count) {
+  const int r = threadIdx.x, b = blockIdx.x;
+  if (r == 0) {
+    int cnt = 0;
+    for (int k = 0; k < K; ++k) cnt += win[(size_t)b * K + k].found;
+    count[b] = cnt;
+  }
+  if (r >= K) return;
+  const size_t by = (size_t)b * K + r;
+  uoc_plane_info o;
+  o.round_candidates = win[by].M;
+  o.removed = 0;
+  o.cos0 = o.offset0 = 0.f;
+  for (int k = 0; k < 4; ++k) o.extent[k] = 0.f;
+  if (win[by].found) {
+    const double *F0 = frame + (size_t)b * K * NFR, *F = frame + by * NFR;
+    o.removed = pcnt[by];
+    o.cos0 = (float)((F[FR_N + 0] * F0[FR_N + 0] + F[FR_N + 1] * F0[FR_N + 1]) + F[FR_N + 2] * F0[FR_N + 2]);
+    o.offset0 = (float)(((F0[FR_N + 0] * F[FR_C + 0] + F0[FR_N + 1] * F[FR_C + 1]) + F0[FR_N + 2] * F[FR_C + 2]) + F0[FR_D]);
+    const unsigned long long *E = pext + by * 4;
+    o.extent[0] = (float)(-ddecode(E[1]));
+    o.extent[1] = (float)ddecode(E[0]);
+    o.extent[2] = (float)(-ddecode(E[3]));
+    o.extent[3] = (float)ddecode(E[2]);
+  }
+  info[by] = o;
+}
+
+// Workspace layout (uoc_planes_workspace_bytes).  The zeroed part comes first.
+struct PWs {
+  unsigned *score;            // [K][B][num_hyp]         zeroed
+  int *ocnt;                  // [B*K][NL]               zeroed
+  unsigned long long *okey;   // [B*K][NL][NKEY]         zeroed
+  int *pcnt;                  // [B*K]                   zeroed
+  unsigned long long *pext;   // [B*K][4]                zeroed
+  int *wcnt;                  // [B][nch][WAVES]
+  int *M;                     // [K+1][B]
+  int2 *cand[2];              // [B][n] each: ping-pong
+  Hyp *hyp;                   // [B][num_hyp]
+  PWin *win;                  // [B*K]
+  double *psum, *pmom, *frame, *osum, *omom, *ofoot, *oaxis;  // as Ws, with (frame, plane) as the batch
+  size_t zero_bytes, total;
+};
+PWs pcarve(void *base, int B, size_t n, int nch, int num_hyp, int K) {
+  PWs w;
+  char *p = (char *)base;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char *r = p ? p + off : nullptr;
+    off = align_up(off + bytes, 256);
+    return r;
+  };
+  const size_t BK = (size_t)B * K;
+  w.score = (unsigned *)take(BK * num_hyp * 4);
+  w.ocnt = (int *)take(BK * NL * 4);
+  w.okey = (unsigned long long *)take(BK * NL * NKEY * 8);
+  w.pcnt = (int *)take(BK * 4);
+  w.pext = (unsigned long long *)take(BK * 4 * 8);
+  w.zero_bytes = off;
+  w.wcnt = (int *)take((size_t)B * nch * WAVES * 4);
+  w.M = (int *)take((size_t)(K + 1) * B * 4);
+  w.cand[0] = (int2 *)take((size_t)B * n * 8);
+  w.cand[1] = (int2 *)take((size_t)B * n * 8);
+  w.hyp = (Hyp *)take((size_t)B * num_hyp * sizeof(Hyp));
+  w.win = (PWin *)take(BK * sizeof(PWin));
+  w.psum = (double *)take(BK * nch * 3 * 8);
+  w.pmom = (double *)take(BK * nch * 6 * 8);
+  w.frame = (double *)take(BK * NFR * 8);
+  w.osum = (double *)take(BK * nch * NL * 2 * 8);
+  w.omom = (double *)take(BK * nch * NL * 3 * 8);
+  w.ofoot = (double *)take(BK * NL * 2 * 8);
+  w.oaxis = (double *)take(BK * NL * 2 * 8);
+  w.total = off;
+  return w;
+}
+
 }  // namespace
 }  // namespace uoc
 
@@ -797,12 +1191,88 @@ int uoc_support_plane(const int32_t *d_labels, const float *d_xyz, int B, int H,
   }
   {
     ProfScope prof(KC_PLANE_OBJECTS, st, 0.0, px * (3 * 16.0 + (d_height ? 4.0 : 0.0)));
-    hipLaunchKernelGGL(obj_sum_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.frame, w.ocnt, w.okey, w.osum, d_height);
+    hipLaunchKernelGGL(obj_sum_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, 1, w.frame, w.ocnt, w.okey, w.osum, d_height);
     hipLaunchKernelGGL(obj_mean_kernel, dim3(B), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.osum, w.ofoot);
-    hipLaunchKernelGGL(obj_mom_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.frame, w.ofoot, w.omom);
+    hipLaunchKernelGGL(obj_mom_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, 1, w.frame, w.ofoot, w.omom);
     hipLaunchKernelGGL(obj_axis_kernel, dim3(B), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.okey, w.ofoot, w.omom, w.oaxis, d_objs);
-    hipLaunchKernelGGL(obj_extent_kernel, grid, blk, 0, st, d_labels, d_xyz, n, w.frame, w.ofoot, w.oaxis, w.okey);
+    hipLaunchKernelGGL(obj_extent_kernel, grid, blk, 0, st, d_labels, d_xyz, n, 1, w.frame, w.ofoot, w.oaxis, w.okey);
     hipLaunchKernelGGL(obj_box_kernel, dim3(B), dim3(NL), 0, st, w.frame, w.ofoot, w.oaxis, w.okey, d_objs);
+  }
+  UOC_LAUNCH_CHECK();
+  return UOC_OK;
+}
+
+size_t uoc_planes_workspace_bytes(int B, int H, int W, int num_hyp, int max_planes) {
+  if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > INT_MAX || num_hyp < 1 || num_hyp > MAX_HYP ||
+      max_planes < 1 || max_planes > MAX_PLANES || (long long)B * max_planes > 65535)
+    return 0;
+  const long long n = (long long)H * W;
+  return pcarve(nullptr, B, (size_t)n, (int)((n + CHUNK - 1) / CHUNK), num_hyp, max_planes).total;
+}
+
+int uoc_support_planes(const int32_t *d_labels, const float *d_xyz, int B, int H, int W, int max_planes, int num_hyp,
+                       int tau_mm, int rem_mm, int min_inliers, uint32_t seed, int32_t *d_count, uoc_plane *d_planes,
+                       uoc_plane_info *d_info, int32_t *d_index, uoc_plane_object *d_objs, void *d_ws, size_t ws_bytes,
+                       void *stream) {
+  UOC_REQUIRE(d_labels && d_xyz && d_count && d_planes && d_info && d_index && d_ws,
+              "uoc_support_planes: null labels / xyz / count / planes / info / index / workspace");
+  UOC_REQUIRE(B > 0 && H > 0 && W > 0, "uoc_support_planes: bad shape B=%d H=%d W=%d", B, H, W);
+  UOC_REQUIRE((long long)B * H * W <= INT_MAX, "uoc_support_planes: B*H*W = %lld exceeds int32 indexing", (long long)B * H * W);
+  UOC_REQUIRE(max_planes >= 1 && max_planes <= MAX_PLANES, "uoc_support_planes: max_planes = %d outside [1, %d]", max_planes, MAX_PLANES);
+  UOC_REQUIRE((long long)B * max_planes <= 65535, "uoc_support_planes: B * max_planes = %lld above 65535", (long long)B * max_planes);
+  UOC_REQUIRE(num_hyp >= 1 && num_hyp <= MAX_HYP, "uoc_support_planes: num_hyp = %d outside [1, %d]", num_hyp, MAX_HYP);
+  UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_support_planes: tau_mm = %d outside [1, 1000]", tau_mm);
+  UOC_REQUIRE(rem_mm >= tau_mm && rem_mm <= 1000, "uoc_support_planes: rem_mm = %d outside [tau_mm = %d, 1000]", rem_mm, tau_mm);
+  UOC_REQUIRE(min_inliers >= 3, "uoc_support_planes: min_inliers = %d below 3", min_inliers);
+  const int K = max_planes, n = H * W;
+  const int nch = (int)(((long long)n + CHUNK - 1) / CHUNK);
+  const PWs w = pcarve(d_ws, B, (size_t)n, nch, num_hyp, K);
+  UOC_REQUIRE(ws_bytes >= w.total, "uoc_support_planes: workspace %zu < %zu bytes", ws_bytes, w.total);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(nch, B), gridk(nch, B * K), blk(256);
+  const double px = (double)B * n;
+  {
+    ProfScope prof(KC_PLANES_CAND, st, 0.0, px * (2 * 16.0 + 8.0));
+    UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.zero_bytes, st));
+    hipLaunchKernelGGL(cand_count_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt);
+    hipLaunchKernelGGL(cand_scan_kernel, dim3(B), blk, 0, st, nch * WAVES, w.wcnt, w.M);
+    hipLaunchKernelGGL(cand_scatter_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt, w.cand[0]);
+  }
+  {
+    ProfScope prof(KC_PLANES_ROUNDS, st, 0.0, px * 8.0 * K);
+    for (int r = 0; r < K; ++r) {
+      const int2 *src = w.cand[r & 1];
+      const int *Mr = w.M + (size_t)r * B;
+      unsigned *score = w.score + (size_t)r * B * num_hyp;
+      hipLaunchKernelGGL(hyp_kernel, dim3((num_hyp + 255) / 256, B), blk, 0, st, src, Mr, n, num_hyp, tau_mm, seed + (uint32_t)r, w.hyp);
+      hipLaunchKernelGGL(score_kernel, dim3((n + TILE - 1) / TILE, B), blk, 0, st, src, Mr, n, num_hyp, w.hyp, score);
+      hipLaunchKernelGGL(pselect_kernel, dim3(B), blk, 0, st, num_hyp, K, r, tau_mm, rem_mm, min_inliers, w.hyp, score, Mr, w.win);
+      if (r + 1 < K) {
+        hipLaunchKernelGGL(recount_kernel, grid, blk, 0, st, src, Mr, n, nch, K, r, w.win, w.wcnt);
+        hipLaunchKernelGGL(rescatter_kernel, grid, blk, 0, st, src, w.cand[(r + 1) & 1], Mr, w.M + (size_t)(r + 1) * B, n, nch, K, r, w.win, w.wcnt);
+      }
+    }
+  }
+  {
+    ProfScope prof(KC_PLANES_INDEX, st, 0.0, px * 20.0);
+    hipLaunchKernelGGL(index_kernel, grid, blk, 0, st, d_labels, d_xyz, n, K, w.win, d_index, w.pcnt);
+  }
+  {
+    ProfScope prof(KC_PLANES_REFINE, st, 0.0, px * 16.0 * (2 * K + 1));
+    hipLaunchKernelGGL(psum_kernel, gridk, blk, 0, st, d_xyz, d_index, n, nch, K, w.win, w.psum);
+    hipLaunchKernelGGL(pmom_kernel, gridk, blk, 0, st, d_xyz, d_index, n, nch, K, w.win, w.psum, w.pmom);
+    hipLaunchKernelGGL(pfit_kernel, dim3(B * K), dim3(64), 0, st, nch, w.win, w.psum, w.pmom, d_planes, w.frame);
+    hipLaunchKernelGGL(pextent_kernel, grid, blk, 0, st, d_xyz, d_index, n, K, w.frame, w.pext);
+    hipLaunchKernelGGL(pinfo_kernel, dim3(B), dim3(64), 0, st, K, w.win, w.frame, w.pcnt, w.pext, d_info, d_count);
+  }
+  if (d_objs) {
+    ProfScope prof(KC_PLANES_OBJECTS, st, 0.0, px * 3 * 16.0 * K);
+    hipLaunchKernelGGL(obj_sum_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, nch, K, w.frame, w.ocnt, w.okey, w.osum, (float *)nullptr);
+    hipLaunchKernelGGL(obj_mean_kernel, dim3(B * K), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.osum, w.ofoot);
+    hipLaunchKernelGGL(obj_mom_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, nch, K, w.frame, w.ofoot, w.omom);
+    hipLaunchKernelGGL(obj_axis_kernel, dim3(B * K), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.okey, w.ofoot, w.omom, w.oaxis, d_objs);
+    hipLaunchKernelGGL(obj_extent_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, K, w.frame, w.ofoot, w.oaxis, w.okey);
+    hipLaunchKernelGGL(obj_box_kernel, dim3(B * K), dim3(NL), 0, st, w.frame, w.ofoot, w.oaxis, w.okey, d_objs);
   }
   UOC_LAUNCH_CHECK();
   return UOC_OK;

@@ -52,6 +52,11 @@ enum KernelClass {
   KC_CONF_GLUE,      // the value paste along the paint plan and the per-id summary
   KC_NORMALS_PIXELS,  // surface normals: the memset and the per-pixel stencil with the face accumulators
   KC_NORMALS_FACES,   // the rows of the faces table
+  KC_PLANES_CAND,     // multi-plane extraction: the memset and the first candidate compaction
+  KC_PLANES_ROUNDS,   // per round: hypotheses, scoring, the argmax and the re-compaction of the survivors
+  KC_PLANES_INDEX,    // the index map and the removed counts
+  KC_PLANES_REFINE,   // fp64 refinement of every plane, the extents and the info records
+  KC_PLANES_OBJECTS,  // heights and upright boxes against every plane
   KC_COUNT
 };
 

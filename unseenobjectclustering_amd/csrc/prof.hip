@@ -26,7 +26,8 @@ static const char *kNames[KC_COUNT] = {
     "footprint_tables",  "footprint_fit",
     "routes_tables",     "routes_solve",
     "ms_confidence",     "conf_glue",
-    "normals_pixels",    "normals_faces"};
+    "normals_pixels",    "normals_faces",
+    "planes_candidates", "planes_rounds",    "planes_index",     "planes_refine",   "planes_objects"};
 
 struct Rec {
   int kc;

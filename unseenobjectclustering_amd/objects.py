@@ -151,7 +151,7 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
 def segment_objects(sample, network, network_crop, use_refined=True, plane=False, plane_args=None, relations=False,
                     relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, elevation=False,
                     elevation_args=None, footprint=False, footprint_args=None, routes=False, routes_args=None, confidence=False,
-                    confidence_args=None, normals=False, normals_args=None, **kw):
+                    confidence_args=None, normals=False, normals_args=None, planes=False, planes_args=None, **kw):
     """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
     refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
     maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
@@ -170,7 +170,11 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     instead (the same label maps, with the assignment margins alongside; confidence_args = its keyword arguments) and
     adds its FrameConfidence as a further item; cosine metric only (NotImplementedError under the euclidean opt-in).
     normals=True implies plane=True and adds, as the last item of all, the surface normals and object faces of the same
-    maps against that plane (normals.estimate, normals_args = its keyword arguments)."""
+    maps against that plane (normals.estimate, normals_args = its keyword arguments).  planes=True adds, as the last
+    item of all, the several planes of the same maps (support.fit_planes; planes_args = its keyword arguments, and `up`,
+    `tol`, `par_deg` of support.choose_support among them).  With it the plane of plane=True (and so of placement=True
+    and every switch that implies it) is not fit_plane's but res.plane(choose_support(res, ...)), the plane most objects
+    stand on, chosen on the device; plane_args is then not used."""
     if footprint and "rects" not in (footprint_args or {}):
         raise ValueError("segment_objects: footprint=True needs footprint_args with `rects`")
     if routes and "queries" not in (routes_args or {}):
@@ -192,7 +196,14 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     objs = extract_objects(src, src_xyz, **kw)
     placement = placement or grasp or elevation or footprint or routes
     plane = plane or placement or normals
-    if plane:
+    if planes:
+        from .support import choose_support, fit_planes
+        pa = dict(planes_args or {})
+        choose = {k: pa.pop(k) for k in ("up", "tol", "par_deg") if k in pa}
+        several = fit_planes(src, src_xyz, **pa)
+        if plane:
+            fitted = several.plane(choose_support(several, **choose))
+    elif plane:
         from .support import fit_plane
         fitted = fit_plane(src, src_xyz, **(plane_args or {}))
     if relations:
@@ -221,4 +232,4 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     return (out_label, out_refined, objs) + ((fitted,) if plane else ()) + ((related,) if relations else ()) \
         + ((placed,) if placement else ()) + ((grasped,) if grasp else ()) + ((raised,) if elevation else ()) \
         + ((fitting,) if footprint else ()) + ((routed,) if routes else ()) + ((conf,) if confidence else ()) \
-        + ((estimated,) if normals else ())
+        + ((estimated,) if normals else ()) + ((several,) if planes else ())
