@@ -5,7 +5,8 @@ np.array_equal.  The scenes and the engineered frames are generated in the refer
 tests/test_elevation_host.py asserts on the CPU that they contain what they are used for here.
 
 Sizes: 5x7 (H*W not a multiple of 4: the scalar path) with G = 8; 48x64 (the vector path, one block) with G = 64 and
-with G = 512 on 2 mm cells; 120x160 (five blocks) with G = 64; 480x640 with G = 256.
+with G = 512 on 2 mm cells; 120x160 (five blocks) with G = 64 and with G = 40 (a second strip of the column pass with 8
+of its 32 columns); 480x640 with G = 256.
 
 Every GPU test runs under a watchdog (faulthandler.dump_traceback_later(..., exit=True)): a hang ends the process instead
 of letting later tests start more GPU work; nothing is retried."""
@@ -82,6 +83,17 @@ def test_tabletop_scenes_match_reference(device, H, W, seed, nobj, G, cell, step
     want = R.heights(lab, xyz, TRUE_F, G, cell, 10, step, min_pts, qs)
     assert want["info"][0] == 1 and want["info"][2] > 0
     check_frame(host(res, 0), want, (H, W, seed, G))
+
+
+def test_partial_strip_of_the_column_pass_matches_reference(device):
+    """G = 40: cell_kernel's second strip holds 8 of its 32 columns; the level cells of those columns are asserted in
+    tests/test_elevation_host.py."""
+    G, cell, tau, step, min_pts = 40, 20, 10, 5, 1
+    lab, xyz = scene(120, 160, 1, 5)
+    dl, dx = to_dev(device, lab, xyz)
+    res = elevation.heights(dl, dx, placed_of(device, TRUE_F, G, cell, tau), step=step / 1000.0, min_pts=min_pts)
+    assert res.elev.shape == (1, G, G) and res.answers.shape == (1, 0, 4)
+    check_frame(host(res, 0), R.heights(lab, xyz, TRUE_F, G, cell, tau, step, min_pts), "G = 40")
 
 
 @pytest.mark.parametrize("name", list(R.ENGINEERED))

@@ -151,6 +151,13 @@ def test_seeded_scenes_hold_the_prototype_condition():
     assert after < before and R.atomic_events(lab, xyz, F, 256, 10, 10, 5, 64)[1] >= after
 
 
+def test_grid_of_40_has_level_cells_in_its_partial_strip():
+    """What tests/test_elevation_gpu.py's G = 40 case is there for: columns 32..39 are the column pass's second strip."""
+    lab, xyz = scene(120, 160, 1, 5)
+    r = R.heights(lab, xyz, R.frame_record(R.true_plane()), 40, 20, 10, 5, 1)
+    assert (~r["blocking"][:, 32:]).sum() > 100 and r["dist2"][:, 32:].max() >= 25     # the reference gives 264 cells, dist2 up to 49
+
+
 def test_einval_paths_and_workspace_bytes():
     from unseenobjectclustering_amd import _native
     lib = _native.lib()

@@ -148,6 +148,15 @@ def test_random_grids_match_reference(device, G):
         check(run(device, *frames[b], A, rects, ub), 0, want[b], (G, n, "alone", b))
 
 
+def test_partial_ballot_word_of_the_runs_matches_reference(device):
+    """G = 72: a row of the run table is one ballot word of 64 cells and one of 8; the fitting cells in those 8 columns are
+    asserted in tests/test_footprint_host.py."""
+    st, ow, d2 = random_grid(72, 1)
+    A, specs, ub = R.RANDOM_SETS[0]
+    rects = R.resolve(specs, R.present_id(ow, st))
+    check(run(device, st, ow, d2, A, rects, ub), 0, R.footprint(st, ow, d2, R.direction_table(A), rects, ub), "G = 72")
+
+
 def test_frames_alone_among_mates_rerun_layouts_and_frame_records(device):
     frames = [random_grid(64, seed) for seed in (1, 2, 3, 4)]
     st, ow, d2 = (dev(device, np.stack([f[n] for f in frames])) for n in range(3))

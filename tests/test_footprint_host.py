@@ -231,6 +231,14 @@ def test_engineered_grids_contain_what_they_are_used_for():
     assert {len(specs) for _, specs, _ in R.RANDOM_SETS} >= {1, 8} and {A for A, _, _ in R.RANDOM_SETS} >= {1, 32}
 
 
+def test_grid_of_72_has_fitting_cells_past_the_first_ballot_word():
+    """What tests/test_footprint_gpu.py's G = 72 case is there for: columns 64..71 are the second ballot word of a row."""
+    st, ow, d2 = R.random_grid(72, 1)
+    A, specs, ub = R.RANDOM_SETS[0]
+    out = R.footprint(st, ow, d2, R.direction_table(A), R.resolve(specs, R.present_id(ow, st)), ub)
+    assert (out["fits"][:, :, 64:] != 0).any()
+
+
 def test_error_paths_through_ctypes():
     lib = _native.lib()
     B, G, A, F = 2, 16, 4, 2

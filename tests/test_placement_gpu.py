@@ -6,7 +6,8 @@ the CPU that they contain what they are used for here.  The seeded scenes take t
 device; the reference reads that record back and restates everything after it.
 
 Sizes: 1x1 and 3x1 (no plane: fewer than three candidates), 24x32 (H*W a multiple of 4: the vector-load path, one
-block), 61x83 (odd: the scalar path, two blocks), 224x224 and 480x640; grids 8, 64, 256, 512.
+block), 61x83 (odd: the scalar path, two blocks), 224x224 and 480x640; grids 8, 64, 256, 512, and 40 (a second strip of
+the column pass with 8 of its 32 columns).
 
 Every GPU test runs under a watchdog (faulthandler.dump_traceback_later(..., exit=True)): a hang ends the process instead
 of letting later tests start more GPU work; nothing is retried."""
@@ -94,6 +95,17 @@ def test_tabletop_scenes_match_reference(device, H, W):
         assert int(want["frame"][13]) == (1 if H * W >= 64 else 0)
         check_frame(host(res, 0), want, (H, W, seed, p))
         assert int(res.outside[0]) == want["counts"][0]
+
+
+def test_partial_strip_of_the_column_pass_matches_reference(device):
+    """G = 40: the column pass's second strip holds 8 of its 32 columns and a row segment 5 rows; the obstacles of those
+    columns and a column distance longer than a segment are asserted in tests/test_placement_host.py."""
+    p, qs, plane = (40, 10, 10, 10, 1, 0), [(4, 0, 0, R.WIDEST)], R.true_plane()
+    lab, xyz = scene(61, 83, 1)
+    dl, dx = to_dev(device, lab, xyz)
+    res = placement.free_space(dl, dx, tuple(plane[k] for k in ("normal", "d", "centroid", "u", "v")), **kwargs(p, qs))
+    assert res.state.shape == (1, 40, 40) and res.answers.shape == (1, 1, 4)
+    check_frame(host(res, 0), R.free_space(lab, xyz, plane, *p, qs), "G = 40")
 
 
 @pytest.mark.parametrize("name", list(R.ENGINEERED))

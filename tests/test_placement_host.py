@@ -149,3 +149,13 @@ def test_seeded_scenes_contain_what_they_are_used_for():
         G, cell, h_obs, tau, min_pts, ub = PARAMS[k]
         rr = R.free_space(*scene(H, W, 2), plane, G, cell, h_obs, tau, min_pts, ub)
         assert all((rr["state"] == s).any() for s in (0, 1, 2)), (H, W, G)
+
+
+def test_grid_of_40_has_obstacles_and_a_segment_carry_in_its_partial_strip():
+    """What tests/test_placement_gpu.py's G = 40 case is there for: columns 32..39 are the column pass's second strip, and
+    a distance along a column above G / 8 rows crosses from one row segment into the next."""
+    G = 40
+    r = R.free_space(*scene(61, 83, 1), R.true_plane(), G, 10, 10, 10, 1, 0, [(4, 0, 0, R.WIDEST)])
+    blocking = r["state"] == 2                                                      # unknown_blocks = 0
+    assert blocking[:, 32:].any() and R.column_distance(blocking)[:, 32:].max() > G // 8
+    assert r["answers"][0, 3] == 1

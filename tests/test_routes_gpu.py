@@ -111,6 +111,14 @@ def test_random_grids_match_reference(device, G):
             assert want["info"][:, 1].sum() >= 4 and want["info"][:, 5].max() > 100
 
 
+def test_partial_ballot_word_of_the_runs_matches_reference(device):
+    """G = 72: a row of the run table is one ballot word of 64 cells and one of 8; that queries reach their targets on this
+    grid is asserted in tests/test_routes_host.py."""
+    st, ow = random_grid(72, 1)
+    queries = R.random_queries(72, 1, st, ow)
+    check(run(device, st, ow, queries, 1, 256), 0, R.routes(st, ow, queries, 1, 256), "G = 72")
+
+
 def test_largest_disc_on_the_largest_grid(device):
     st, ow = R.big_grid()
     queries = [R.record(4096, (100, 100), (400, 100)), R.record(4096, (100, 100), (380, 440), ignore=9)]

@@ -187,6 +187,14 @@ def test_generated_grids_contain_what_they_are_used_for():
     assert pas[100, 100] and not pas[400, 100] and pas.sum() == 94898       # the target is too near the lone obstacle: a closest approach
 
 
+def test_grid_of_72_has_queries_that_reach_their_targets():
+    """What tests/test_routes_gpu.py's G = 72 case is there for: a second, partial ballot word per row of the run table."""
+    st, ow = R.random_grid(72, 1)
+    qs = R.random_queries(72, 1, st, ow)
+    R.check_params(72, qs, 1, 256)
+    assert R.routes(st, ow, qs, 1, 256)["info"][:, 1].sum() >= 1
+
+
 def test_query_conversions():
     assert routes.query(0.04, (120, 40), (60, 200), 10) == (25, 120, 40, 60, 200, 0, 0, 0)       # ceil(40 / 10) + 1 = 5
     assert routes.query(0.04, (1, 2), None, 10, ignore=7) == (25, 1, 2, -1, -1, 7, 0, 0)

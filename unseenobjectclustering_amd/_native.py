@@ -333,6 +333,12 @@ def check(rc: int, what: str):
         raise NativeError(f"{what} failed (rc={rc}): {msg}")
 
 
+def on_gpu(t) -> bool:
+    """True for a torch tensor on a GPU: what every entry point without a CPU fallback asks of its inputs."""
+    import torch
+    return isinstance(t, torch.Tensor) and t.device.type == "cuda"
+
+
 def ptr(t):
     """Device (or host) pointer of a torch tensor as c_void_p; None -> NULL."""
     if t is None:

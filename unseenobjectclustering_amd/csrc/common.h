@@ -106,5 +106,21 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += dpp_f<0x140>(v);
   return v;
 }
+// Integer reductions over the 64 lanes by shuffles; every lane must take part and ends with the result.
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, __shfl_xor(v, sft));
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, (unsigned long long)__shfl_xor((long long)v, sft));
+  return v;
+}
 
 }  // namespace uoc

@@ -5,7 +5,7 @@
 // queries.  Integers only.
 //
 // Four memsets (the top words and the accumulators in the workspace, d_pts, d_near, d_info) and five launches:
-//   point_kernel<.., 1>  grid (pixel chunks of CHUNK, frames), 4 waves; a wave owns SUB consecutive pixels.  A lane owns 4
+//   point_kernel<.., 1>  grid (pixel chunks of PIX_CHUNK, frames), 4 waves; a wave owns PIX_SUB consecutive pixels.  A lane owns 4
 //                   consecutive pixels per turn (one int4 and three float4 loads) when H*W is a multiple of 4 and the
 //                   pointers are 16-byte aligned, else one pixel.  A kept point is (cell, word), word = (key << 7) | id.
 //                   Per DISTINCT cell of the wave's 256 (64) pixels: ballot + popcount for the count, shuffles for the
@@ -28,135 +28,37 @@
 // part of the key), so no result depends on the order in which lanes, waves or blocks arrive.  Nothing of frame b
 // depends on the other frames of the batch.
 //
+// The frame record, step P, the pixel sweep, the merge of equal cells (wave_distinct), the segment scan of the column
+// pass, the row minimum and the widest key are grid.h's: the definitions placement.hip uses.
+//
 // Key of "widest" (0: no candidate).  dist2 <= (G/2)^2 = 2^16, idx = i*G + j < 2^18:
 //   ((dist2 + 1) << 18) | (0x3FFFF - idx)
-#include "common.h"
+#include "grid.h"
 #include "prof.h"
-
-#include <limits.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;             // ids 0..127; 0 is the table and whatever is unlabelled
-constexpr int WAVES = 4;
-constexpr int SUB = 1024;           // pixels per wave
-constexpr int CHUNK = WAVES * SUB;  // pixels per block
-constexpr int SCALE = 16384;        // S
-constexpr int MAX_G = 512;
 constexpr int MAX_Q = UOC_ELEV_MAX_QUERIES;
-constexpr int NFR = 16;             // int64 words of a frame record
-constexpr int STRIP = 32;           // columns per block of the column pass
-constexpr int SEGS = 8;             // row segments per column: STRIP * SEGS threads
-constexpr int ROW_THREADS = 256;
-constexpr int IDX_MASK = 0x3FFFF;
 constexpr int KEY_BIAS = 1024;      // key = hq + 1024 >= 24: a word of 0 means "no point"
 constexpr int HQ_MAX = 32767;
 
-static_assert(MAX_G * MAX_G <= IDX_MASK + 1, "a cell index must fit the key's low 18 bits");
-static_assert((MAX_G / 2) * (MAX_G / 2) < (1 << 17), "dist2 must fit 17 bits of the key");
-static_assert(STRIP * SEGS == 256 && MAX_G % SEGS == 0, "column pass layout");
 static_assert(((HQ_MAX + KEY_BIAS) << 7 | (NL - 1)) > 0, "a word is a positive int");
-
-struct Frame {
-  int N[3], U[3], V[3], qc[3];
-  long long D;
-  int found;
-};
 
 struct Queries {
   int v[MAX_Q][4];  // need2, id, hmin_mm, hmax_mm
 };
 
-__device__ __forceinline__ bool within(long long v, long long lim) { return v >= -lim && v <= lim; }
-
-// Step F.  Wave-uniform: every thread reads the same record.
-__device__ __forceinline__ Frame load_frame(const long long *__restrict__ F) {
-  Frame f;
-  bool ok = F[13] == 1 && within(F[3], 1ll << 34);
-  for (int k = 0; k < 3; ++k)
-    ok = ok && within(F[k], 32768) && within(F[4 + k], 32768) && within(F[7 + k], 32768) && within(F[10 + k], 32767);
-  for (int k = 0; k < 3; ++k) {
-    f.N[k] = ok ? (int)F[k] : 0;
-    f.U[k] = ok ? (int)F[4 + k] : 0;
-    f.V[k] = ok ? (int)F[7 + k] : 0;
-    f.qc[k] = ok ? (int)F[10 + k] : 0;
-  }
-  f.D = ok ? F[3] : 0;
-  f.found = ok ? 1 : 0;
-  return f;
-}
-
-__device__ __forceinline__ long long floor_div(long long a, long long c) {  // c > 0
-  const long long q = a / c;
-  return q - ((a - q * c) < 0 ? 1 : 0);
-}
-
-// Step P of one pixel: cell (-1: not kept) and word; returns true when the point lies outside the grid.
+// One pixel after step P (grid.h): cell (-1: not kept) and word; returns true when the point lies outside the grid.
 __device__ __forceinline__ bool project(const Frame &f, int cell_div, int t_low, int G, int l, float x, float y, float z,
                                         int &cell, int &word) {
   cell = -1;
   word = 0;
-  if (!(isfinite(x) && isfinite(y) && isfinite(z) && z > 0.f)) return false;
-  const float rx = rintf(x * 1000.0f), ry = rintf(y * 1000.0f), rz = rintf(z * 1000.0f);
-  if (!(fabsf(rx) <= 32767.f && fabsf(ry) <= 32767.f && fabsf(rz) <= 32767.f)) return false;
-  const int qx = (int)rx, qy = (int)ry, qz = (int)rz;
-  const int dx = qx - f.qc[0], dy = qy - f.qc[1], dz = qz - f.qc[2];
-  const long long A = (long long)f.U[0] * dx + (long long)f.U[1] * dy + (long long)f.U[2] * dz;
-  const long long Bv = (long long)f.V[0] * dx + (long long)f.V[1] * dy + (long long)f.V[2] * dz;
-  const long long i = floor_div(A, cell_div) + G / 2, j = floor_div(Bv, cell_div) + G / 2;
-  if ((unsigned long long)i >= (unsigned long long)G || (unsigned long long)j >= (unsigned long long)G) return true;
-  const long long T = (long long)f.N[0] * qx + (long long)f.N[1] * qy + (long long)f.N[2] * qz + f.D;
-  if (T < t_low) return false;
-  const long long hq = min(T >> 14, (long long)HQ_MAX);  // arithmetic shift: a floor; hq >= -tau_mm >= -1000
-  const int id = ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0;
-  cell = (int)i * G + (int)j;
-  word = (((int)hq + KEY_BIAS) << 7) | id;
-  return false;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, __shfl_xor(v, sft));
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, (unsigned long long)__shfl_xor((long long)v, sft));
-  return v;
-}
-
-// Every distinct cell >= 0 among the K slots of the wave's lanes is handed to `emit` once, by one lane, with the number
-// of (lane, slot) places that hold it and the largest of their values w.  Every lane of the wave must call this.
-template <int K, bool MAXW, typename Emit>
-__device__ __forceinline__ void wave_distinct(int (&e)[K], const int (&w)[K], int lane, Emit emit) {
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    unsigned long long rem = __ballot(e[j] >= 0);
-    while (rem) {
-      const int first = __ffsll((long long)rem) - 1;
-      const int c = __builtin_amdgcn_readlane(e[j], first);
-      int total = 0, mine = 0;
-#pragma unroll
-      for (int k = j; k < K; ++k) {
-        const bool hit = e[k] == c;
-        const unsigned long long m = __ballot(hit);
-        total += __popcll(m);
-        if (k == j) rem &= ~m;
-        if (hit) {
-          e[k] = -1;
-          mine = max(mine, w[k]);
-        }
-      }
-      if constexpr (MAXW) mine = wave_max(mine);
-      if (lane == first) emit(c, total, mine);
-    }
-  }
+  return project_point(f, cell_div, t_low, G, x, y, z, [&](int i, int j, long long T) {
+    const long long hq = min(T >> 14, (long long)HQ_MAX);  // arithmetic shift: a floor; hq >= -tau_mm >= -1000
+    cell = i * G + j;
+    word = (((int)hq + KEY_BIAS) << 7) | label_id(l);
+  });
 }
 
 // ---- 1, 2. the point passes ---------------------------------------------------------------------------------------------
@@ -166,49 +68,20 @@ __global__ __launch_bounds__(256) void point_kernel(const int *__restrict__ labe
                                                     int t_low, int step_mm, int *__restrict__ top, int *__restrict__ pts,
                                                     int *__restrict__ near, int *__restrict__ info) {
   constexpr int K = VEC ? 4 : 1;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = blockIdx.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, b = blockIdx.y;
   const Frame f = load_frame(frame + (size_t)b * NFR);
   if (!f.found) return;  // uniform per frame
-  const int *L = labels + (size_t)b * n;
-  const float *X = xyz + (size_t)b * 3 * n;
   const size_t cells = (size_t)G * G;
   int *TOP = top + (size_t)b * cells, *PTS = pts + (size_t)b * cells, *NEAR = near + (size_t)b * cells;
-  const long long p0 = (long long)c * CHUNK + (long long)w * SUB;
   int outside = 0;
-  for (int it = 0; it < SUB / (64 * K); ++it) {
-    const long long base = p0 + (long long)it * 64 * K;
-    if (base >= n) break;  // uniform per wave
-    const long long p = base + (long long)lane * K;
+  Pixels<K> px;
+  for (PixelSweep<VEC> sweep(labels + (size_t)b * n, xyz + (size_t)b * 3 * n, n); sweep.load(px);) {
     int e[K], wd[K];
     bool out[K];
-    if constexpr (VEC) {
-      int4 l4 = make_int4(0, 0, 0, 0);
-      float4 x4 = make_float4(0.f, 0.f, 0.f, 0.f), y4 = x4, z4 = x4;  // z = 0: no point
-      if (p < n) {  // n is a multiple of 4: the four pixels are inside together
-        l4 = *reinterpret_cast<const int4 *>(L + p);
-        x4 = *reinterpret_cast<const float4 *>(X + p);
-        y4 = *reinterpret_cast<const float4 *>(X + n + p);
-        z4 = *reinterpret_cast<const float4 *>(X + 2 * n + p);
-      }
-      out[0] = project(f, cell_div, t_low, G, l4.x, x4.x, y4.x, z4.x, e[0], wd[0]);
-      out[1] = project(f, cell_div, t_low, G, l4.y, x4.y, y4.y, z4.y, e[1], wd[1]);
-      out[2] = project(f, cell_div, t_low, G, l4.z, x4.z, y4.z, z4.z, e[2], wd[2]);
-      out[3] = project(f, cell_div, t_low, G, l4.w, x4.w, y4.w, z4.w, e[3], wd[3]);
-    } else {
-      int l = 0;
-      float x = 0.f, y = 0.f, z = 0.f;
-      if (p < n) {
-        l = L[p];
-        x = X[p];
-        y = X[n + p];
-        z = X[2 * n + p];
-      }
-      out[0] = project(f, cell_div, t_low, G, l, x, y, z, e[0], wd[0]);
-    }
-    if constexpr (PASS == 1) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) outside += __popcll(__ballot(out[k]));
+    for (int k = 0; k < K; ++k) out[k] = project(f, cell_div, t_low, G, px.l[k], px.x[k], px.y[k], px.z[k], e[k], wd[k]);
+    if constexpr (PASS == 1) {
+      outside += wave_count_set(out);
       wave_distinct<K, true>(e, wd, lane, [&](int cell, int total, int word) {
         atomicAdd(&PTS[cell], total);
         atomicMax(&TOP[cell], word);
@@ -230,7 +103,6 @@ __global__ __launch_bounds__(STRIP *SEGS) void cell_kernel(const int *__restrict
                                                            int *__restrict__ owner, int *__restrict__ g_out,
                                                            int *__restrict__ info) {
   __shared__ unsigned short s[MAX_G][STRIP];  // bit 15: blocking; after the upward scan the low bits hold the distance up
-  __shared__ int s_first[SEGS][STRIP], s_last[SEGS][STRIP];
   __shared__ int s_cnt[2];
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y, j0 = blockIdx.x * STRIP;
   const bool found = load_frame(frame + (size_t)b * NFR).found != 0;
@@ -269,42 +141,7 @@ __global__ __launch_bounds__(STRIP *SEGS) void cell_kernel(const int *__restrict
   __syncthreads();
   if (tid < 2 && s_cnt[tid]) atomicAdd(&info[(size_t)b * 4 + 2 + tid], s_cnt[tid]);
   if (blockIdx.x == 0 && tid == 2) info[(size_t)b * 4] = found ? 1 : 0;
-  const int jj = tid % STRIP, seg = tid / STRIP, rows = G / SEGS, r0 = seg * rows, r1 = r0 + rows;
-  const bool col = j0 + jj < G;
-  {  // the first and the last blocking row of the segment
-    int first = INT_MAX, last = -1;
-    if (col)
-      for (int i = r0; i < r1; ++i)
-        if (s[i][jj] & 0x8000u) {
-          if (first == INT_MAX) first = i;
-          last = i;
-        }
-    s_first[seg][jj] = first;
-    s_last[seg][jj] = last;
-  }
-  __syncthreads();
-  if (!col) return;
-  int up = -1, down = G;  // the virtual blocking cells
-  for (int k = seg - 1; k >= 0; --k)
-    if (s_last[k][jj] >= 0) {
-      up = s_last[k][jj];
-      break;
-    }
-  for (int k = seg + 1; k < SEGS; ++k)
-    if (s_first[k][jj] != INT_MAX) {
-      down = s_first[k][jj];
-      break;
-    }
-  for (int i = r0; i < r1; ++i) {  // distance up, at most 512: bits 0..9
-    const unsigned v = s[i][jj];
-    if (v & 0x8000u) up = i;
-    s[i][jj] = (unsigned short)((v & 0x8000u) | (unsigned)(i - up));
-  }
-  for (int i = r1 - 1; i >= r0; --i) {
-    const unsigned v = s[i][jj];
-    if (v & 0x8000u) down = i;
-    g_out[off + (size_t)i * G + j0 + jj] = min((int)(v & 0x7FFFu), down - i);
-  }
+  column_scan(s, G, j0, g_out + off);
 }
 
 // ---- 4. the row pass, the per-id table and the queries -----------------------------------------------------------------
@@ -323,10 +160,7 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
   __shared__ unsigned long long s_key[NL];
   const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x, b = blockIdx.y;
   const size_t off = ((size_t)b * G + i) * G;
-  for (int j = tid; j < G; j += ROW_THREADS) {
-    const int g = dist2[off + j];
-    s_g2[j] = g * g;
-  }
+  row_fill_g2(s_g2, dist2 + off, G);
   if (tid < MAX_Q) s_qkey[tid] = 0ull;
   if (tid < NL) {
     s_cells[tid] = s_level[tid] = s_emax[tid] = s_sum[tid] = 0;
@@ -341,15 +175,7 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
     const bool valid = j < G;
     int best = 0, code = -1, el = 0;
     if (valid) {
-      best = min((j + 1) * (j + 1), (G - j) * (G - j));  // the virtual columns -1 and G
-      for (int k = 0; k < G; k += 4) {                   // G is a multiple of 8
-        const int4 v = *reinterpret_cast<const int4 *>(&s_g2[k]);
-        const int d = j - k;
-        best = min(best, d * d + v.x);
-        best = min(best, (d - 1) * (d - 1) + v.y);
-        best = min(best, (d - 2) * (d - 2) + v.z);
-        best = min(best, (d - 3) * (d - 3) + v.w);
-      }
+      best = row_min_dist2(s_g2, j, G);
       dist2[off + j] = best;
       if (near[off + j] >= min_pts) {  // solid
         code = owner[off + j];
@@ -357,7 +183,7 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
       }
     }
     const bool lvl = code >= 0 && best > 0;  // not blocking: level
-    const unsigned long long wide = lvl ? (((unsigned long long)(best + 1) << 18) | (unsigned long long)(IDX_MASK - (i * G + j))) : 0ull;
+    const unsigned long long wide = lvl ? widest_key(best, i * G + j) : 0ull;
     const int own = code;
     unsigned long long rem = __ballot(code >= 0);
     while (rem) {  // per distinct owner of the wave
@@ -425,10 +251,10 @@ __global__ __launch_bounds__(NL) void answer_kernel(Acc acc, const int *__restri
   int row[8] = {cells, level, -1, -1, 0, 0, cells ? acc.emax[r] - KEY_BIAS : 0, 0};
   if (level) {
     const unsigned long long k64 = acc.key[r];
-    const int idx = IDX_MASK - (int)(k64 & (unsigned long long)IDX_MASK);
+    const int idx = key_cell(k64);
     row[2] = idx / G;
     row[3] = idx % G;
-    row[4] = (int)(k64 >> 18) - 1;
+    row[4] = key_dist2(k64);
     row[5] = elev[(size_t)b * G * G + idx];
     row[7] = (int)floor_div((long long)acc.sum[r], level);
   }
@@ -439,10 +265,10 @@ __global__ __launch_bounds__(NL) void answer_kernel(Acc acc, const int *__restri
     const unsigned long long k64 = acc.qkey[(size_t)b * MAX_Q + a];
     int4 ans = make_int4(-1, -1, 0, 0);
     if (k64) {
-      const int idx = IDX_MASK - (int)(k64 & (unsigned long long)IDX_MASK);
+      const int idx = key_cell(k64);
       ans.x = idx / G;
       ans.y = idx % G;
-      ans.z = (int)(k64 >> 18) - 1;
+      ans.z = key_dist2(k64);
       ans.w = ans.z >= qs.v[a][0];
     }
     int *A = answers + ((size_t)b * Q + a) * 4;
@@ -453,9 +279,7 @@ __global__ __launch_bounds__(NL) void answer_kernel(Acc acc, const int *__restri
   }
 }
 
-bool shape_ok(int B, int H, int W, int G) {
-  return B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX && G >= 8 && G <= MAX_G && G % 8 == 0;
-}
+bool shape_ok(int B, int H, int W, int G) { return image_ok(B, H, W) && grid_ok(G); }
 
 struct Ws {
   int *top;  // [B][G][G]
@@ -511,9 +335,9 @@ int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_
                   void *d_ws, size_t ws_bytes, void *stream) {
   UOC_REQUIRE(d_labels && d_xyz && d_frame && d_elev && d_owner && d_pts && d_near && d_dist2 && d_tops && d_info && d_ws,
               "uoc_elevation: null labels / xyz / frame / elev / owner / pts / near / dist2 / tops / info / workspace");
-  UOC_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX,
+  UOC_REQUIRE(image_ok(B, H, W),
               "uoc_elevation: bad shape B=%d H=%d W=%d (B in 1..65535, H*W below 2^31)", B, H, W);
-  UOC_REQUIRE(G >= 8 && G <= MAX_G && G % 8 == 0, "uoc_elevation: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
+  UOC_REQUIRE(grid_ok(G), "uoc_elevation: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
   UOC_REQUIRE(cell_mm >= 1 && cell_mm <= 1000, "uoc_elevation: cell_mm = %d outside [1, 1000]", cell_mm);
   UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_elevation: tau_mm = %d outside [1, 1000]", tau_mm);
   UOC_REQUIRE(step_mm >= 1 && step_mm <= 1000, "uoc_elevation: step_mm = %d outside [1, 1000]", step_mm);
@@ -531,9 +355,9 @@ int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_
   }
   const Ws w = carve(d_ws, B, G);
   UOC_REQUIRE(ws_bytes >= w.total, "uoc_elevation: workspace %zu < %zu bytes", ws_bytes, w.total);
-  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_elevation: workspace not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_ws), "uoc_elevation: workspace not 16-byte aligned");
   const long long n = (long long)H * W;
-  const int nch = (int)((n + CHUNK - 1) / CHUNK);
+  const int nch = (int)((n + PIX_CHUNK - 1) / PIX_CHUNK);
   const size_t cells = (size_t)B * G * G;
   const bool vec = n % 4 == 0 && (((uintptr_t)d_labels | (uintptr_t)d_xyz) & 15) == 0;
   const long long *frame = (const long long *)d_frame;

@@ -8,7 +8,7 @@
 //   span_kernel    one thread per (rectangle f, direction k, mask row di): it scans dj over the window and writes the
 //                  row's span (dj_lo, dj_hi) as two signed bytes, (1, 0) for an empty row.  The mask is an intersection of
 //                  half planes, so a row of it is one span.  Independent of the frame: once per call.
-//   run_kernel     grid (rows, tables, frames), 4 waves.  A table belongs to one value of `ignore`; rectangles with the
+//   run_kernel     (grid.h) grid (rows, tables, frames), 4 waves.  A table belongs to one value of `ignore`; rectangles with the
 //                  same value share it.  The row's FREE bits by ballot into LDS (8 words of 64 at G = 512), then per cell
 //                  the length of the run of FREE cells that ends there, by counting leading ones: 16-bit words.  A frame
 //                  without a plane gets a table of zeros, which makes everything downstream of it zero.
@@ -27,33 +27,22 @@
 //
 // Determinism: integer adds and maxima commute and the key is a strict total order over (cell, k), so no result depends
 // on the order in which lanes, waves or blocks arrive.  Nothing of frame b depends on the other frames of the batch.
-#include "common.h"
+#include "grid.h"
 #include "prof.h"
-
-#include <limits.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;  // ids 0..127
-constexpr int SCALE = 16384;  // S
 constexpr int UNIT = 256;     // a half extent counts 1/256 cell; S / UNIT = 64
-constexpr int MAX_G = 512;
 constexpr int MAX_A = 32, MAX_F = UOC_FOOT_MAX_RECTS, MAX_HALF = UOC_FOOT_MAX_HALF;
 constexpr int MAX_R = 64;                  // (256 * 64)^2 = MAX_HALF^2
 constexpr int MAX_ROWS = 2 * MAX_R + 3;    // the window is |di| <= R + 1: 131 rows
-constexpr int NFR = 16;                    // int64 words of a frame record
 constexpr int THREADS = 256;
 constexpr int CELLS = 256, KGROUPS = 4, FIT_THREADS = CELLS * KGROUPS, BATCH = 8;  // fit_kernel: cells per block, groups of directions
-constexpr int IDX_MASK = 0x3FFFF;
-constexpr int MAX_ANCHOR = 4096;
 constexpr int DIST_CAP = 65536;
 
-static_assert(MAX_G * MAX_G <= IDX_MASK + 1, "a cell index must fit 18 bits of the key");
 static_assert((long long)(MAX_R + 1) * SCALE * 2 < (1 << 22), "a projection stays below 2^22");
-static_assert(2ll * (MAX_G + MAX_ANCHOR) * (MAX_G + MAX_ANCHOR) < (1ll << 26), "da must stay below 2^26");
-static_assert(MAX_R + 1 <= 127 && MAX_G <= 65535, "a span is two signed bytes, a run one 16-bit word");
-static_assert(MAX_G / 64 <= 8, "a row is at most 8 ballot words");
+static_assert(MAX_R + 1 <= 127, "a span is two signed bytes");
 
 struct Dirs {
   int c[MAX_A][2];  // (Cx, Cy)
@@ -64,7 +53,7 @@ struct Rects {
 struct Plan {
   int R[MAX_F];       // R_f
   int table[MAX_F];   // the run table of rectangle f
-  int ignore[MAX_F];  // the `ignore` of table t
+  RunIgnore<MAX_F> ignore;  // the `ignore` of table t
 };
 
 // ---- 1. the spans of the masks ----------------------------------------------------------------------------------------
@@ -89,61 +78,11 @@ __global__ __launch_bounds__(THREADS) void span_kernel(Dirs d, Rects r, Plan p, 
   spans[2 * t + 1] = (signed char)hi;
 }
 
-// ---- 2. the runs of FREE cells ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(THREADS) void run_kernel(const int *__restrict__ state, const int *__restrict__ owner,
-                                                      const long long *__restrict__ frame, int G, int NT, Plan p,
-                                                      int unknown_blocks, unsigned short *__restrict__ runs) {
-  __shared__ unsigned long long s_bits[MAX_G / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blockIdx.x, t = blockIdx.y, b = blockIdx.z;
-  const bool found = frame == nullptr || frame[(size_t)b * NFR + 13] == 1;  // uniform per frame
-  const int ignore = p.ignore[t];
-  const size_t in = ((size_t)b * G + i) * G, out = (((size_t)b * NT + t) * G + i) * G;
-  for (int jb = 0; jb < G; jb += THREADS) {  // uniform: every lane takes part in the ballot
-    const int j = jb + tid;
-    bool fr = false;
-    if (found && j < G) {
-      const int st = state[in + j];
-      if (st == 1) {
-        fr = true;
-      } else if (st == 2) {
-        const int o = owner[in + j];
-        fr = (unsigned)(o - 1) < (unsigned)(NL - 1) ? (o == ignore) : !unknown_blocks;  // ignore == 0 matches no id
-      } else {
-        fr = !unknown_blocks;  // state 0 and every state outside 0..2: unknown
-      }
-    }
-    const unsigned long long m = __ballot(fr);
-    if (lane == 0 && jb + wave * 64 < G) s_bits[(jb >> 6) + wave] = m;
-  }
-  __syncthreads();
-  for (int j = tid; j < G; j += THREADS) {
-    int w = j >> 6, len = 0;
-    unsigned long long x = ~s_bits[w] << (63 - (j & 63));  // bit 63 is cell j; a set bit is a cell that is not FREE
-    while (true) {
-      if (x) {
-        len += __clzll((long long)x);
-        break;
-      }
-      len += (w == (j >> 6)) ? (j & 63) + 1 : 64;
-      if (--w < 0) break;
-      x = ~s_bits[w];
-    }
-    runs[out + j] = (unsigned short)len;
-  }
-}
-
 // ---- 3. the fit -------------------------------------------------------------------------------------------------------
 struct Acc {
   unsigned long long *key;  // [B][F]
   int *cells;               // [B][F]
 };
-
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, (unsigned long long)__shfl_xor((long long)v, sft));
-  return v;
-}
 
 __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(const unsigned short *__restrict__ runs, const int *__restrict__ dist2,
                                                           const signed char *__restrict__ spans, int G, int A, int F, int NT,
@@ -215,7 +154,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(const unsigned short *
     if (idx < cells) fits[((size_t)b * F + f) * cells + idx] = (int)word;
     if (word) {
       const int k = __ffs((int)word) - 1;  // the lowest direction carries the cell's largest key
-      const unsigned long long low = ((unsigned long long)(IDX_MASK - idx) << 5) | (unsigned long long)(31 - k);
+      const unsigned long long low = (cell_key(idx) << 5) | (unsigned long long)(31 - k);
       if (r.v[f][3] == UOC_FOOT_NEAREST) {
         const int ei = i - r.v[f][4], ej = j - r.v[f][5];
         key = ((unsigned long long)((1 << 27) - 1 - (ei * ei + ej * ej)) << 23) | low;
@@ -255,7 +194,7 @@ __global__ __launch_bounds__(64) void answer_kernel(Acc acc, const int *__restri
   const unsigned long long key = acc.key[t];
   int row[8] = {0, -1, -1, -1, 0, 0, 0, 0};
   if (key) {
-    const int idx = IDX_MASK - (int)((key >> 5) & (unsigned long long)IDX_MASK);
+    const int idx = key_cell(key >> 5);
     const int i = idx / G, j = idx - i * G, ei = i - r.v[f][4], ej = j - r.v[f][5];
     int poses = 0;
     for (int k = 0; k < A; ++k) poses += count[(size_t)t * 32 + k];
@@ -274,7 +213,7 @@ __global__ __launch_bounds__(64) void answer_kernel(Acc acc, const int *__restri
 }
 
 bool shape_ok(int B, int G, int A, int F) {
-  return B > 0 && B <= 65535 && G >= 8 && G <= MAX_G && G % 8 == 0 && A >= 1 && A <= MAX_A && F >= 1 && F <= MAX_F;
+  return batch_ok(B) && grid_ok(G) && A >= 1 && A <= MAX_A && F >= 1 && F <= MAX_F;
 }
 
 struct Ws {
@@ -319,8 +258,8 @@ int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t 
                   int32_t *d_count, int32_t *d_best, void *d_ws, size_t ws_bytes, void *stream) {
   UOC_REQUIRE(d_state && d_owner && d_dist2 && h_dirs && h_rects && d_fits && d_count && d_best && d_ws,
               "uoc_footprint: null state / owner / dist2 / dirs / rects / fits / count / best / workspace");
-  UOC_REQUIRE(B > 0 && B <= 65535, "uoc_footprint: bad shape B=%d (B in 1..65535)", B);
-  UOC_REQUIRE(G >= 8 && G <= MAX_G && G % 8 == 0, "uoc_footprint: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
+  UOC_REQUIRE(batch_ok(B), "uoc_footprint: bad shape B=%d (B in 1..65535)", B);
+  UOC_REQUIRE(grid_ok(G), "uoc_footprint: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
   UOC_REQUIRE(A >= 1 && A <= MAX_A, "uoc_footprint: %d directions outside [1, %d]", A, MAX_A);
   UOC_REQUIRE(F >= 1 && F <= MAX_F, "uoc_footprint: %d rectangles outside [1, %d]", F, MAX_F);
   UOC_REQUIRE(unknown_blocks == 0 || unknown_blocks == 1, "uoc_footprint: unknown_blocks = %d is neither 0 nor 1", unknown_blocks);
@@ -335,7 +274,7 @@ int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t 
   int NT = 0;
   for (int f = 0; f < MAX_F; ++f) {
     for (int k = 0; k < 8; ++k) r.v[f][k] = f < F ? h_rects[f * 8 + k] : 0;
-    p.R[f] = p.table[f] = p.ignore[f] = 0;
+    p.R[f] = p.table[f] = p.ignore.v[f] = 0;
   }
   for (int f = 0; f < F; ++f) {
     const int *v = r.v[f];
@@ -352,13 +291,13 @@ int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t 
     while ((long long)(UNIT * R) * (UNIT * R) < q) ++R;  // at most 64
     p.R[f] = R;
     int t = 0;
-    while (t < NT && p.ignore[t] != v[2]) ++t;
-    if (t == NT) p.ignore[NT++] = v[2];
+    while (t < NT && p.ignore.v[t] != v[2]) ++t;
+    if (t == NT) p.ignore.v[NT++] = v[2];
     p.table[f] = t;
   }
   const Ws w = carve(d_ws, B, G, A, F);
   UOC_REQUIRE(ws_bytes >= w.total, "uoc_footprint: workspace %zu < %zu bytes", ws_bytes, w.total);
-  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_footprint: workspace not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_ws), "uoc_footprint: workspace not 16-byte aligned");
   const int cells = G * G, nspan = F * A * MAX_ROWS;
   hipStream_t st = (hipStream_t)stream;
   {
@@ -366,8 +305,8 @@ int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t 
     UOC_HIP_CHECK(hipMemsetAsync((char *)d_ws + w.acc_at, 0, w.acc_bytes, st));
     UOC_HIP_CHECK(hipMemsetAsync(d_count, 0, (size_t)B * F * 32 * sizeof(int32_t), st));
     hipLaunchKernelGGL(span_kernel, dim3((nspan + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d, r, p, A, F, w.spans);
-    hipLaunchKernelGGL(run_kernel, dim3(G, NT, B), dim3(THREADS), 0, st, d_state, d_owner, (const long long *)d_frame, G, NT, p,
-                       unknown_blocks, w.runs);
+    hipLaunchKernelGGL(run_kernel<MAX_F>, dim3(G, NT, B), dim3(RUN_THREADS), 0, st, d_state, d_owner, (const long long *)d_frame, G,
+                       NT, p.ignore, unknown_blocks, w.runs);
   }
   {
     ProfScope prof(KC_FOOT_FIT, st, 0.0, (double)B * F * cells * 10.0);

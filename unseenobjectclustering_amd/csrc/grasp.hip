@@ -5,8 +5,8 @@
 //
 // One memset (the moments in the workspace) and two launches:
 //   moments_kernel    grid (chunks of CHUNK cells, frames), 4 waves.  n_a, sum i, sum j per id: the wave adds every
-//                     DISTINCT id of its 64 cells once (ballot, popcount and two shuffle sums; track.hip's
-//                     wave_add_pairs) to an LDS table, the block flushes its non-zero words with integer atomics.
+//                     DISTINCT id of its 64 cells once (ballot, popcount and two wave_sums of common.h) to an LDS
+//                     table, the block flushes its non-zero words with integer atomics.
 //   candidate_kernel  grid (ids 0..127, frames), 4 waves, dynamic LDS.  Block 0 and the block of an absent id zero
 //                     their rows and leave.  The others loop over the directions in chunks of KC that fit the class table:
 //                       pass 1  a wave owns a line (k, l), its lanes sweep t: the class of the sample, one byte, to LDS;
@@ -15,20 +15,17 @@
 //                     then the key maximum per wave by shuffles, per block by one LDS atomicMax; the thread that holds the
 //                     winning key writes the best record (the key is a strict total order over (k, m): one thread).
 //
+// The grid's constants and the host-side shape checks are grid.h's, the shuffle reductions common.h's.
+//
 // Determinism: integer adds and maxima commute and the key is a strict total order, so no result depends on the order in
 // which lanes, waves or blocks arrive.  Nothing of frame b depends on the other frames of the batch.
-#include "common.h"
+#include "grid.h"
 #include "prof.h"
-
-#include <limits.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;  // ids 0..127; 1..127 are objects
-constexpr int SHIFT = 14;
-constexpr int SCALE = 1 << SHIFT;  // S
-constexpr int MAX_G = 512;
+constexpr int SHIFT = 14;  // S = 1 << SHIFT
 constexpr int MAX_A = UOC_GRASP_MAX_DIRS, MAX_M = 8, MAX_W = 64, MAX_GAP = 4, MAX_F = 8, MAX_HP = 4;
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int CHUNK = 8 * THREADS;     // cells per block of the moments pass
@@ -36,7 +33,7 @@ constexpr int MOM = 4;                 // words per (frame, id) in the workspace
 constexpr int TABLE_CAP = 48 * 1024;   // bytes of class table per block
 enum : unsigned char { C_OWN = 0, C_FREE = 1, C_OTHER = 2, C_OUT = 3, C_UNKNOWN = 4 };
 
-static_assert((long long)MAX_G * MAX_G * (MAX_G - 1) < INT_MAX, "sum i of one id must fit an int32");
+static_assert(SCALE == 1 << SHIFT && (long long)MAX_G * MAX_G * (MAX_G - 1) < INT_MAX, "sum i of one id must fit an int32");
 static_assert((2 * (MAX_M + MAX_HP) + 1) * (2 * (2 * MAX_W + MAX_GAP + MAX_F) + 1) <= TABLE_CAP, "one direction must fit the class table");
 static_assert((long long)MAX_G * SCALE + (2 * MAX_W + MAX_GAP + MAX_F + MAX_M + MAX_HP) * 2ll * SCALE < INT_MAX, "X, Y must fit an int32");
 static_assert(MAX_M < 16 && MAX_W <= 256 && MAX_A <= 256, "the key's fields");
@@ -79,12 +76,7 @@ __global__ __launch_bounds__(THREADS) void moments_kernel(const int *__restrict_
       const bool hit = id == c;
       const unsigned long long m = __ballot(hit);
       rem &= ~m;
-      int si = hit ? i : 0, sj = hit ? j : 0;
-#pragma unroll
-      for (int sft = 32; sft > 0; sft >>= 1) {
-        si += __shfl_xor(si, sft);
-        sj += __shfl_xor(sj, sft);
-      }
+      const int si = wave_sum(hit ? i : 0), sj = wave_sum(hit ? j : 0);
       if (lane == first) {
         atomicAdd(&s_m[c * 3], (int)__popcll(m));
         atomicAdd(&s_m[c * 3 + 1], si);
@@ -199,6 +191,9 @@ __global__ __launch_bounds__(THREADS) void candidate_kernel(const int *__restric
   unsigned wkey = my_key;
   int wok = my_ok;
 #pragma unroll
+  // Spelled out, not common.h's helpers: the key is unsigned and wave_max is a signed reduction.  This loop is the code
+  // the kernel was measured with; wave_max on the key cast to int gave the same bits and 1.1 us more per call
+  // (profiles/grid_common.md, first session).
   for (int sft = 32; sft > 0; sft >>= 1) {
     wkey = max(wkey, (unsigned)__shfl_xor((int)wkey, sft));
     wok += __shfl_xor(wok, sft);
@@ -231,7 +226,7 @@ __global__ __launch_bounds__(THREADS) void candidate_kernel(const int *__restric
 }
 
 bool shape_ok(int B, int G, int A, int M) {
-  return B > 0 && B <= 65535 && G >= 8 && G <= MAX_G && G % 8 == 0 && A >= 1 && A <= MAX_A && M >= 0 && M <= MAX_M;
+  return batch_ok(B) && grid_ok(G) && A >= 1 && A <= MAX_A && M >= 0 && M <= MAX_M;
 }
 
 size_t ws_total(int B) { return align_up((size_t)B * NL * MOM * sizeof(int), 256); }
@@ -252,8 +247,8 @@ int uoc_grasp(const int32_t *d_state, const int32_t *d_owner, int B, int G, cons
               int gap, int F, int Hp, int unknown_blocks, int32_t *d_cand, int32_t *d_best, void *d_ws, size_t ws_bytes,
               void *stream) {
   UOC_REQUIRE(d_state && d_owner && h_dirs && d_cand && d_best && d_ws, "uoc_grasp: null state / owner / dirs / cand / best / workspace");
-  UOC_REQUIRE(B > 0 && B <= 65535, "uoc_grasp: bad shape B=%d (B in 1..65535)", B);
-  UOC_REQUIRE(G >= 8 && G <= MAX_G && G % 8 == 0, "uoc_grasp: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
+  UOC_REQUIRE(batch_ok(B), "uoc_grasp: bad shape B=%d (B in 1..65535)", B);
+  UOC_REQUIRE(grid_ok(G), "uoc_grasp: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
   UOC_REQUIRE(A >= 1 && A <= MAX_A, "uoc_grasp: %d directions outside [1, %d]", A, MAX_A);
   UOC_REQUIRE(M >= 0 && M <= MAX_M, "uoc_grasp: M = %d outside [0, %d]", M, MAX_M);
   UOC_REQUIRE(Wmax >= 1 && Wmax <= MAX_W, "uoc_grasp: Wmax = %d outside [1, %d]", Wmax, MAX_W);
@@ -269,7 +264,7 @@ int uoc_grasp(const int32_t *d_state, const int32_t *d_owner, int B, int G, cons
                 "uoc_grasp: direction %d = (%d, %d) has a component outside [-%d, %d]", k, d.c[k][0], d.c[k][1], SCALE, SCALE);
   const size_t total = ws_total(B);
   UOC_REQUIRE(ws_bytes >= total, "uoc_grasp: workspace %zu < %zu bytes", ws_bytes, total);
-  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_grasp: workspace not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_ws), "uoc_grasp: workspace not 16-byte aligned");
   Params p;
   p.G = G, p.A = A, p.M = M, p.Wmax = Wmax, p.gap = gap, p.F = F, p.Hp = Hp, p.unknown_blocks = unknown_blocks;
   p.R = 2 * Wmax;

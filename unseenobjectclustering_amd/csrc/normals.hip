@@ -16,18 +16,17 @@
 //                  words with integer atomics.  LDS: 56000 bytes, below the 64 KB that need no opt-in.
 //   faces_kernel   one block per frame, one thread per id: the accumulators and the fullest bin into a row of d_faces.
 //
+// The plane record becomes integers by grid.h's frame_from_plane, rule F of the table grid; the classes and the azimuth
+// read its N, U and V.
+//
 // Determinism: integer adds commute, the bin and the peak are maxima with an index tie-break, so no result depends on
 // the order in which lanes, waves or blocks arrive.  Nothing of frame b depends on the other frames of the batch.
-#include "common.h"
+#include "grid.h"
 #include "prof.h"
-
-#include <limits.h>
-#include <math.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;  // ids 0..127; 0 is the background
 constexpr int FW = UOC_NORMALS_FACE_WORDS;
 constexpr int MAX_A = UOC_NORMALS_MAX_DIRS;
 constexpr int TW = 32, TH = 16, THREADS = 256;
@@ -41,39 +40,18 @@ constexpr int F_PIXELS = 0, F_NORMAL = 1, F_GRAZING = 6, F_PEAK = 7, F_HIST = 8;
 static_assert(FW == F_HIST + MAX_A, "a row of faces is eight counters and the histogram");
 static_assert(THREADS == TW * TH / 2 && THREADS / 64 * 2 * 2 == TH, "a thread owns the pixels (ty, tx) and (ty + 8, tx)");
 static_assert((QR * QP + 2 * PR * PP) * 8 + NL * FW * 4 + QR * QP <= 65536, "LDS stays below 64 KB");
-static_assert(sizeof(uoc_plane) == 21 * 4, "uoc_plane is 21 words");
 static_assert((NL * FW) % 4 == 0, "the accumulators are cleared and flushed as int4");
 
 struct Dirs {
   int v[MAX_A][2];
 };
 
-struct PlaneQ {
-  int P[3], U[3], V[3];
-  int found;
-};
-
-__device__ __forceinline__ bool unit_ok(float a) { return isfinite(a) && fabsf(a) <= 2.0f; }
-
-// Rule F of uoc_placement, restated (placement.hip: make_frame).  Wave-uniform: every thread reads the same record.
-__device__ __forceinline__ PlaneQ make_plane(const uoc_plane *__restrict__ planes, int b) {
-  PlaneQ f;
-  f.found = 0;
-  for (int k = 0; k < 3; ++k) f.P[k] = f.U[k] = f.V[k] = 0;
-  if (!planes) return f;
-  const uoc_plane p = planes[b];
-  bool ok = p.found == 1 && isfinite(p.d) && fabsf(p.d) <= 1000.0f;
-  for (int k = 0; k < 3; ++k) {
-    ok = ok && unit_ok(p.normal[k]) && unit_ok(p.u[k]) && unit_ok(p.v[k]) && isfinite(p.centroid[k]);
-    ok = ok && fabsf(rintf(p.centroid[k] * 1000.0f)) <= 32767.0f;
-  }
-  if (ok) {
-    for (int k = 0; k < 3; ++k) {
-      f.P[k] = (int)rint((double)p.normal[k] * 16384.0);
-      f.U[k] = (int)rint((double)p.u[k] * 16384.0);
-      f.V[k] = (int)rint((double)p.v[k] * 16384.0);
-    }
-    f.found = 1;
+// Step F of grid.h; what the classes and the azimuth need of the frame.  No plane records: no plane.
+__device__ __forceinline__ Frame make_plane(const uoc_plane *__restrict__ planes, int b) {
+  Frame f = {};
+  if (planes) {
+    const uoc_plane p = planes[b];
+    f = frame_from_plane(p);
   }
   return f;
 }
@@ -137,7 +115,7 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
   const size_t n = (size_t)H * W;
   const float *X = xyz + (size_t)b * 3 * n;
   const int *L = labels ? labels + (size_t)b * n : nullptr;
-  const PlaneQ pl = make_plane(planes, b);
+  const Frame pl = make_plane(planes, b);
   const int h = r + s, qw = TW + 2 * h, qh = TH + 2 * h;
 
   for (int i = tid; i < NL * FW / 4; i += THREADS) reinterpret_cast<int4 *>(s_faces)[i] = make_int4(0, 0, 0, 0);
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
     if (y >= 0 && y < H && x >= 0 && x < W) {
       const size_t p = (size_t)y * W + x;
       const int l = L ? L[p] : 0;
-      idb = ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0;
+      idb = label_id(l);
       const float fx = X[p], fy = X[n + p], fz = X[2 * n + p];
       bool ok = isfinite(fx) && isfinite(fy) && isfinite(fz) && fz > 0.f;
       const float rx = rintf(fx * 16000.0f), ry = rintf(fy * 16000.0f), rz = rintf(fz * 16000.0f);
@@ -215,7 +193,7 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
         const unsigned long long S = (unsigned long long)(n0 * n0 + n1 * n1 + n2 * n2);
         int cls = 0, bin = 0;
         if (pl.found) {  // rules C and Z; uniform per frame
-          const long long c16 = (n0 * pl.P[0] + n1 * pl.P[1] + n2 * pl.P[2]) * 16384;
+          const long long c16 = (n0 * pl.N[0] + n1 * pl.N[1] + n2 * pl.N[2]) * 16384;
           const long long Lr = (long long)isqrt64(S);
           if (c16 >= c_up * Lr) {
             cls = UOC_NORMAL_UP;
@@ -294,8 +272,6 @@ __global__ __launch_bounds__(NL) void faces_kernel(const int *__restrict__ acc, 
   O[F_PEAK] = peak;
 }
 
-bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX; }
-
 size_t acc_bytes(int B) { return align_up((size_t)B * NL * FW * sizeof(int), 256); }
 
 }  // namespace
@@ -306,7 +282,7 @@ using namespace uoc;
 extern "C" {
 
 size_t uoc_normals_workspace_bytes(int B, int H, int W) {
-  if (!shape_ok(B, H, W)) return 0;
+  if (!image_ok(B, H, W)) return 0;
   return acc_bytes(B);
 }
 
@@ -314,7 +290,7 @@ int uoc_normals(const float *d_xyz, const int32_t *d_labels, const uoc_plane *d_
                 int window, int jump_mm, int min_pairs, const int32_t *h_dirs, int A, int c_up, int s_side, int32_t *d_n,
                 float *d_unit, int32_t *d_faces, void *d_ws, size_t ws_bytes, void *stream) {
   UOC_REQUIRE(d_xyz && d_n && d_faces && h_dirs && d_ws, "uoc_normals: null xyz / n / faces / dirs / workspace");
-  UOC_REQUIRE(shape_ok(B, H, W), "uoc_normals: bad shape B=%d H=%d W=%d (B in 1..65535, H*W below 2^31)", B, H, W);
+  UOC_REQUIRE(image_ok(B, H, W), "uoc_normals: bad shape B=%d H=%d W=%d (B in 1..65535, H*W below 2^31)", B, H, W);
   UOC_REQUIRE(step >= 1 && step <= MAX_R, "uoc_normals: step = %d outside [1, %d]", step, MAX_R);
   UOC_REQUIRE(window >= 0 && window <= MAX_S, "uoc_normals: window = %d outside [0, %d]", window, MAX_S);
   UOC_REQUIRE(jump_mm >= 1 && jump_mm <= 1000, "uoc_normals: jump_mm = %d outside [1, 1000]", jump_mm);
@@ -330,9 +306,9 @@ int uoc_normals(const float *d_xyz, const int32_t *d_labels, const uoc_plane *d_
   for (int k = 0; k < A; ++k)
     UOC_REQUIRE(abs(dirs.v[k][0]) <= 16384 && abs(dirs.v[k][1]) <= 16384, "uoc_normals: direction %d = (%d, %d) outside [-16384, 16384]",
                 k, dirs.v[k][0], dirs.v[k][1]);
-  UOC_REQUIRE(((uintptr_t)d_n & 15) == 0, "uoc_normals: n not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_n), "uoc_normals: n not 16-byte aligned");
   UOC_REQUIRE(ws_bytes >= acc_bytes(B), "uoc_normals: workspace %zu < %zu bytes", ws_bytes, acc_bytes(B));
-  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_normals: workspace not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_ws), "uoc_normals: workspace not 16-byte aligned");
   const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;  // tiles_x * tiles_y <= H * W: an int
   const double n = (double)B * H * W;
   hipStream_t st = (hipStream_t)stream;

@@ -5,7 +5,7 @@
 //
 // Three memsets (the counters n_obs / n_table and the query keys in the workspace, d_owner, d_counts) and three
 // launches, a fourth when there are queries:
-//   raster_kernel   grid (pixel chunks of CHUNK, frames), 4 waves; a wave owns SUB consecutive pixels.  Every block
+//   raster_kernel   grid (pixel chunks of PIX_CHUNK, frames), 4 waves; a wave owns PIX_SUB consecutive pixels.  Every block
 //                   turns the frame's plane record into the integer frame F (block 0 of a frame writes it out).  A lane
 //                   owns 4 consecutive pixels per turn (one int4 and three float4 loads) when H*W is a multiple of 4 and
 //                   the pointers are 16-byte aligned, else one pixel.  A point becomes at most two events: a count event
@@ -26,136 +26,47 @@
 // is part of the key), so no result depends on the order in which lanes, waves or blocks arrive.  Nothing of frame b
 // depends on the other frames of the batch.
 //
+// The frame and its record, step P, the pixel sweep, the merge of equal events (wave_distinct), the segment scan of the
+// column pass, the row minimum and the widest key are grid.h's, shared with the other stages on this grid.
+//
 // Query keys (0: no candidate).  dist2 <= (G/2)^2 = 2^16, idx = i*G + j < 2^18, da = (i-ai)^2 + (j-aj)^2 <=
 // 2 * (4096 + 511)^2 < 2^26:
 //   widest   ((dist2 + 1) << 18) | (0x3FFFF - idx)
 //   nearest  ((2^27 - 1 - da) << 35) | (dist2 << 18) | (0x3FFFF - idx)      for the candidates with dist2 >= need2
-#include "common.h"
+#include "grid.h"
 #include "prof.h"
-
-#include <limits.h>
-#include <math.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;             // ids 0..127; 1..127 are objects
-constexpr int WAVES = 4;
-constexpr int SUB = 1024;           // pixels per wave
-constexpr int CHUNK = WAVES * SUB;  // pixels per block
-constexpr int SCALE = 16384;        // S
-constexpr int MAX_G = 512;
 constexpr int MAX_Q = UOC_PLACE_MAX_QUERIES;
-constexpr int NFR = 16;             // int64 words of a frame record
-constexpr int STRIP = 32;           // columns per block of the column pass
-constexpr int SEGS = 8;             // row segments per column: STRIP * SEGS threads
-constexpr int ROW_THREADS = 256;
-constexpr int IDX_MASK = 0x3FFFF;
-constexpr int MAX_ANCHOR = 4096;
 
-static_assert(MAX_G * MAX_G <= IDX_MASK + 1, "a cell index must fit the key's low 18 bits");
-static_assert((MAX_G / 2) * (MAX_G / 2) < (1 << 17), "dist2 must fit 17 bits of the key");
 static_assert(2ll * (MAX_ANCHOR + MAX_G) * (MAX_ANCHOR + MAX_G) < (1ll << 27) - 1, "the anchor distance must fit 27 bits");
-static_assert(STRIP * SEGS == 256 && MAX_G % SEGS == 0, "column pass layout");
-static_assert(sizeof(uoc_plane) == 21 * 4, "uoc_plane is 21 words");
-
-struct Frame {
-  int N[3], U[3], V[3], qc[3];
-  long long D;
-  int found;
-};
 
 struct Queries {
   int v[MAX_Q][4];  // need2, ai, aj, mode
 };
-
-__device__ __forceinline__ bool unit_ok(float a) { return isfinite(a) && fabsf(a) <= 2.0f; }
-
-// Step F.  Wave-uniform: every thread reads the same record.
-__device__ __forceinline__ Frame make_frame(const uoc_plane &p) {
-  Frame f;
-  f.found = 0;
-  f.D = 0;
-  for (int k = 0; k < 3; ++k) f.N[k] = f.U[k] = f.V[k] = f.qc[k] = 0;
-  bool ok = p.found == 1 && isfinite(p.d) && fabsf(p.d) <= 1000.0f;
-  float r[3];
-  for (int k = 0; k < 3; ++k) {
-    ok = ok && unit_ok(p.normal[k]) && unit_ok(p.u[k]) && unit_ok(p.v[k]) && isfinite(p.centroid[k]);
-    r[k] = rintf(p.centroid[k] * 1000.0f);
-    ok = ok && fabsf(r[k]) <= 32767.0f;
-  }
-  if (ok) {
-    for (int k = 0; k < 3; ++k) {
-      f.N[k] = (int)rint((double)p.normal[k] * 16384.0);
-      f.U[k] = (int)rint((double)p.u[k] * 16384.0);
-      f.V[k] = (int)rint((double)p.v[k] * 16384.0);
-      f.qc[k] = (int)r[k];
-    }
-    f.D = (long long)rint((double)p.d * 16384000.0);
-    f.found = 1;
-  }
-  return f;
-}
-
-__device__ __forceinline__ long long floor_div(long long a, int c) {  // c > 0
-  const long long q = a / c;
-  return q - ((a - q * c) < 0 ? 1 : 0);
-}
 
 struct Thresholds {
   int cell_div;         // cell_mm * S
   int t_low, t_obs, t_tab;  // -tau_mm*S, h_obs_mm*S, tau_mm*S   (all below 2^24)
 };
 
-// Step P of one pixel: the count event (cell*2 + obstacle) and the owner event (cell*128 + id), -1 for none; returns
-// true when the point lies outside the grid.
+// One pixel after step P (grid.h): the count event (cell*2 + obstacle) and the owner event (cell*128 + id), -1 for none;
+// returns true when the point lies outside the grid.
 __device__ __forceinline__ bool classify(const Frame &f, const Thresholds &th, int G, int l, float x, float y, float z,
                                          int &e_cnt, int &e_own) {
   e_cnt = e_own = -1;
-  if (!(isfinite(x) && isfinite(y) && isfinite(z) && z > 0.f)) return false;
-  const float rx = rintf(x * 1000.0f), ry = rintf(y * 1000.0f), rz = rintf(z * 1000.0f);
-  if (!(fabsf(rx) <= 32767.f && fabsf(ry) <= 32767.f && fabsf(rz) <= 32767.f)) return false;
-  const int qx = (int)rx, qy = (int)ry, qz = (int)rz;
-  const int dx = qx - f.qc[0], dy = qy - f.qc[1], dz = qz - f.qc[2];
-  const long long A = (long long)f.U[0] * dx + (long long)f.U[1] * dy + (long long)f.U[2] * dz;
-  const long long Bv = (long long)f.V[0] * dx + (long long)f.V[1] * dy + (long long)f.V[2] * dz;
-  const long long i = floor_div(A, th.cell_div) + G / 2, j = floor_div(Bv, th.cell_div) + G / 2;
-  if ((unsigned long long)i >= (unsigned long long)G || (unsigned long long)j >= (unsigned long long)G) return true;
-  const long long T = (long long)f.N[0] * qx + (long long)f.N[1] * qy + (long long)f.N[2] * qz + f.D;
-  if (T < th.t_low) return false;
-  const int id = ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0;
-  const int cell = (int)i * G + (int)j;
-  if (id != 0 || T > th.t_obs) {
-    e_cnt = cell * 2 + 1;
-    if (id) e_own = cell * NL + id;
-  } else if (T <= th.t_tab) {
-    e_cnt = cell * 2;
-  }
-  return false;
-}
-
-// Every distinct code >= 0 among the K slots of the wave's lanes is handed to `emit` once, by one lane, with the number
-// of (lane, slot) places that hold it.
-template <int K, typename Emit>
-__device__ __forceinline__ void wave_distinct(int (&e)[K], int lane, Emit emit) {
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    unsigned long long rem = __ballot(e[j] >= 0);
-    while (rem) {
-      const int first = __ffsll((long long)rem) - 1;
-      const int c = __builtin_amdgcn_readlane(e[j], first);
-      int total = 0;
-#pragma unroll
-      for (int k = j; k < K; ++k) {
-        const bool hit = e[k] == c;
-        const unsigned long long m = __ballot(hit);
-        total += __popcll(m);
-        if (k == j) rem &= ~m;
-        if (hit) e[k] = -1;
-      }
-      if (lane == first) emit(c, total);
+  return project_point(f, th.cell_div, th.t_low, G, x, y, z, [&](int i, int j, long long T) {
+    const int id = label_id(l);
+    const int cell = i * G + j;
+    if (id != 0 || T > th.t_obs) {
+      e_cnt = cell * 2 + 1;
+      if (id) e_own = cell * NL + id;
+    } else if (T <= th.t_tab) {
+      e_cnt = cell * 2;
     }
-  }
+  });
 }
 
 // ---- 1. raster --------------------------------------------------------------------------------------------------------
@@ -166,62 +77,24 @@ __global__ __launch_bounds__(256) void raster_kernel(const int *__restrict__ lab
                                                      int *__restrict__ owner, int *__restrict__ counts,
                                                      long long *__restrict__ frame) {
   constexpr int K = VEC ? 4 : 1;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int c = blockIdx.x, b = blockIdx.y;
-  const Frame f = make_frame(planes[b]);
-  if (c == 0 && tid == 0) {
-    long long *F = frame + (size_t)b * NFR;
-    for (int k = 0; k < 3; ++k) {
-      F[k] = f.N[k];
-      F[4 + k] = f.U[k];
-      F[7 + k] = f.V[k];
-      F[10 + k] = f.qc[k];
-    }
-    F[3] = f.D;
-    F[13] = f.found;
-    F[14] = F[15] = 0;
-  }
+  const Frame f = frame_from_plane(planes[b]);
+  if (c == 0 && tid == 0) store_frame(frame + (size_t)b * NFR, f);
   if (!f.found) return;  // uniform per frame
-  const int *L = labels + (size_t)b * n;
-  const float *X = xyz + (size_t)b * 3 * n;
   const size_t cells = (size_t)G * G;
   int *NO = n_obs + (size_t)b * cells, *NT = n_table + (size_t)b * cells, *OW = owner + (size_t)b * cells;
-  const long long p0 = (long long)c * CHUNK + (long long)w * SUB;
   int outside = 0;
-  for (int it = 0; it < SUB / (64 * K); ++it) {
-    const long long base = p0 + (long long)it * 64 * K;
-    if (base >= n) break;  // uniform per wave
-    const long long p = base + (long long)lane * K;
+  Pixels<K> px;
+  for (PixelSweep<VEC> sweep(labels + (size_t)b * n, xyz + (size_t)b * 3 * n, n); sweep.load(px);) {
     int e_cnt[K], e_own[K];
+    const int none[K] = {};
     bool out[K];
-    if constexpr (VEC) {
-      int4 l4 = make_int4(0, 0, 0, 0);
-      float4 x4 = make_float4(0.f, 0.f, 0.f, 0.f), y4 = x4, z4 = x4;  // z = 0: no point
-      if (p < n) {  // n is a multiple of 4: the four pixels are inside together
-        l4 = *reinterpret_cast<const int4 *>(L + p);
-        x4 = *reinterpret_cast<const float4 *>(X + p);
-        y4 = *reinterpret_cast<const float4 *>(X + n + p);
-        z4 = *reinterpret_cast<const float4 *>(X + 2 * n + p);
-      }
-      out[0] = classify(f, th, G, l4.x, x4.x, y4.x, z4.x, e_cnt[0], e_own[0]);
-      out[1] = classify(f, th, G, l4.y, x4.y, y4.y, z4.y, e_cnt[1], e_own[1]);
-      out[2] = classify(f, th, G, l4.z, x4.z, y4.z, z4.z, e_cnt[2], e_own[2]);
-      out[3] = classify(f, th, G, l4.w, x4.w, y4.w, z4.w, e_cnt[3], e_own[3]);
-    } else {
-      int l = 0;
-      float x = 0.f, y = 0.f, z = 0.f;
-      if (p < n) {
-        l = L[p];
-        x = X[p];
-        y = X[n + p];
-        z = X[2 * n + p];
-      }
-      out[0] = classify(f, th, G, l, x, y, z, e_cnt[0], e_own[0]);
-    }
 #pragma unroll
-    for (int k = 0; k < K; ++k) outside += __popcll(__ballot(out[k]));
-    wave_distinct<K>(e_cnt, lane, [&](int code, int total) { atomicAdd((code & 1) ? &NO[code >> 1] : &NT[code >> 1], total); });
-    wave_distinct<K>(e_own, lane, [&](int code, int) { atomicMax(&OW[code >> 7], code & (NL - 1)); });
+    for (int k = 0; k < K; ++k) out[k] = classify(f, th, G, px.l[k], px.x[k], px.y[k], px.z[k], e_cnt[k], e_own[k]);
+    outside += wave_count_set(out);
+    wave_distinct<K, false>(e_cnt, none, lane, [&](int code, int total, int) { atomicAdd((code & 1) ? &NO[code >> 1] : &NT[code >> 1], total); });
+    wave_distinct<K, false>(e_own, none, lane, [&](int code, int, int) { atomicMax(&OW[code >> 7], code & (NL - 1)); });
   }
   if (lane == 0 && outside) atomicAdd(&counts[(size_t)b * NL], outside);
 }
@@ -233,10 +106,9 @@ __global__ __launch_bounds__(STRIP *SEGS) void column_kernel(const int *__restri
                                                              int *__restrict__ owner, int *__restrict__ g_out,
                                                              int *__restrict__ counts) {
   __shared__ unsigned short s[MAX_G][STRIP];  // bit 15: blocking; after the upward scan the low bits hold the distance up
-  __shared__ int s_first[SEGS][STRIP], s_last[SEGS][STRIP];
   __shared__ int s_hist[NL];
   const int tid = threadIdx.x, b = blockIdx.y, j0 = blockIdx.x * STRIP;
-  const bool found = frame[(size_t)b * NFR + 13] != 0;
+  const bool found = frame_found_nonzero(frame + (size_t)b * NFR);
   const size_t off = (size_t)b * G * G;
   if (tid < NL) s_hist[tid] = 0;
   __syncthreads();
@@ -256,42 +128,7 @@ __global__ __launch_bounds__(STRIP *SEGS) void column_kernel(const int *__restri
   }
   __syncthreads();
   if (tid >= 1 && tid < NL && s_hist[tid]) atomicAdd(&counts[(size_t)b * NL + tid], s_hist[tid]);
-  const int jj = tid % STRIP, seg = tid / STRIP, rows = G / SEGS, r0 = seg * rows, r1 = r0 + rows;
-  const bool col = j0 + jj < G;
-  {  // the first and the last blocking row of the segment
-    int first = INT_MAX, last = -1;
-    if (col)
-      for (int i = r0; i < r1; ++i)
-        if (s[i][jj] & 0x8000u) {
-          if (first == INT_MAX) first = i;
-          last = i;
-        }
-    s_first[seg][jj] = first;
-    s_last[seg][jj] = last;
-  }
-  __syncthreads();
-  if (!col) return;
-  int up = -1, down = G;  // the virtual blocking cells
-  for (int k = seg - 1; k >= 0; --k)
-    if (s_last[k][jj] >= 0) {
-      up = s_last[k][jj];
-      break;
-    }
-  for (int k = seg + 1; k < SEGS; ++k)
-    if (s_first[k][jj] != INT_MAX) {
-      down = s_first[k][jj];
-      break;
-    }
-  for (int i = r0; i < r1; ++i) {  // distance up, at most 512: bits 0..9
-    const unsigned v = s[i][jj];
-    if (v & 0x8000u) up = i;
-    s[i][jj] = (unsigned short)((v & 0x8000u) | (unsigned)(i - up));
-  }
-  for (int i = r1 - 1; i >= r0; --i) {
-    const unsigned v = s[i][jj];
-    if (v & 0x8000u) down = i;
-    g_out[off + (size_t)i * G + j0 + jj] = min((int)(v & 0x7FFFu), down - i);
-  }
+  column_scan(s, G, j0, g_out + off);
 }
 
 // ---- 3. the row pass and the queries -----------------------------------------------------------------------------------
@@ -301,34 +138,23 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
   __shared__ unsigned long long s_key[MAX_Q];
   const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x, b = blockIdx.y;
   const size_t off = ((size_t)b * G + i) * G;
-  for (int j = tid; j < G; j += ROW_THREADS) {
-    const int g = dist2[off + j];
-    s_g2[j] = g * g;
-  }
+  row_fill_g2(s_g2, dist2 + off, G);
   if (tid < MAX_Q) s_key[tid] = 0ull;
   __syncthreads();
   unsigned long long key[MAX_Q];
 #pragma unroll
   for (int q = 0; q < MAX_Q; ++q) key[q] = 0ull;
   for (int j = tid; j < G; j += ROW_THREADS) {
-    int best = min((j + 1) * (j + 1), (G - j) * (G - j));  // the virtual columns -1 and G
-    for (int k = 0; k < G; k += 4) {                       // G is a multiple of 8
-      const int4 v = *reinterpret_cast<const int4 *>(&s_g2[k]);
-      const int d = j - k;
-      best = min(best, d * d + v.x);
-      best = min(best, (d - 1) * (d - 1) + v.y);
-      best = min(best, (d - 2) * (d - 2) + v.z);
-      best = min(best, (d - 3) * (d - 3) + v.w);
-    }
+    const int best = row_min_dist2(s_g2, j, G);
     dist2[off + j] = best;
     if (Q > 0 && state[off + j] == 1) {
-      const unsigned long long low = (unsigned long long)(IDX_MASK - (i * G + j));
+      const unsigned long long low = cell_key(i * G + j);
 #pragma unroll
       for (int q = 0; q < MAX_Q; ++q) {
         unsigned long long k64 = 0ull;
         if (q >= Q) {  // uniform
         } else if (qs.v[q][3] == UOC_PLACE_WIDEST) {
-          k64 = ((unsigned long long)(best + 1) << 18) | low;
+          k64 = widest_key(best, i * G + j);
         } else if (best >= qs.v[q][0]) {
           const int di = i - qs.v[q][1], dj = j - qs.v[q][2];
           const unsigned long long da = (unsigned long long)(di * di + dj * dj);
@@ -342,9 +168,7 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
 #pragma unroll
   for (int q = 0; q < MAX_Q; ++q) {
     if (q < Q) {  // uniform
-      unsigned long long k64 = key[q];
-#pragma unroll
-      for (int sft = 32; sft > 0; sft >>= 1) k64 = max(k64, (unsigned long long)__shfl_xor((long long)k64, sft));
+      const unsigned long long k64 = wave_max64(key[q]);
       if (lane == 0 && k64) atomicMax(&s_key[q], k64);
     }
   }
@@ -359,11 +183,11 @@ __global__ __launch_bounds__(64) void answer_kernel(const unsigned long long *__
   const unsigned long long k64 = keys[(size_t)b * MAX_Q + q];
   int4 a = make_int4(-1, -1, 0, 0);
   if (k64) {
-    const int idx = IDX_MASK - (int)(k64 & (unsigned long long)IDX_MASK);
+    const int idx = key_cell(k64);
     a.x = idx / G;
     a.y = idx % G;
     if (qs.v[q][3] == UOC_PLACE_WIDEST) {
-      a.z = (int)(k64 >> 18) - 1;
+      a.z = key_dist2(k64);
       a.w = a.z >= qs.v[q][0];
     } else {
       a.z = (int)((k64 >> 18) & 0x1FFFFull);
@@ -377,9 +201,7 @@ __global__ __launch_bounds__(64) void answer_kernel(const unsigned long long *__
   A[3] = a.w;
 }
 
-bool shape_ok(int B, int H, int W, int G) {
-  return B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX && G >= 8 && G <= MAX_G && G % 8 == 0;
-}
+bool shape_ok(int B, int H, int W, int G) { return image_ok(B, H, W) && grid_ok(G); }
 
 struct Ws {
   int *n_obs, *n_table;        // [B][G][G] each
@@ -415,9 +237,9 @@ int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *
                   int32_t *d_answers, void *d_ws, size_t ws_bytes, void *stream) {
   UOC_REQUIRE(d_labels && d_xyz && d_planes && d_state && d_owner && d_dist2 && d_counts && d_frame && d_ws,
               "uoc_placement: null labels / xyz / planes / state / owner / dist2 / counts / frame / workspace");
-  UOC_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= INT_MAX,
+  UOC_REQUIRE(image_ok(B, H, W),
               "uoc_placement: bad shape B=%d H=%d W=%d (B in 1..65535, H*W below 2^31)", B, H, W);
-  UOC_REQUIRE(G >= 8 && G <= MAX_G && G % 8 == 0, "uoc_placement: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
+  UOC_REQUIRE(grid_ok(G), "uoc_placement: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
   UOC_REQUIRE(cell_mm >= 1 && cell_mm <= 1000, "uoc_placement: cell_mm = %d outside [1, 1000]", cell_mm);
   UOC_REQUIRE(h_obs_mm >= 0 && h_obs_mm <= 1000, "uoc_placement: h_obs_mm = %d outside [0, 1000]", h_obs_mm);
   UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_placement: tau_mm = %d outside [1, 1000]", tau_mm);
@@ -437,9 +259,9 @@ int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *
   }
   const Ws w = carve(d_ws, B, G);
   UOC_REQUIRE(ws_bytes >= w.total, "uoc_placement: workspace %zu < %zu bytes", ws_bytes, w.total);
-  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_placement: workspace not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_ws), "uoc_placement: workspace not 16-byte aligned");
   const long long n = (long long)H * W;
-  const int nch = (int)((n + CHUNK - 1) / CHUNK);
+  const int nch = (int)((n + PIX_CHUNK - 1) / PIX_CHUNK);
   const size_t cells = (size_t)B * G * G;
   const Thresholds th = {cell_mm * SCALE, -tau_mm * SCALE, h_obs_mm * SCALE, tau_mm * SCALE};
   const bool vec = n % 4 == 0 && (((uintptr_t)d_labels | (uintptr_t)d_xyz) & 15) == 0;

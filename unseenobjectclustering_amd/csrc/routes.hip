@@ -7,7 +7,8 @@
 // One memset (the sweep counters in the workspace) and three launches:
 //   run_kernel    grid (rows, maps, frames), 4 waves.  A map belongs to one distinct (ignore, need2); queries with the
 //                 same pair share it.  The row's FREE bits by ballot into LDS, then per cell the length of the run of FREE
-//                 cells that ends there: 16-bit words (§18's run_kernel, copied).  A frame without a plane gets zeros.
+//                 cells that ends there: 16-bit words (grid.h's run_kernel, which footprint.hip launches too).  A frame
+//                 without a plane gets zeros.
 //   pass_kernel   grid (chunks of 256 cells, maps, frames).  A row of the disc is one span |dj| <= h(di), h from the host
 //                 as a kernel argument: the span of row i+di is free iff it lies in the grid and
 //                 run[i+di][j+h] >= 2h+1.  One byte per cell: PASSABLE or not.
@@ -33,44 +34,35 @@
 //
 // Determinism: the fixpoint of the relaxation is unique, the key is a strict total order and the walk back follows a
 // fixed order: nothing depends on the schedule.  Nothing of frame b depends on the other frames of the batch.
-#include "common.h"
+#include "grid.h"
 #include "prof.h"
-
-#include <limits.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;  // ids 0..127
-constexpr int MAX_G = 512;
 constexpr int MAX_Q = UOC_ROUTES_MAX_QUERIES;
 constexpr int MAX_NEED2 = UOC_ROUTES_MAX_NEED2;
 constexpr int MAX_PATH = UOC_ROUTES_MAX_PATH;
 constexpr int MAX_R = 63;            // di*di < 4096
 constexpr int ROWS = 2 * MAX_R + 2;  // 127 rows of the disc, padded to 128 bytes
-constexpr int NFR = 16;              // int64 words of a frame record
 constexpr int THREADS = 256;
 constexpr int SOLVE_THREADS = 1024;
-constexpr int IDX_MASK = 0x3FFFF;
 constexpr int COST_MASK = (1 << 21) - 1, DA_MASK = (1 << 19) - 1;
 constexpr int LDS_FIELD_BYTES = 152 * 1024;  // of the CU's 160 KB; the rest is for the few words beside the field
 constexpr int W_ORTH = 5, W_DIAG = 7;
 constexpr unsigned PACK_DI = 0xA094u, PACK_DJ = 0x8861u;  // 2 bits per move k: d + 1 of (-1,0) (0,-1) (0,1) (1,0) (-1,-1) (-1,1) (1,-1) (1,1)
 enum { FIELD_LDS32 = 0, FIELD_LDS16 = 1, FIELD_GLOBAL = 2 };
 
-static_assert(MAX_G * MAX_G <= IDX_MASK + 1, "a cell index must fit 18 bits of the key");
 static_assert(7ll * MAX_G * MAX_G <= COST_MASK, "a cost must fit 21 bits of the key");
 static_assert(2 * (MAX_G - 1) * (MAX_G - 1) <= DA_MASK, "da must fit 19 bits of the key");
 static_assert((MAX_R + 1) * (MAX_R + 1) >= MAX_NEED2 && MAX_R * MAX_R < MAX_NEED2, "the disc has rows -63..63");
-static_assert(MAX_G <= 65535, "a run is one 16-bit word");
-static_assert(MAX_G / 64 <= 8, "a row is at most 8 ballot words");
 
 struct Queries {
   int v[MAX_Q][8];  // need2, si, sj, ti, tj, ignore, 0, 0
 };
 struct Plan {
   int map[MAX_Q];     // the map of query q
-  int ignore[MAX_Q];  // of map m
+  RunIgnore<MAX_Q> ignore;  // of map m
   int need2[MAX_Q];   // of map m
   signed char half[MAX_Q][ROWS];  // h of row di + 63 of map m's disc: |dj| <= h, -1 for an empty row
 };
@@ -85,50 +77,6 @@ int field_mode(int G) {
   if ((size_t)(G + 2) * pitch16(G) * 2 <= (size_t)LDS_FIELD_BYTES) return FIELD_LDS16;
   return FIELD_GLOBAL;
 #endif
-}
-
-// ---- 1. the runs of FREE cells (footprint.hip's run_kernel, one table per map) --------------------------------------
-__global__ __launch_bounds__(THREADS) void run_kernel(const int *__restrict__ state, const int *__restrict__ owner,
-                                                      const long long *__restrict__ frame, int G, int NM, Plan p,
-                                                      int unknown_blocks, unsigned short *__restrict__ runs) {
-  __shared__ unsigned long long s_bits[MAX_G / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blockIdx.x, m = blockIdx.y, b = blockIdx.z;
-  const bool found = frame == nullptr || frame[(size_t)b * NFR + 13] == 1;  // uniform per frame
-  const int ignore = p.ignore[m];
-  const size_t in = ((size_t)b * G + i) * G, out = (((size_t)b * NM + m) * G + i) * G;
-  for (int jb = 0; jb < G; jb += THREADS) {  // uniform: every lane takes part in the ballot
-    const int j = jb + tid;
-    bool fr = false;
-    if (found && j < G) {
-      const int st = state[in + j];
-      if (st == 1) {
-        fr = true;
-      } else if (st == 2) {
-        const int o = owner[in + j];
-        fr = (unsigned)(o - 1) < (unsigned)(NL - 1) ? (o == ignore) : !unknown_blocks;  // ignore == 0 matches no id
-      } else {
-        fr = !unknown_blocks;  // state 0 and every state outside 0..2: unknown
-      }
-    }
-    const unsigned long long bits = __ballot(fr);
-    if (lane == 0 && jb + wave * 64 < G) s_bits[(jb >> 6) + wave] = bits;
-  }
-  __syncthreads();
-  for (int j = tid; j < G; j += THREADS) {
-    int w = j >> 6, len = 0;
-    unsigned long long x = ~s_bits[w] << (63 - (j & 63));  // bit 63 is cell j; a set bit is a cell that is not FREE
-    while (true) {
-      if (x) {
-        len += __clzll((long long)x);
-        break;
-      }
-      len += (w == (j >> 6)) ? (j & 63) + 1 : 64;
-      if (--w < 0) break;
-      x = ~s_bits[w];
-    }
-    runs[out + j] = (unsigned short)len;
-  }
 }
 
 // ---- 2. PASSABLE ------------------------------------------------------------------------------------------------------
@@ -245,17 +193,6 @@ __device__ int relax(const F f, int G, int pitch, Shared &s, int &sweeps) {
   return fl;
 }
 
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, (unsigned long long)__shfl_xor((long long)v, sft));
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
-  return v;
-}
-
 // cost, info and path of one (frame, query) from the converged field.
 template <class F>
 __device__ void tail(const F f, int G, int pitch, const int *q, bool src_ok, int max_path, Shared &s, int *__restrict__ cost,
@@ -275,7 +212,7 @@ __device__ void tail(const F f, int G, int pitch, const int *q, bool src_ok, int
     if (re && target) {
       const int da = (i - ti) * (i - ti) + (j - tj) * (j - tj);
       key = max(key, ((unsigned long long)(DA_MASK - da) << 39) | ((unsigned long long)(COST_MASK - (int)v) << 18) |
-                         (unsigned long long)(IDX_MASK - idx));
+                         cell_key(idx));
     }
   }
   reached = wave_sum(reached), passable = wave_sum(passable), key = wave_max64(key);
@@ -290,7 +227,7 @@ __device__ void tail(const F f, int G, int pitch, const int *q, bool src_ok, int
     int rec[8] = {src_ok ? 1 : 0, 0, -1, -1, 0, 0, s.reached, s.passable};
     int last = -1;
     if (key) {
-      const int idx = IDX_MASK - (int)(key & (unsigned long long)IDX_MASK);
+      const int idx = key_cell(key);
       unsigned vc = (unsigned)(COST_MASK - (int)((key >> 18) & (unsigned long long)COST_MASK));
       const int ci = idx / G, cj = idx - ci * G;
       int i = ci, j = cj, steps = 0;
@@ -398,7 +335,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const unsigned cha
 }
 
 bool shape_ok(int B, int G, int Q) {
-  return B > 0 && B <= 65535 && G >= 8 && G <= MAX_G && G % 8 == 0 && Q >= 1 && Q <= MAX_Q;
+  return batch_ok(B) && grid_ok(G) && Q >= 1 && Q <= MAX_Q;
 }
 
 struct Ws {
@@ -443,8 +380,8 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
                void *stream) {
   UOC_REQUIRE(d_state && d_owner && h_queries && d_cost && d_info && d_path && d_ws,
               "uoc_routes: null state / owner / queries / cost / info / path / workspace");
-  UOC_REQUIRE(B > 0 && B <= 65535, "uoc_routes: bad shape B=%d (B in 1..65535)", B);
-  UOC_REQUIRE(G >= 8 && G <= MAX_G && G % 8 == 0, "uoc_routes: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
+  UOC_REQUIRE(batch_ok(B), "uoc_routes: bad shape B=%d (B in 1..65535)", B);
+  UOC_REQUIRE(grid_ok(G), "uoc_routes: grid = %d is not a multiple of 8 in [8, %d]", G, MAX_G);
   UOC_REQUIRE(Q >= 1 && Q <= MAX_Q, "uoc_routes: %d queries outside [1, %d]", Q, MAX_Q);
   UOC_REQUIRE(unknown_blocks == 0 || unknown_blocks == 1, "uoc_routes: unknown_blocks = %d is neither 0 nor 1", unknown_blocks);
   UOC_REQUIRE(max_path >= 1 && max_path <= MAX_PATH, "uoc_routes: max_path = %d outside [1, %d]", max_path, MAX_PATH);
@@ -453,7 +390,7 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
   int NM = 0;
   for (int q = 0; q < MAX_Q; ++q) {
     for (int k = 0; k < 8; ++k) qs.v[q][k] = q < Q ? h_queries[q * 8 + k] : 0;
-    p.map[q] = p.ignore[q] = p.need2[q] = 0;
+    p.map[q] = p.ignore.v[q] = p.need2[q] = 0;
     for (int r = 0; r < ROWS; ++r) p.half[q][r] = -1;
   }
   for (int q = 0; q < Q; ++q) {
@@ -466,9 +403,9 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
     UOC_REQUIRE(v[5] >= 0 && v[5] < NL, "uoc_routes: query %d: ignore = %d outside [0, 127]", q, v[5]);
     UOC_REQUIRE(v[6] == 0 && v[7] == 0, "uoc_routes: query %d: reserved words (%d, %d) are not zero", q, v[6], v[7]);
     int m = 0;
-    while (m < NM && !(p.ignore[m] == v[5] && p.need2[m] == v[0])) ++m;
+    while (m < NM && !(p.ignore.v[m] == v[5] && p.need2[m] == v[0])) ++m;
     if (m == NM) {
-      p.ignore[m] = v[5], p.need2[m] = v[0];
+      p.ignore.v[m] = v[5], p.need2[m] = v[0];
       for (int di = -MAX_R; di <= MAX_R; ++di) {  // the span of row di: dj*dj < need2 - di*di
         int h = -1;
         while ((h + 1) * (h + 1) < v[0] - di * di) ++h;
@@ -480,7 +417,7 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
   }
   const Ws w = carve(d_ws, B, G, Q);
   UOC_REQUIRE(ws_bytes >= w.total, "uoc_routes: workspace %zu < %zu bytes", ws_bytes, w.total);
-  UOC_REQUIRE(((uintptr_t)d_ws & 15) == 0, "uoc_routes: workspace not 16-byte aligned");
+  UOC_REQUIRE(aligned16(d_ws), "uoc_routes: workspace not 16-byte aligned");
   const int cells = G * G, mode = field_mode(G);
   const size_t lds = mode == FIELD_LDS32 ? (size_t)(G + 2) * pitch32(G) * 4 : mode == FIELD_LDS16 ? (size_t)(G + 2) * pitch16(G) * 2 : 0;
   static DeviceOnce attr_set;
@@ -493,8 +430,8 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
   {
     ProfScope prof(KC_ROUTES_TABLES, st, 0.0, (double)B * cells * (8.0 + 5.0 * NM));
     UOC_HIP_CHECK(hipMemsetAsync(w.sweeps, 0, w.sweeps_bytes, st));
-    hipLaunchKernelGGL(run_kernel, dim3(G, NM, B), dim3(THREADS), 0, st, d_state, d_owner, (const long long *)d_frame, G, NM, p,
-                       unknown_blocks, w.runs);
+    hipLaunchKernelGGL(run_kernel<MAX_Q>, dim3(G, NM, B), dim3(RUN_THREADS), 0, st, d_state, d_owner, (const long long *)d_frame, G,
+                       NM, p.ignore, unknown_blocks, w.runs);
     hipLaunchKernelGGL(pass_kernel, dim3((cells + THREADS - 1) / THREADS, NM, B), dim3(THREADS), 0, st, w.runs, G, NM, p, w.pass);
   }
   {

@@ -46,10 +46,6 @@ class ElevationResult:
         self.__dict__.update(fields)
 
 
-def _on_gpu(t):
-    return isinstance(t, torch.Tensor) and t.device.type == "cuda"
-
-
 def elevation_records(labels, xyz, frame, grid, cell_mm, tau_mm, step_mm, min_pts, queries=()):
     """The raw uoc_elevation call: (elev, owner, pts, near, dist2 [B,G,G] int32, tops [B,128,8] int32, info [B,4] int32,
     answers [B,Q,4] int32), on the device, no synchronisation.  labels int32 [B,H,W], xyz float32 [B,3,H,W], frame int64
@@ -111,7 +107,7 @@ def heights(labels, xyz, placed, step=0.005, min_pts=2, queries=None) -> Elevati
         if not 1 <= mm <= _native.PLACE_MAX_MM:
             raise ValueError(f"{name} = {mm} outside 1..{_native.PLACE_MAX_MM} mm")
     for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _on_gpu(t):
+        if not _native.on_gpu(t):
             raise _native.NativeError(f"heights: {what} must be a tensor on the GPU (there is no CPU fallback)")
     if labels.dim() == 2:
         labels = labels[None]
@@ -125,7 +121,7 @@ def heights(labels, xyz, placed, step=0.005, min_pts=2, queries=None) -> Elevati
         raise _native.NativeError("heights: labels and xyz are on different devices")
     B = int(labels.shape[0])
     frame = getattr(placed, "frame", None)
-    if not _on_gpu(frame) or frame.device != labels.device or frame.dtype != torch.int64 or tuple(frame.shape) != (B, 16):
+    if not _native.on_gpu(frame) or frame.device != labels.device or frame.dtype != torch.int64 or tuple(frame.shape) != (B, 16):
         raise _native.NativeError(f"heights: the frame records of `placed` do not match the {B} frames on {labels.device}")
     lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
     frame = frame.contiguous()
@@ -160,9 +156,8 @@ def cell_to_camera(result, b, i, j, h_mm=0):
     F = np.asarray(result.frame[b].cpu().tolist(), np.float64)
     S = float(_native.PLACE_SCALE)
     n, u, v, c = F[0:3] / S, F[4:7] / S, F[7:10] / S, F[10:13] / 1000.0
-    cell = result.cell_mm / 1000.0
     n = n / np.linalg.norm(n)
-    return c + (int(i) - result.grid // 2 + 0.5) * cell * u + (int(j) - result.grid // 2 + 0.5) * cell * v + float(h_mm) / 1000.0 * n
+    return placement.grid_point(c, u, v, result.grid, result.cell_mm, int(i) + 0.5, int(j) + 0.5) + float(h_mm) / 1000.0 * n
 
 
 def spot(result, b, a):

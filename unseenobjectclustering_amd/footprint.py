@@ -21,7 +21,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, placement
 from .grasp import direction_table
 
 ROOMIEST, NEAREST = _native.FOOT_ROOMIEST, _native.FOOT_NEAREST
@@ -70,7 +70,7 @@ def footprint_records(state, owner, dist2, frame, dirs, rects, unknown_blocks):
     synchronisation.  state, owner, dist2: device tensors [B,G,G] or [G,G] of any integer type and layout (they are made
     int32 and contiguous); frame: [B,16] int64 on the device, or None; dirs: [A,2] integers in -S..S; rects: [F,8]."""
     for t, what in ((state, "state"), (owner, "owner"), (dist2, "dist2")):
-        if not (isinstance(t, torch.Tensor) and t.device.type == "cuda"):
+        if not _native.on_gpu(t):
             raise _native.NativeError(f"footprint: {what} must be a tensor on the GPU (there is no CPU fallback)")
     state, owner, dist2 = (t[None] if t.dim() == 2 else t for t in (state, owner, dist2))
     if state.dim() != 3 or state.shape[1] != state.shape[2] or any(tuple(t.shape) != tuple(state.shape) or t.device != state.device
@@ -174,11 +174,8 @@ def pose(result, b, f):
         return None
     i, j, k = rec[1:4]
     cx, cy = (float(x) for x in result.dirs[k])
-    p = result.planes[b].cpu().numpy().view(np.float32).astype(np.float64)
-    off = {name: getattr(_native.UocPlane, name).offset // 4 for name in ("normal", "centroid", "u", "v")}
-    n, c, u, v = (p[off[name]:off[name] + 3] for name in ("normal", "centroid", "u", "v"))
-    cell = result.cell_mm / 1000.0
-    center = c + (i - result.grid // 2 + 0.5) * cell * u + (j - result.grid // 2 + 0.5) * cell * v
+    n, c, u, v = placement.plane_axes(result.planes, b)
+    center = placement.grid_point(c, u, v, result.grid, result.cell_mm, i + 0.5, j + 0.5)
     axis = cx * u + cy * v
     n = n / np.linalg.norm(n)
     axis = axis - (axis @ n) * n                                               # the record is float32: u.n is not exactly 0

@@ -22,7 +22,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, placement
 
 NUM_IDS = 128
 MISS, WIDE, PINCHED, BLOCKED = _native.GRASP_MISS, _native.GRASP_WIDE, _native.GRASP_PINCHED, _native.GRASP_BLOCKED
@@ -81,7 +81,7 @@ def grasp_records(state, owner, dirs, offsets, max_open, gap, finger, pad, unkno
     synchronisation.  state, owner: device tensors [B,G,G] or [G,G] of any integer type and layout (they are made int32
     and contiguous); dirs: [A,2] integers in -S..S; the other parameters in cells."""
     for t, what in ((state, "state"), (owner, "owner")):
-        if not (isinstance(t, torch.Tensor) and t.device.type == "cuda"):
+        if not _native.on_gpu(t):
             raise _native.NativeError(f"grasp: {what} must be a tensor on the GPU (there is no CPU fallback)")
     if state.dim() == 2:
         state = state[None]
@@ -163,11 +163,9 @@ def pose(result, b, a, k=None, m=None):
     cx, cy = (float(x) for x in result.dirs[k])
     mid = tlo + (w - 1) / 2.0
     X, Y = rec[5] + mid * cx - m * cy, rec[6] + mid * cy + m * cx             # units of 1/S cell; cell i spans [i, i+1)
-    p = result.planes[b].cpu().numpy().view(np.float32).astype(np.float64)
-    off = {name: getattr(_native.UocPlane, name).offset // 4 for name in ("normal", "centroid", "u", "v")}
-    n, c, u, v = (p[off[name]:off[name] + 3] for name in ("normal", "centroid", "u", "v"))
+    n, c, u, v = placement.plane_axes(result.planes, b)
     cell = result.cell_mm / 1000.0
-    center = c + (X / S - result.grid // 2) * cell * u + (Y / S - result.grid // 2) * cell * v
+    center = placement.grid_point(c, u, v, result.grid, result.cell_mm, X / S, Y / S)
     axis = cx * u + cy * v
     n = n / np.linalg.norm(n)
     axis = axis - (axis @ n) * n                                               # the record is float32: u.n is not exactly 0

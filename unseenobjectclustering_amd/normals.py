@@ -42,10 +42,6 @@ class NormalsResult:
         self.__dict__.update(fields)
 
 
-def _on_gpu(t):
-    return isinstance(t, torch.Tensor) and t.device.type == "cuda"
-
-
 def direction_table(angles):
     """The azimuth bins [A,2] int32: (rint(cos(2 pi k / A) S), rint(sin(2 pi k / A) S)), S = 16384, in float64."""
     A = int(angles)
@@ -118,7 +114,7 @@ def estimate(xyz, labels=None, fitted=None, step=2, window=2, jump=0.030, min_pa
         raise ValueError(f"min_pairs = {min_pairs} outside 1..{(2 * s + 1) ** 2}")
     dirs = direction_table(angles)
     c_up, s_side = thresholds(up_deg, side_deg)
-    if not _on_gpu(xyz):
+    if not _native.on_gpu(xyz):
         raise _native.NativeError("normals: xyz must be a tensor on the GPU (there is no CPU fallback)")
     if xyz.dim() == 3:
         xyz = xyz[None]
@@ -128,7 +124,7 @@ def estimate(xyz, labels=None, fitted=None, step=2, window=2, jump=0.030, min_pa
     dev = xyz.device
     lab = None
     if labels is not None:
-        if not _on_gpu(labels) or labels.device != dev:
+        if not _native.on_gpu(labels) or labels.device != dev:
             raise _native.NativeError("normals: labels must be a tensor on the GPU of xyz (there is no CPU fallback)")
         if labels.dim() == 2:
             labels = labels[None]
@@ -144,7 +140,7 @@ def estimate(xyz, labels=None, fitted=None, step=2, window=2, jump=0.030, min_pa
             planes = getattr(fitted, "records", None)
             if planes is None:
                 raise _native.NativeError("normals: fitted is neither a fit_plane result nor (normal, d, centroid, u, v)")
-        if not _on_gpu(planes) or planes.device != dev or planes.dtype != torch.int32 or tuple(planes.shape) != (B, _PLANE_WORDS):
+        if not _native.on_gpu(planes) or planes.device != dev or planes.dtype != torch.int32 or tuple(planes.shape) != (B, _PLANE_WORDS):
             raise _native.NativeError(f"normals: the plane records do not match the {B} frames on {dev}")
         planes = planes.contiguous()
     packed, un, faces = normals_records(xyz.to(torch.float32).contiguous(), lab, planes, r, s, jump_mm, mp, dirs, c_up, s_side,
@@ -181,13 +177,8 @@ def _plane_axes(fitted, b):
     """(u, v) of frame b, float64 on the host, from a fit_plane result, device records or the pack_planes tuple."""
     if isinstance(fitted, (tuple, list)):
         rec = placement.pack_planes(*fitted)
-        p = rec[b if len(rec) > 1 else 0]
-    else:
-        rec = getattr(fitted, "records", fitted)
-        p = rec[b].cpu().numpy()
-    p = np.ascontiguousarray(p).view(np.float32).astype(np.float64)
-    off = {name: getattr(_native.UocPlane, name).offset // 4 for name in ("u", "v")}
-    return p[off["u"]:off["u"] + 3], p[off["v"]:off["v"] + 3]
+        return placement.plane_axes(rec, b if len(rec) > 1 else 0)[2:]
+    return placement.plane_axes(getattr(fitted, "records", fitted), b)[2:]
 
 
 def side_directions(result, fitted, b, a, min_share=0.2):

@@ -41,10 +41,6 @@ class PlacementResult:
         self.__dict__.update(fields)
 
 
-def _on_gpu(t):
-    return isinstance(t, torch.Tensor) and t.device.type == "cuda"
-
-
 def pack_planes(normal, d, centroid, u, v, frames=None):
     """uoc_plane records [B,21] int32 (host) with found = 1 from the plane normal.p + d = 0, a point `centroid` on it and
     the in-plane axes u, v; arrays [B,3] / [3] and d [B] / scalar, metres, rounded to float32."""
@@ -124,7 +120,7 @@ def free_space(labels, xyz, plane, grid=256, cell=0.010, h_obs=0.010, tau=0.010,
         raise ValueError(f"min_pts = {min_pts} outside 1..{_native.PLACE_MAX_MIN_PTS}")
     qs = _check_queries(queries)
     for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _on_gpu(t):
+        if not _native.on_gpu(t):
             raise _native.NativeError(f"free_space: {what} must be a tensor on the GPU (there is no CPU fallback)")
     if labels.dim() == 2:
         labels = labels[None]
@@ -143,7 +139,7 @@ def free_space(labels, xyz, plane, grid=256, cell=0.010, h_obs=0.010, tau=0.010,
         planes = getattr(plane, "records", None)
         if planes is None:
             raise _native.NativeError("free_space: plane is neither a fit_plane result nor (normal, d, centroid, u, v)")
-    if not _on_gpu(planes) or planes.device != labels.device or planes.dtype != torch.int32 \
+    if not _native.on_gpu(planes) or planes.device != labels.device or planes.dtype != torch.int32 \
             or tuple(planes.shape) != (B, _PLANE_WORDS):
         raise _native.NativeError(f"free_space: the plane records do not match the {B} frames on {labels.device}")
     lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
@@ -200,13 +196,27 @@ def camera_to_cell(result, b, xyz):
     return a // div + result.grid // 2, bv // div + result.grid // 2
 
 
+def plane_axes(planes, b):
+    """(normal, centroid, u, v) of frame b: float64 [3] each on the host, from uoc_plane records [B,21] int32 (a tensor on
+    any device or a numpy array).  One small host read."""
+    rec = planes[b]
+    rec = rec.cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
+    p = np.ascontiguousarray(rec).view(np.float32).astype(np.float64)
+    return tuple(p[_OFF[k]:_OFF[k] + 3] for k in ("normal", "centroid", "u", "v"))
+
+
+def grid_point(origin, u, v, grid, cell_mm, a, b):
+    """The point of the plane at the grid coordinates (a, b), in cells and fractions of one: origin + (a - G/2) cell u +
+    (b - G/2) cell v.  Cell (i, j) spans [i, i+1) x [j, j+1): its centre is (i + 0.5, j + 0.5)."""
+    cell = cell_mm / 1000.0
+    return origin + (a - grid // 2) * cell * u + (b - grid // 2) * cell * v
+
+
 def cell_to_camera(result, b, i, j):
     """The centre of cell (i, j) of frame b on the plane, in camera coordinates (metres): centroid + a u + b v, float64
     on the host from the plane record."""
-    rec = result.planes[b].cpu().numpy().view(np.float32).astype(np.float64)
-    c, u, v = (rec[_OFF[k]:_OFF[k] + 3] for k in ("centroid", "u", "v"))
-    cell = result.cell_mm / 1000.0
-    return c + (int(i) - result.grid // 2 + 0.5) * cell * u + (int(j) - result.grid // 2 + 0.5) * cell * v
+    _, c, u, v = plane_axes(result.planes, b)
+    return grid_point(c, u, v, result.grid, result.cell_mm, int(i) + 0.5, int(j) + 0.5)
 
 
 def free_mask(result, radius):

@@ -30,10 +30,6 @@ class RelationResult:
         self.__dict__.update(fields)
 
 
-def _on_gpu(t):
-    return isinstance(t, torch.Tensor) and t.device.type == "cuda"
-
-
 def relation_records(labels, xyz, connectivity, gap_mm, min_pairs):
     """The raw uoc_relations call: (pairs [B,3,128,128] int32, objects [B,128,11] int32 holding uoc_relation_object), on
     the device, no synchronisation.  labels int32 [B,H,W] and xyz float32 [B,3,H,W] contiguous on one GPU."""
@@ -66,7 +62,7 @@ def relate(labels, xyz, connectivity=4, gap=0.015, min_pairs=8) -> RelationResul
     if int(min_pairs) < 1:
         raise ValueError(f"min_pairs = {min_pairs} is below 1")
     for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _on_gpu(t):
+        if not _native.on_gpu(t):
             raise _native.NativeError(f"relate: {what} must be a tensor on the GPU (there is no CPU fallback)")
     if labels.dim() == 2:
         labels = labels[None]

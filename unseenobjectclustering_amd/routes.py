@@ -65,7 +65,7 @@ def _check_queries(queries, G=None):
 def _call(state, owner, frame, queries, unknown_blocks, max_path):
     """uoc_routes; returns (cost, info, path, workspace).  The workspace's first B*Q int32 words are the sweeps taken."""
     for t, what in ((state, "state"), (owner, "owner")):
-        if not (isinstance(t, torch.Tensor) and t.device.type == "cuda"):
+        if not _native.on_gpu(t):
             raise _native.NativeError(f"routes: {what} must be a tensor on the GPU (there is no CPU fallback)")
     state, owner = (t[None] if t.dim() == 2 else t for t in (state, owner))
     if state.dim() != 3 or state.shape[1] != state.shape[2] or tuple(owner.shape) != tuple(state.shape) or owner.device != state.device:
@@ -180,4 +180,6 @@ def path_to_camera(result, b, q):
     w = waypoints(result, b, q)
     if w is None:
         return None
-    return np.array([_placement.cell_to_camera(result, b, i, j) for i, j in w.cells.tolist()], np.float64).reshape(len(w.cells), 3)
+    _, c, u, v = _placement.plane_axes(result.planes, b)
+    return np.array([_placement.grid_point(c, u, v, result.grid, result.cell_mm, i + 0.5, j + 0.5) for i, j in w.cells.tolist()],
+                    np.float64).reshape(len(w.cells), 3)
