@@ -147,7 +147,7 @@ def test_fit_plane_argument_handling_with_the_native_call_stubbed(monkeypatch):
         return (torch.zeros(B, support._PW, dtype=torch.int32), torch.zeros(B, 128, support._OW, dtype=torch.int32),
                 torch.zeros(B, H, W) if height_map else None)
 
-    monkeypatch.setattr(support, "_on_gpu", lambda t: isinstance(t, torch.Tensor))
+    monkeypatch.setattr(_native, "on_gpu", lambda t: isinstance(t, torch.Tensor))
     monkeypatch.setattr(support, "plane_records", stub)
     res = support.fit_plane(lab, xyz, num_hyp=7, tau=0.0126, seed=-1, height_map=True)
     labels, xyz_, num_hyp, tau_mm, seed, height_map = calls[-1]

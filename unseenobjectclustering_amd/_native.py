@@ -339,6 +339,49 @@ def on_gpu(t) -> bool:
     return isinstance(t, torch.Tensor) and t.device.type == "cuda"
 
 
+class Fields:
+    """Base of every result class: the keyword arguments become the attributes.  A result class derives from it and adds
+    its name, its docstring and what methods it has."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def as_labels(labels):
+    """A label map as the kernels read it: int32 and contiguous; a tensor that already is comes back itself."""
+    import torch
+    return (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
+
+
+def label_input(who, labels):
+    """The labels-only input check: `labels` on the GPU, else `who`'s NativeError, then as_labels.  Shapes are the
+    caller's: the stages that take labels alone differ in what they accept."""
+    if not on_gpu(labels):
+        raise NativeError(f"{who}: labels must be a tensor on the GPU (there is no CPU fallback)")
+    return as_labels(labels)
+
+
+def frame_inputs(who, labels, xyz):
+    """The input check of every stage that takes a label map with its XYZ planes: both on the GPU, [H,W] and [3,H,W]
+    batched to B = 1, [B,H,W] against [B,3,H,W], one device; else `who`'s NativeError.  Returns (labels int32, xyz
+    float32), both contiguous; a tensor that already is comes back itself, so the hot path copies nothing."""
+    import torch
+    for t, what in ((labels, "labels"), (xyz, "xyz")):
+        if not on_gpu(t):
+            raise NativeError(f"{who}: {what} must be a tensor on the GPU (there is no CPU fallback)")
+    if labels.dim() == 2:
+        labels = labels[None]
+    if xyz.dim() == 3:
+        xyz = xyz[None]
+    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
+            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
+        raise NativeError(f"{who}: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
+                          "([B,H,W] and [B,3,H,W])")
+    if xyz.device != labels.device:
+        raise NativeError(f"{who}: labels and xyz are on different devices")
+    return as_labels(labels), xyz.to(torch.float32).contiguous()
+
+
 def ptr(t):
     """Device (or host) pointer of a torch tensor as c_void_p; None -> NULL."""
     if t is None:

@@ -27,15 +27,13 @@ def split_components(labels, connectivity=8, min_area=1, mode="all"):
     """labels: device tensor [H,W], [1,H,W] or [B,H,W] of int32 / int64 / float ids.  Returns (out, table, counts) on the
     device: out int32 of the input's shape with values 0..127; table [B,128,4] int32 = src, area, root, siblings per
     new id (mode "all") or raw id (mode "largest"); counts [B,4] int32 = found, small, kept, dropped."""
-    if not isinstance(labels, torch.Tensor) or labels.device.type != "cuda":
-        raise _native.NativeError("split_components: labels must be a tensor on the GPU (there is no CPU fallback)")
+    lab = _native.label_input("split_components", labels)
     if mode not in _native.CC_MODES:
         raise ValueError(f"mode = {mode!r} is neither 'all' nor 'largest'")
     if connectivity not in (4, 8):
         raise ValueError(f"connectivity = {connectivity} is neither 4 nor 8")
     if int(min_area) < 1:
         raise ValueError(f"min_area = {min_area} below 1")
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
     if lab.dim() not in (2, 3):
         raise _native.NativeError(f"split_components: labels {tuple(labels.shape)} must be [H,W] or [B,H,W]")
     lab3 = lab[None] if lab.dim() == 2 else lab

@@ -26,34 +26,25 @@ ONE = _native.CONF_ONE
 STAT_FIELDS = ("pixels", "sum_q", "min_q", "weak")
 
 
-class AssignConfidence:
+class AssignConfidence(_native.Fields):
     """Device tensors of one uoc_ms_confidence call over B fields of n pixels: labels [B,n] int32 (what the clustering's
     assignment writes, bit for bit), margin [B,n] float32, second [B,n] int32 (-1: every seed carries the pixel's label),
     closest and rival [B,n] int32 (seed indices; rival -1 likewise)."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class ConfidenceSummary:
+class ConfidenceSummary(_native.Fields):
     """Per id 0..127 of every frame (row 0: the background), host numpy arrays [B,128]: pixels, min (the smallest q /
     65536), weak (pixels with q < weak_q), mean = sum_q / pixels / 65536 and weak_share = weak / pixels as float64 (NaN
     for an id without pixels); stats: the raw table [B,128,4] int64 (STAT_FIELDS) on the device; weak_q: the threshold."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class FrameConfidence:
+class FrameConfidence(_native.Fields):
     """segment_confidence's third item.  margin1 [B,H,W] float32 and second1 [B,H,W] int32: stage 1 (second1 in the
     numbering of the clustering, before the depth filter); margin [H,W] float32: the final map of item 0; per_object: the
     ConfidenceSummary of (final label map, margin); rois: the number of stage-1 ROIs; stage2: None without ROIs, else what
     the final map was pasted from: margin_crop [K,S*S] float32, labels_crop [K,S*S] int32, table (the uoc_roi_table bytes),
     plan [K + K*128] int32 and labels1 [H*W] int32, the filtered stage-1 map of item 0.  Device tensors but for
     per_object's host arrays."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def _device_f32(t, what):
@@ -131,14 +122,13 @@ def summarize(labels, conf, weak=0.02) -> ConfidenceSummary:
     """The per-id summary of a (label map, value map) pair: labels [B,H,W] or [H,W] of int32 / int64 / float ids (the maps
     test_sample returns are float32), conf of the same shape, float32.  A pixel counts as weak when its q =
     floor(conf * 65536) is below ceil(weak * 65536).  One small read of the table (synchronises)."""
-    for t, what in ((labels, "labels"), (conf, "conf")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise _native.NativeError(f"summarize: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if labels.dim() == 2:
-        labels, conf = labels[None], conf[None] if conf.dim() == 2 else conf
-    if labels.dim() != 3 or tuple(conf.shape) != tuple(labels.shape) or conf.device != labels.device:
-        raise _native.NativeError(f"summarize: labels {tuple(labels.shape)} and conf {tuple(conf.shape)} do not match ([B,H,W])")
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
+    lab = _native.label_input("summarize", labels)
+    if not _native.on_gpu(conf):
+        raise _native.NativeError("summarize: conf must be a tensor on the GPU (there is no CPU fallback)")
+    if lab.dim() == 2:
+        lab, conf = lab[None], conf[None] if conf.dim() == 2 else conf
+    if lab.dim() != 3 or tuple(conf.shape) != tuple(lab.shape) or conf.device != lab.device:
+        raise _native.NativeError(f"summarize: labels {tuple(lab.shape)} and conf {tuple(conf.shape)} do not match ([B,H,W])")
     weak_q = weak_to_q(weak)
     stats = object_stats(lab, conf.to(torch.float32).contiguous(), weak_q)
     h = stats.cpu().numpy()

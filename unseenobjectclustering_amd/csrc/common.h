@@ -122,5 +122,40 @@ __device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
   for (int sft = 32; sft > 0; sft >>= 1) v = max(v, (unsigned long long)__shfl_xor((long long)v, sft));
   return v;
 }
+// The unsigned maximum: a DPP tree per 16-lane row, then the four rows.  All 64 lanes active.
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+  v = max(v, (unsigned)dpp_i<0xB1>((int)v));
+  v = max(v, (unsigned)dpp_i<0x4E>((int)v));
+  v = max(v, (unsigned)dpp_i<0x141>((int)v));
+  v = max(v, (unsigned)dpp_i<0x140>((int)v));
+  const unsigned a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
+  const unsigned c = __builtin_amdgcn_readlane((int)v, 32), d = __builtin_amdgcn_readlane((int)v, 48);
+  return max(max(a, b), max(c, d));
+}
+__device__ __forceinline__ int lane_rank(unsigned long long mask) {  // set bits of mask below this lane
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+// The wave-group loop.  Every distinct key >= 0 among the wave's lanes gets one turn, in the order of the lowest lane
+// that holds it: body(c, mask, first) with the key, the ballot of the lanes holding it and the lowest of them.  Every
+// lane of the wave must call this, and every lane runs the body, so the body may ballot and reduce over the wave; what
+// only one lane should do, it does under `lane == first`.
+template <typename Body>
+__device__ __forceinline__ void for_each_wave_key(int key, Body body) {
+  unsigned long long rem = __ballot(key >= 0);
+  while (rem) {
+    const int first = __ffsll((long long)rem) - 1;
+    const int c = __builtin_amdgcn_readlane(key, first);
+    const unsigned long long m = __ballot(key == c);
+    rem &= ~m;
+    body(c, m, first);
+  }
+}
+// Its commonest user: table[c] += weight * (lanes holding c), one atomic per distinct key c.
+__device__ __forceinline__ void wave_add_keys(int *__restrict__ table, int key, int weight, int lane) {
+  for_each_wave_key(key, [&](int c, unsigned long long m, int first) {
+    if (lane == first) atomicAdd(&table[c], weight * (int)__popcll(m));
+  });
+}
 
 }  // namespace uoc

@@ -28,14 +28,13 @@
 // "same" = inside the image with id c):  W if same;  N if same and not (W and NW same);  with connectivity 8 also NW if
 // same and neither N nor W same, and NE if same and N not same.  The skipped pairs are joined through the others
 // (induction along the row), so the partition is that of the full neighbourhood.
-#include "common.h"
+#include "labelmap.h"
 
 #include <limits.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;                 // ids 0..127; 1..127 are objects
 constexpr int TW = 32, TH = 32;         // tile of tile_kernel; one thread per pixel
 constexpr int TILE_THREADS = TW * TH;
 constexpr int PIX_THREADS = 1024;       // pixels per block of the per-pixel kernels
@@ -64,13 +63,6 @@ struct Frame {
 __device__ __forceinline__ Frame frame_of(void *ws, const Layout &l, int b) {
   char *p = (char *)ws + l.stride * b;
   return Frame{(int *)p, (int *)(p + l.off_blk), (int *)(p + l.off_parent), (int *)(p + l.off_cnt)};
-}
-
-// Object id of a raw label: 1..127, anything else (negatives included) is background.
-__device__ __forceinline__ int obj_id(int l) { return ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0; }
-
-__device__ __forceinline__ int lane_rank(u64 mask) {  // set bits of mask below this lane
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 // ---- union-find in LDS ------------------------------------------------------------------------------------------------
@@ -213,10 +205,10 @@ __global__ __launch_bounds__(PIX_THREADS) void flatten_kernel(void *__restrict__
 template <bool LARGEST>
 __global__ __launch_bounds__(PIX_THREADS) void stats_kernel(const int *__restrict__ labels, void *__restrict__ ws, Layout lay,
                                                             long long n, int min_area) {
-  __shared__ int s_sib[NL], s_small, s_surv;
-  __shared__ u64 s_best[NL];
+  __shared__ int s_sib[NUM_IDS], s_small, s_surv;
+  __shared__ u64 s_best[NUM_IDS];
   const int tid = threadIdx.x, b = blockIdx.y;
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     s_sib[tid] = 0;
     s_best[tid] = 0ull;
   }
@@ -238,7 +230,7 @@ __global__ __launch_bounds__(PIX_THREADS) void stats_kernel(const int *__restric
     if (surv) atomicAdd(&s_surv, (int)__popcll(surv));
   }
   __syncthreads();
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     if (s_sib[tid]) atomicAdd(&f.hdr[HDR_SIB + tid], s_sib[tid]);
     if (LARGEST && s_best[tid]) atomicMax(reinterpret_cast<u64 *>(f.hdr + HDR_BEST) + tid, s_best[tid]);
   }
@@ -251,7 +243,7 @@ __global__ __launch_bounds__(PIX_THREADS) void stats_kernel(const int *__restric
 // ---- 5. plan: block bases, counts, LARGEST's table ----------------------------------------------------------------------------
 __global__ __launch_bounds__(PIX_THREADS) void plan_kernel(void *__restrict__ ws, Layout lay, int largest,
                                                            int *__restrict__ table, int *__restrict__ counts) {
-  __shared__ int s_scan[PIX_THREADS], s_found[NL], s_kept[NL];
+  __shared__ int s_scan[PIX_THREADS], s_found[NUM_IDS], s_kept[NUM_IDS];
   const int tid = threadIdx.x, b = blockIdx.x;
   const Frame f = frame_of(ws, lay, b);
   // exclusive scan of the per-block counts: a contiguous segment per thread, then a scan of the segment sums
@@ -274,8 +266,8 @@ __global__ __launch_bounds__(PIX_THREADS) void plan_kernel(void *__restrict__ ws
     f.blk[k] = run;
     run += v;
   }
-  int *T = table + (size_t)b * NL * 4;
-  if (tid < NL) {
+  int *T = table + (size_t)b * NUM_IDS * 4;
+  if (tid < NUM_IDS) {
     const int sib = tid ? f.hdr[HDR_SIB + tid] : 0;
     s_found[tid] = sib;
     int4 row = make_int4(0, 0, 0, 0);
@@ -293,11 +285,11 @@ __global__ __launch_bounds__(PIX_THREADS) void plan_kernel(void *__restrict__ ws
   __syncthreads();
   if (tid == 0) {
     int found = 0, kept = 0;
-    for (int k = 1; k < NL; ++k) {
+    for (int k = 1; k < NUM_IDS; ++k) {
       found += s_found[k];
       kept += s_kept[k];
     }
-    if (!largest) kept = total < NL - 1 ? total : NL - 1;
+    if (!largest) kept = total < NUM_IDS - 1 ? total : NUM_IDS - 1;
     int *C = counts + (size_t)b * 4;
     C[0] = found;
     C[1] = f.hdr[HDR_SMALL];
@@ -324,10 +316,10 @@ __global__ __launch_bounds__(PIX_THREADS) void rank_kernel(const int *__restrict
   if (surv) {
     int rank = f.blk[blockIdx.x] + lane_rank(bal);
     for (int k = 0; k < wave; ++k) rank += s_wave[k];
-    if (rank < NL - 1) {
+    if (rank < NUM_IDS - 1) {
       id = rank + 1;
       const int c = obj_id(labels[(size_t)b * n + i]);
-      reinterpret_cast<int4 *>(table + (size_t)b * NL * 4)[id] = make_int4(c, area, (int)i, f.hdr[HDR_SIB + c]);
+      reinterpret_cast<int4 *>(table + (size_t)b * NUM_IDS * 4)[id] = make_int4(c, area, (int)i, f.hdr[HDR_SIB + c]);
     }
   }
   f.cnt[i] = id;
@@ -337,11 +329,11 @@ __global__ __launch_bounds__(PIX_THREADS) void rank_kernel(const int *__restrict
 template <int V, bool LARGEST>
 __global__ __launch_bounds__(256) void write_kernel(const int *__restrict__ labels, void *__restrict__ ws, Layout lay,
                                                     long long n, int *__restrict__ out) {
-  __shared__ int s_win[NL];   // LARGEST: root of the id's winner
+  __shared__ int s_win[NUM_IDS];   // LARGEST: root of the id's winner
   const int tid = threadIdx.x, b = blockIdx.y;
   const Frame f = frame_of(ws, lay, b);
   if (LARGEST) {
-    if (tid < NL) {
+    if (tid < NUM_IDS) {
       const u64 best = reinterpret_cast<const u64 *>(f.hdr + HDR_BEST)[tid];
       s_win[tid] = (tid && best) ? (int)~(unsigned)best : -2;
     }

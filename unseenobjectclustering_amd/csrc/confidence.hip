@@ -3,7 +3,7 @@
 //   uoc_conf_objects  conf_objects_kernel  per-id integer summary (pixels, sum, min, weak) of a (label map, value map) pair
 //                     + conf_finish_kernel the minimum out of its accumulator form
 // Every result is an integer sum, an integer minimum or a copied float: defined exactly, independent of launch order and batch.
-#include "common.h"
+#include "labelmap.h"
 #include "prof.h"
 
 #include <limits.h>
@@ -11,7 +11,6 @@
 
 namespace uoc {
 
-constexpr int NL = UOC_MAX_SEEDS;  // label ids are < 128
 constexpr int QONE = 65536;        // the fixed-point unit of a confidence value
 
 // Source index of frame coordinate c (relative to the box start) in a crop of S along an axis of `len` frame pixels: the
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(256) void conf_paste_kernel(const float *__restrict
       const int sx = paste_src_index(x - x0, S, x1 - x0 + 1);
       const size_t src = (size_t)k * SS + sy * S + sx;
       const int l = labels_crop[src];
-      const int v = ((unsigned)l < (unsigned)NL) ? map[k * NL + l] : 0;
+      const int v = ((unsigned)l < (unsigned)NUM_IDS) ? map[k * NUM_IDS + l] : 0;
       if (v != 0) {
         out[p] = values_crop[src];
         break;
@@ -56,29 +55,18 @@ __device__ __forceinline__ int conf_quantise(float c) {
   return (int)(c * (float)QONE);       // exact product (a power of two), truncated
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v = max(v, __shfl_xor(v, sft));
-  return v;
-}
-
 // stats [B][128][4] int64, zero-filled: (pixels, sum_q, 65536 - min_q as a maximum with 0 = empty, weak).  Equal labels of a
-// wave are combined before the LDS atomics (the distinct-cell loop of csrc/elevation.hip), a block's rows before the
+// wave are combined before the LDS atomics (for_each_wave_key of common.h), a block's rows before the
 // global ones.
 __global__ __launch_bounds__(256) void conf_objects_kernel(const int *__restrict__ labels, const float *__restrict__ conf,
                                                            int n, int weak_q, long long *__restrict__ stats) {
-  __shared__ int s_pix[NL], s_inv[NL], s_weak[NL];
-  __shared__ unsigned long long s_sum[NL];
+  __shared__ int s_pix[NUM_IDS], s_inv[NUM_IDS], s_weak[NUM_IDS];
+  __shared__ unsigned long long s_sum[NUM_IDS];
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y;
   labels += (size_t)b * n;
   conf += (size_t)b * n;
-  stats += (size_t)b * NL * 4;
-  if (tid < NL) {
+  stats += (size_t)b * NUM_IDS * 4;
+  if (tid < NUM_IDS) {
     s_pix[tid] = 0;
     s_inv[tid] = 0;
     s_weak[tid] = 0;
@@ -89,29 +77,24 @@ __global__ __launch_bounds__(256) void conf_objects_kernel(const int *__restrict
     const int p = base + tid;
     int l = -1, qv = 0;
     if (p < n) {
-      l = labels[p];
-      if ((unsigned)l >= (unsigned)NL) l = -1;
+      l = label_row(labels[p]);
       qv = conf_quantise(conf[p]);
     }
-    unsigned long long rem = __ballot(l >= 0);
-    while (rem) {   // per distinct label of the wave
-      const int first = __ffsll((long long)rem) - 1;
-      const int c = __builtin_amdgcn_readlane(l, first);
+    for_each_wave_key(l, [&](int c, unsigned long long m, int first) {   // per distinct label of the wave
       const bool hit = l == c;
-      const unsigned long long m = __ballot(hit), mw = __ballot(hit && qv < weak_q);
-      rem &= ~m;
-      const int sm = wave_sum_i(hit ? qv : 0);            // <= 64 * 65535
-      const int inv = wave_max_i(hit ? QONE - qv : 0);
+      const unsigned long long mw = __ballot(hit && qv < weak_q);
+      const int sm = wave_sum(hit ? qv : 0);            // <= 64 * 65535
+      const int inv = wave_max(hit ? QONE - qv : 0);
       if (lane == first) {
         atomicAdd(&s_pix[c], __popcll(m));
         atomicAdd(&s_sum[c], (unsigned long long)sm);
         atomicMax(&s_inv[c], inv);
         if (mw) atomicAdd(&s_weak[c], __popcll(mw));
       }
-    }
+    });
   }
   __syncthreads();
-  if (tid < NL && s_pix[tid]) {
+  if (tid < NUM_IDS && s_pix[tid]) {
     unsigned long long *row = reinterpret_cast<unsigned long long *>(stats) + 4 * tid;
     atomicAdd(row + 0, (unsigned long long)s_pix[tid]);
     atomicAdd(row + 1, s_sum[tid]);
@@ -144,7 +127,7 @@ int uoc_conf_paste(const float *d_values_crop, const int32_t *d_labels_crop, con
   UOC_REQUIRE(d_table != nullptr, "uoc_conf_paste: d_table is null");
   UOC_REQUIRE(d_plan != nullptr, "uoc_conf_paste: d_plan is null");
   UOC_REQUIRE(d_out != nullptr, "uoc_conf_paste: d_out is null");
-  UOC_REQUIRE(K >= 1 && K < NL, "uoc_conf_paste: K = %d outside [1, %d]", K, NL - 1);
+  UOC_REQUIRE(K >= 1 && K < NUM_IDS, "uoc_conf_paste: K = %d outside [1, %d]", K, NUM_IDS - 1);
   UOC_REQUIRE(S >= 1 && S <= 4096, "uoc_conf_paste: S = %d outside [1, 4096]", S);
   UOC_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= UOC_CONF_MAX_N, "uoc_conf_paste: bad shape H = %d, W = %d (H * W in 1..%d)", H, W,
               UOC_CONF_MAX_N);
@@ -152,7 +135,7 @@ int uoc_conf_paste(const float *d_values_crop, const int32_t *d_labels_crop, con
     struct Span { const char *name; const void *p; size_t bytes; };
     const size_t crops = (size_t)K * S * S * 4;
     const Span in[4] = {{"d_values_crop", d_values_crop, crops}, {"d_labels_crop", d_labels_crop, crops},
-                        {"d_table", d_table, sizeof(uoc_roi_table)}, {"d_plan", d_plan, ((size_t)K + (size_t)K * NL) * 4}};
+                        {"d_table", d_table, sizeof(uoc_roi_table)}, {"d_plan", d_plan, ((size_t)K + (size_t)K * NUM_IDS) * 4}};
     const uintptr_t a = (uintptr_t)d_out;
     const size_t n = (size_t)H * W * 4;
     for (const Span &i : in) {
@@ -179,7 +162,7 @@ int uoc_conf_objects(const int32_t *d_labels, const float *d_conf, int B, int H,
   UOC_REQUIRE(weak_q >= 0 && weak_q <= QONE - 1, "uoc_conf_objects: weak_q = %d outside [0, %d]", weak_q, QONE - 1);
   UOC_REQUIRE(((uintptr_t)d_stats & 7) == 0, "uoc_conf_objects: d_stats is not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const int n = H * W, rows = B * NL;
+  const int n = H * W, rows = B * NUM_IDS;
   ProfScope prof(KC_CONF_GLUE, st, 0.0, 8.0 * B * n + 32.0 * rows);
   UOC_HIP_CHECK(hipMemsetAsync(d_stats, 0, (size_t)rows * 4 * sizeof(int64_t), st));
   int gx = conf_grid(n);

@@ -43,7 +43,7 @@ constexpr int MAX_Q = UOC_ELEV_MAX_QUERIES;
 constexpr int KEY_BIAS = 1024;      // key = hq + 1024 >= 24: a word of 0 means "no point"
 constexpr int HQ_MAX = 32767;
 
-static_assert(((HQ_MAX + KEY_BIAS) << 7 | (NL - 1)) > 0, "a word is a positive int");
+static_assert(((HQ_MAX + KEY_BIAS) << 7 | (NUM_IDS - 1)) > 0, "a word is a positive int");
 
 struct Queries {
   int v[MAX_Q][4];  // need2, id, hmin_mm, hmax_mm
@@ -57,7 +57,7 @@ __device__ __forceinline__ bool project(const Frame &f, int cell_div, int t_low,
   return project_point(f, cell_div, t_low, G, x, y, z, [&](int i, int j, long long T) {
     const long long hq = min(T >> 14, (long long)HQ_MAX);  // arithmetic shift: a floor; hq >= -tau_mm >= -1000
     cell = i * G + j;
-    word = (((int)hq + KEY_BIAS) << 7) | label_id(l);
+    word = (((int)hq + KEY_BIAS) << 7) | obj_id(l);
   });
 }
 
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(STRIP *SEGS) void cell_kernel(const int *__restrict
     const int t = top[a], np = pts[a];
     const bool sol = found && near[a] >= min_pts;  // near <= pts: a solid cell has a point
     elev[a] = np > 0 ? (t >> 7) - KEY_BIAS : UOC_ELEV_NONE;
-    owner[a] = np > 0 ? (t & (NL - 1)) : 0;
+    owner[a] = np > 0 ? (t & (NUM_IDS - 1)) : 0;
     known += np > 0;
     solid += sol;
     bool blk = !sol || i == 0 || j == 0 || i == G - 1 || j == G - 1;
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(STRIP *SEGS) void cell_kernel(const int *__restrict
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int t2 = top[a + d[k]];
-        const bool ok = near[a + d[k]] >= min_pts && ((t2 ^ t) & (NL - 1)) == 0 && abs((t2 >> 7) - (t >> 7)) <= step_mm;
+        const bool ok = near[a + d[k]] >= min_pts && ((t2 ^ t) & (NUM_IDS - 1)) == 0 && abs((t2 >> 7) - (t >> 7)) <= step_mm;
         blk = blk || !ok;
       }
     }
@@ -156,13 +156,13 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
                                                           int *__restrict__ dist2, Acc acc) {
   __shared__ __attribute__((aligned(16))) int s_g2[MAX_G];
   __shared__ unsigned long long s_qkey[MAX_Q];
-  __shared__ int s_cells[NL], s_level[NL], s_emax[NL], s_sum[NL];  // a row's sum: at most 512 * 32767
-  __shared__ unsigned long long s_key[NL];
+  __shared__ int s_cells[NUM_IDS], s_level[NUM_IDS], s_emax[NUM_IDS], s_sum[NUM_IDS];  // a row's sum: at most 512 * 32767
+  __shared__ unsigned long long s_key[NUM_IDS];
   const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x, b = blockIdx.y;
   const size_t off = ((size_t)b * G + i) * G;
   row_fill_g2(s_g2, dist2 + off, G);
   if (tid < MAX_Q) s_qkey[tid] = 0ull;
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     s_cells[tid] = s_level[tid] = s_emax[tid] = s_sum[tid] = 0;
     s_key[tid] = 0ull;
   }
@@ -184,15 +184,9 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
     }
     const bool lvl = code >= 0 && best > 0;  // not blocking: level
     const unsigned long long wide = lvl ? widest_key(best, i * G + j) : 0ull;
-    const int own = code;
-    unsigned long long rem = __ballot(code >= 0);
-    while (rem) {  // per distinct owner of the wave
-      const int first = __ffsll((long long)rem) - 1;
-      const int c = __builtin_amdgcn_readlane(code, first);
+    for_each_wave_key(code, [&](int c, unsigned long long m, int first) {  // per distinct owner of the wave
       const bool hit = code == c;
-      const unsigned long long m = __ballot(hit), ml = __ballot(hit && lvl);
-      rem &= ~m;
-      if (hit) code = -1;
+      const unsigned long long ml = __ballot(hit && lvl);
       const int em = wave_max(hit ? el + KEY_BIAS : 0);
       unsigned long long k64 = 0ull;
       int sm = 0;
@@ -209,13 +203,13 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
           atomicAdd(&s_sum[c], sm);
         }
       }
-    }
+    });
     if (Q > 0 && lvl) {
 #pragma unroll
       for (int q = 0; q < MAX_Q; ++q) {
         if (q < Q) {  // uniform
           const int id = qs.v[q][1];
-          const bool cand = el >= qs.v[q][2] && el <= qs.v[q][3] && (id < 0 ? own >= 1 : own == id);
+          const bool cand = el >= qs.v[q][2] && el <= qs.v[q][3] && (id < 0 ? code >= 1 : code == id);
           qkey[q] = max(qkey[q], cand ? wide : 0ull);
         }
       }
@@ -230,8 +224,8 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
   }
   __syncthreads();
   if (tid < Q && s_qkey[tid]) atomicMax(&acc.qkey[(size_t)b * MAX_Q + tid], s_qkey[tid]);
-  if (tid < NL && s_cells[tid]) {
-    const size_t a = (size_t)b * NL + tid;
+  if (tid < NUM_IDS && s_cells[tid]) {
+    const size_t a = (size_t)b * NUM_IDS + tid;
     atomicAdd(&acc.cells[a], s_cells[tid]);
     atomicMax(&acc.emax[a], s_emax[tid]);
     if (s_level[tid]) {
@@ -243,10 +237,10 @@ __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict_
 }
 
 // ---- 5. the rows of tops and the answers -------------------------------------------------------------------------------
-__global__ __launch_bounds__(NL) void answer_kernel(Acc acc, const int *__restrict__ elev, int G, Queries qs, int Q,
+__global__ __launch_bounds__(NUM_IDS) void answer_kernel(Acc acc, const int *__restrict__ elev, int G, Queries qs, int Q,
                                                     int *__restrict__ tops, int *__restrict__ answers) {
   const int a = threadIdx.x, b = blockIdx.x;
-  const size_t r = (size_t)b * NL + a;
+  const size_t r = (size_t)b * NUM_IDS + a;
   const int cells = acc.cells[r], level = acc.level[r];
   int row[8] = {cells, level, -1, -1, 0, 0, cells ? acc.emax[r] - KEY_BIAS : 0, 0};
   if (level) {
@@ -296,11 +290,11 @@ Ws carve(void *base, int B, int G) {
     return q;
   };
   w.top = (int *)take((size_t)B * G * G * sizeof(int));
-  w.acc.cells = (int *)take((size_t)B * NL * sizeof(int));
-  w.acc.level = (int *)take((size_t)B * NL * sizeof(int));
-  w.acc.emax = (int *)take((size_t)B * NL * sizeof(int));
-  w.acc.key = (unsigned long long *)take((size_t)B * NL * sizeof(unsigned long long));
-  w.acc.sum = (unsigned long long *)take((size_t)B * NL * sizeof(unsigned long long));
+  w.acc.cells = (int *)take((size_t)B * NUM_IDS * sizeof(int));
+  w.acc.level = (int *)take((size_t)B * NUM_IDS * sizeof(int));
+  w.acc.emax = (int *)take((size_t)B * NUM_IDS * sizeof(int));
+  w.acc.key = (unsigned long long *)take((size_t)B * NUM_IDS * sizeof(unsigned long long));
+  w.acc.sum = (unsigned long long *)take((size_t)B * NUM_IDS * sizeof(unsigned long long));
   w.acc.qkey = (unsigned long long *)take((size_t)B * MAX_Q * sizeof(unsigned long long));
   w.total = at;
   return w;
@@ -349,7 +343,7 @@ int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_
     for (int k = 0; k < 4; ++k) qs.v[q][k] = q < Q ? h_queries[q * 4 + k] : 0;
   for (int q = 0; q < Q; ++q) {
     UOC_REQUIRE(qs.v[q][0] >= 0 && qs.v[q][0] <= (1 << 30), "uoc_elevation: query %d: need2 = %d outside [0, 2^30]", q, qs.v[q][0]);
-    UOC_REQUIRE(qs.v[q][1] >= -1 && qs.v[q][1] < NL, "uoc_elevation: query %d: id = %d outside [-1, 127]", q, qs.v[q][1]);
+    UOC_REQUIRE(qs.v[q][1] >= -1 && qs.v[q][1] < NUM_IDS, "uoc_elevation: query %d: id = %d outside [-1, 127]", q, qs.v[q][1]);
     UOC_REQUIRE(qs.v[q][2] >= -32768 && qs.v[q][2] <= 32767 && qs.v[q][3] >= -32768 && qs.v[q][3] <= 32767,
                 "uoc_elevation: query %d: band (%d, %d) outside [-32768, 32767]", q, qs.v[q][2], qs.v[q][3]);
   }
@@ -378,7 +372,7 @@ int uoc_elevation(const int32_t *d_labels, const float *d_xyz, const int64_t *d_
     hipLaunchKernelGGL(cell_kernel, dim3((G + STRIP - 1) / STRIP, B), dim3(STRIP * SEGS), 0, st, w.top, d_pts, d_near, frame, G,
                        step_mm, min_pts, d_elev, d_owner, d_dist2, d_info);
     hipLaunchKernelGGL(row_kernel, dim3(G, B), dim3(ROW_THREADS), 0, st, d_elev, d_owner, d_near, G, min_pts, qs, Q, d_dist2, w.acc);
-    hipLaunchKernelGGL(answer_kernel, dim3(B), dim3(NL), 0, st, w.acc, d_elev, G, qs, Q, d_tops, d_answers);
+    hipLaunchKernelGGL(answer_kernel, dim3(B), dim3(NUM_IDS), 0, st, w.acc, d_elev, G, qs, Q, d_tops, d_answers);
   }
   UOC_LAUNCH_CHECK();
   return UOC_OK;

@@ -42,9 +42,6 @@ __device__ __forceinline__ double wave_max_d(double v) {
   v = fmax(v, dpp_d<0x140>(v));
   return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
 }
-__device__ __forceinline__ int lane_rank(unsigned long long mask) {  // set bits of mask below this lane
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // Cyclic Jacobi on a symmetric 3x3 in fp64: a becomes diagonal, the columns of v the eigenvectors.
 __device__ inline void jacobi3(double a[3][3], double v[3][3]) {

@@ -282,7 +282,7 @@ int uoc_footprint(const int32_t *d_state, const int32_t *d_owner, const int32_t 
                 "uoc_footprint: rectangle %d: half extents HL = %d, HW = %d outside [0, %d]", f, v[0], v[1], MAX_HALF);
     const long long q = (long long)v[0] * v[0] + (long long)v[1] * v[1];
     UOC_REQUIRE(q <= (long long)MAX_HALF * MAX_HALF, "uoc_footprint: rectangle %d: HL^2 + HW^2 = %lld above %d^2", f, q, MAX_HALF);
-    UOC_REQUIRE(v[2] >= 0 && v[2] < NL, "uoc_footprint: rectangle %d: ignore = %d outside [0, 127]", f, v[2]);
+    UOC_REQUIRE(v[2] >= 0 && v[2] < NUM_IDS, "uoc_footprint: rectangle %d: ignore = %d outside [0, 127]", f, v[2]);
     UOC_REQUIRE(v[3] == UOC_FOOT_ROOMIEST || v[3] == UOC_FOOT_NEAREST, "uoc_footprint: rectangle %d: mode = %d is neither 0 nor 1", f, v[3]);
     UOC_REQUIRE(v[4] >= -MAX_ANCHOR && v[4] < MAX_ANCHOR && v[5] >= -MAX_ANCHOR && v[5] < MAX_ANCHOR,
                 "uoc_footprint: rectangle %d: anchor (ai, aj) = (%d, %d) outside [-%d, %d]", f, v[4], v[5], MAX_ANCHOR, MAX_ANCHOR - 1);

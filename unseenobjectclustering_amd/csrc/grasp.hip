@@ -50,12 +50,13 @@ struct Params {
 // ---- 1. moments -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void moments_kernel(const int *__restrict__ state, const int *__restrict__ owner, int G,
                                                           int *__restrict__ mom) {
-  __shared__ int s_m[NL * 3];
+  __shared__ int s_m[NUM_IDS * 3];
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y;
   const int cells = G * G;
-  for (int i = tid; i < NL * 3; i += THREADS) s_m[i] = 0;
+  for (int i = tid; i < NUM_IDS * 3; i += THREADS) s_m[i] = 0;
   __syncthreads();
   const int *St = state + (size_t)b * cells, *Ow = owner + (size_t)b * cells;
+#pragma unroll  // as the compiler did unasked while the group loop stood here in full
   for (int r = 0; r < CHUNK / THREADS; ++r) {
     const int base = blockIdx.x * CHUNK + r * THREADS + (tid - lane);
     if (base >= cells) break;  // uniform per wave
@@ -63,31 +64,26 @@ __global__ __launch_bounds__(THREADS) void moments_kernel(const int *__restrict_
     int id = -1, i = 0, j = 0;
     if (idx < cells && St[idx] == 2) {
       const int o = Ow[idx];
-      if ((unsigned)(o - 1) < (unsigned)(NL - 1)) {
+      if (obj_id(o)) {
         id = o;
         i = idx / G;
         j = idx - i * G;
       }
     }
-    unsigned long long rem = __ballot(id >= 0);
-    while (rem) {  // uniform: every lane takes part in the shuffles
-      const int first = __ffsll((long long)rem) - 1;
-      const int c = __builtin_amdgcn_readlane(id, first);
+    for_each_wave_key(id, [&](int c, unsigned long long m, int first) {  // every lane takes part in the shuffles
       const bool hit = id == c;
-      const unsigned long long m = __ballot(hit);
-      rem &= ~m;
       const int si = wave_sum(hit ? i : 0), sj = wave_sum(hit ? j : 0);
       if (lane == first) {
         atomicAdd(&s_m[c * 3], (int)__popcll(m));
         atomicAdd(&s_m[c * 3 + 1], si);
         atomicAdd(&s_m[c * 3 + 2], sj);
       }
-    }
+    });
   }
   __syncthreads();
-  for (int i = tid; i < NL * 3; i += THREADS) {
+  for (int i = tid; i < NUM_IDS * 3; i += THREADS) {
     const int v = s_m[i];
-    if (v) atomicAdd(&mom[((size_t)b * NL + i / 3) * MOM + i % 3], v);
+    if (v) atomicAdd(&mom[((size_t)b * NUM_IDS + i / 3) * MOM + i % 3], v);
   }
 }
 
@@ -101,9 +97,9 @@ __global__ __launch_bounds__(THREADS) void candidate_kernel(const int *__restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int a = blockIdx.x, b = blockIdx.y;
   const int G = p.G, A = p.A, M = p.M, Hp = p.Hp, R = p.R, E = p.E, T = p.T, NLn = p.NLn, NM = 2 * p.M + 1;
-  int *C = cand + ((size_t)b * NL + a) * (size_t)(A * NM * 2);
-  int *Bst = best + ((size_t)b * NL + a) * 8;
-  const int *mo = mom + ((size_t)b * NL + a) * MOM;
+  int *C = cand + ((size_t)b * NUM_IDS + a) * (size_t)(A * NM * 2);
+  int *Bst = best + ((size_t)b * NUM_IDS + a) * 8;
+  const int *mo = mom + ((size_t)b * NUM_IDS + a) * MOM;
   const int n = a ? mo[0] : 0;
   if (n == 0) {  // uniform per block
     for (int i = tid; i < A * NM * 2; i += THREADS) C[i] = 0;
@@ -136,7 +132,7 @@ __global__ __launch_bounds__(THREADS) void candidate_kernel(const int *__restric
           const int st = St[i * G + j];
           if (st == 2) {
             const int o = Ow[i * G + j];
-            cls = o == a ? C_OWN : ((unsigned)(o - 1) < (unsigned)(NL - 1) ? C_OTHER : C_UNKNOWN);
+            cls = o == a ? C_OWN : ((unsigned)(o - 1) < (unsigned)(NUM_IDS - 1) ? C_OTHER : C_UNKNOWN);
           } else {
             cls = (st == 1 || (st == 0 && !p.unknown_blocks)) ? C_FREE : C_UNKNOWN;
           }
@@ -229,7 +225,7 @@ bool shape_ok(int B, int G, int A, int M) {
   return batch_ok(B) && grid_ok(G) && A >= 1 && A <= MAX_A && M >= 0 && M <= MAX_M;
 }
 
-size_t ws_total(int B) { return align_up((size_t)B * NL * MOM * sizeof(int), 256); }
+size_t ws_total(int B) { return align_up((size_t)B * NUM_IDS * MOM * sizeof(int), 256); }
 
 }  // namespace
 }  // namespace uoc
@@ -274,7 +270,7 @@ int uoc_grasp(const int32_t *d_state, const int32_t *d_owner, int B, int G, cons
   p.KC = min(A, TABLE_CAP / (p.NLn * p.T));
   const size_t lds = (size_t)p.KC * p.NLn * p.T;
   const int cells = G * G;
-  const double samples = (double)B * (NL - 1) * A * p.NLn * p.T;
+  const double samples = (double)B * (NUM_IDS - 1) * A * p.NLn * p.T;
   hipStream_t st = (hipStream_t)stream;
   {
     ProfScope prof(KC_GRASP_MOMENTS, st, 0.0, (double)B * cells * 8.0);
@@ -283,7 +279,7 @@ int uoc_grasp(const int32_t *d_state, const int32_t *d_owner, int B, int G, cons
   }
   {
     ProfScope prof(KC_GRASP_CANDIDATES, st, 0.0, samples * 8.0);
-    hipLaunchKernelGGL(candidate_kernel, dim3(NL, B), dim3(THREADS), lds, st, d_state, d_owner, (const int *)d_ws, d, p, d_cand,
+    hipLaunchKernelGGL(candidate_kernel, dim3(NUM_IDS, B), dim3(THREADS), lds, st, d_state, d_owner, (const int *)d_ws, d, p, d_cand,
                        d_best);
   }
   UOC_LAUNCH_CHECK();

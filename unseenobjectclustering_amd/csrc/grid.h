@@ -4,14 +4,13 @@
 // transform, the runs of FREE cells, the widest-cell key and the host-side shape checks.  Every stage that names a cell
 // means the cell these functions give it.  Integers only; everything returns the same bits from run to run.
 #pragma once
-#include "common.h"
+#include "labelmap.h"
 
 #include <limits.h>
 #include <math.h>
 
 namespace uoc {
 
-constexpr int NL = 128;          // ids 0..127; 1..127 are objects
 constexpr int SCALE = 16384;     // S: a unit vector's component in the frame, a direction's in the tables
 constexpr int MAX_G = 512;       // cells per side
 constexpr int IDX_MASK = 0x3FFFF;
@@ -115,8 +114,6 @@ __device__ __forceinline__ long long floor_div(long long a, int c) {  // c > 0
   return q - ((a - q * c) < 0 ? 1 : 0);
 }
 
-__device__ __forceinline__ int label_id(int l) { return ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0; }
-
 // Step P.  cell_div = cell_mm * S, t_low = -tau_mm * S.  A point is ignored (not valid, or more than tau below the
 // plane), outside the grid (the function returns true) or inside: then `inside(i, j, T)` gets its cell and its height
 // above the plane in units of 1/S mm.  The tests in this order: validity, the grid, the height.
@@ -197,25 +194,20 @@ template <int K, bool MAXW, typename Emit>
 __device__ __forceinline__ void wave_distinct(int (&e)[K], const int (&w)[K], int lane, Emit emit) {
 #pragma unroll
   for (int j = 0; j < K; ++j) {
-    unsigned long long rem = __ballot(e[j] >= 0);
-    while (rem) {
-      const int first = __ffsll((long long)rem) - 1;
-      const int c = __builtin_amdgcn_readlane(e[j], first);
-      int total = 0, mine = 0;
+    for_each_wave_key(e[j], [&](int c, unsigned long long m, int first) {
+      int total = __popcll(m), mine = 0;
 #pragma unroll
       for (int k = j; k < K; ++k) {
         const bool hit = e[k] == c;
-        const unsigned long long m = __ballot(hit);
-        total += __popcll(m);
-        if (k == j) rem &= ~m;
+        if (k > j) total += __popcll(__ballot(hit));
         if (hit) {
-          e[k] = -1;
+          if (k > j) e[k] = -1;  // slot j's own turns are the primitive's to count off
           mine = max(mine, w[k]);
         }
       }
       if constexpr (MAXW) mine = wave_max(mine);
       if (lane == first) emit(c, total, mine);
-    }
+    });
   }
 }
 
@@ -327,7 +319,7 @@ __global__ __launch_bounds__(RUN_THREADS) void run_kernel(const int *__restrict_
         fr = true;
       } else if (st == 2) {
         const int o = owner[in + j];
-        fr = (unsigned)(o - 1) < (unsigned)(NL - 1) ? (o == ignore) : !unknown_blocks;  // ignore == 0 matches no id
+        fr = obj_id(o) ? (o == ignore) : !unknown_blocks;  // ignore == 0 matches no id
       } else {
         fr = !unknown_blocks;  // state 0 and every state outside 0..2: unknown
       }

@@ -39,8 +39,8 @@ constexpr int F_PIXELS = 0, F_NORMAL = 1, F_GRAZING = 6, F_PEAK = 7, F_HIST = 8;
 
 static_assert(FW == F_HIST + MAX_A, "a row of faces is eight counters and the histogram");
 static_assert(THREADS == TW * TH / 2 && THREADS / 64 * 2 * 2 == TH, "a thread owns the pixels (ty, tx) and (ty + 8, tx)");
-static_assert((QR * QP + 2 * PR * PP) * 8 + NL * FW * 4 + QR * QP <= 65536, "LDS stays below 64 KB");
-static_assert((NL * FW) % 4 == 0, "the accumulators are cleared and flushed as int4");
+static_assert((QR * QP + 2 * PR * PP) * 8 + NUM_IDS * FW * 4 + QR * QP <= 65536, "LDS stays below 64 KB");
+static_assert((NUM_IDS * FW) % 4 == 0, "the accumulators are cleared and flushed as int4");
 
 struct Dirs {
   int v[MAX_A][2];
@@ -88,18 +88,6 @@ __device__ __forceinline__ unsigned long long isqrt64(unsigned long long S) {  /
   return r;
 }
 
-// Every distinct key >= 0 of the wave's lanes adds its number of lanes to s_faces once.  Every lane must call this.
-__device__ __forceinline__ void wave_count(int *__restrict__ s_faces, int key, int lane) {
-  unsigned long long rem = __ballot(key >= 0);
-  while (rem) {
-    const int first = __ffsll((long long)rem) - 1;
-    const int k = __builtin_amdgcn_readlane(key, first);
-    const unsigned long long m = __ballot(key == k);
-    rem &= ~m;
-    if (lane == first) atomicAdd(&s_faces[k], (int)__popcll(m));
-  }
-}
-
 // ---- 1. pixels ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict__ xyz, const int *__restrict__ labels,
                                                         const uoc_plane *__restrict__ planes, int H, int W, int tiles_x, int r,
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
                                                         int *__restrict__ acc) {
   __shared__ unsigned long long s_q[QR * QP];
   __shared__ unsigned long long s_ph[PR * PP], s_pv[PR * PP];
-  __shared__ __attribute__((aligned(16))) int s_faces[NL * FW];
+  __shared__ __attribute__((aligned(16))) int s_faces[NUM_IDS * FW];
   __shared__ unsigned char s_id[QR * QP];
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y;
   const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * TW, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * TH;
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
   const Frame pl = make_plane(planes, b);
   const int h = r + s, qw = TW + 2 * h, qh = TH + 2 * h;
 
-  for (int i = tid; i < NL * FW / 4; i += THREADS) reinterpret_cast<int4 *>(s_faces)[i] = make_int4(0, 0, 0, 0);
+  for (int i = tid; i < NUM_IDS * FW / 4; i += THREADS) reinterpret_cast<int4 *>(s_faces)[i] = make_int4(0, 0, 0, 0);
   for (int idx = tid; idx < qh * qw; idx += THREADS) {  // rule P for the tile and its halo
     const int i = idx / qw, j = idx - i * qw, y = y0 - h + i, x = x0 - h + j;
     unsigned long long w = 0ull;
@@ -126,7 +114,7 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
     if (y >= 0 && y < H && x >= 0 && x < W) {
       const size_t p = (size_t)y * W + x;
       const int l = L ? L[p] : 0;
-      idb = label_id(l);
+      idb = obj_id(l);
       const float fx = X[p], fy = X[n + p], fz = X[2 * n + p];
       bool ok = isfinite(fx) && isfinite(fy) && isfinite(fz) && fz > 0.f;
       const float rx = rintf(fx * 16000.0f), ry = rintf(fy * 16000.0f), rz = rintf(fz * 16000.0f);
@@ -237,15 +225,15 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
         Un[2 * n] = un[2];
       }
     }
-    wave_count(s_faces, inside ? id * FW + F_PIXELS : -1, lane);
-    wave_count(s_faces, k_norm, lane);
-    wave_count(s_faces, k_cls, lane);
-    wave_count(s_faces, k_graz, lane);
-    wave_count(s_faces, k_bin, lane);
+    wave_add_keys(s_faces, inside ? id * FW + F_PIXELS : -1, 1, lane);
+    wave_add_keys(s_faces, k_norm, 1, lane);
+    wave_add_keys(s_faces, k_cls, 1, lane);
+    wave_add_keys(s_faces, k_graz, 1, lane);
+    wave_add_keys(s_faces, k_bin, 1, lane);
   }
   __syncthreads();
-  int *ACC = acc + (size_t)b * NL * FW;
-  for (int i = tid; i < NL * FW / 4; i += THREADS) {
+  int *ACC = acc + (size_t)b * NUM_IDS * FW;
+  for (int i = tid; i < NUM_IDS * FW / 4; i += THREADS) {
     const int4 v = reinterpret_cast<const int4 *>(s_faces)[i];
     if (v.x) atomicAdd(&ACC[4 * i + 0], v.x);
     if (v.y) atomicAdd(&ACC[4 * i + 1], v.y);
@@ -255,8 +243,8 @@ __global__ __launch_bounds__(THREADS) void pixel_kernel(const float *__restrict_
 }
 
 // ---- 2. the rows of faces ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NL) void faces_kernel(const int *__restrict__ acc, int *__restrict__ faces) {
-  const size_t row = ((size_t)blockIdx.x * NL + threadIdx.x) * FW;
+__global__ __launch_bounds__(NUM_IDS) void faces_kernel(const int *__restrict__ acc, int *__restrict__ faces) {
+  const size_t row = ((size_t)blockIdx.x * NUM_IDS + threadIdx.x) * FW;
   const int *R = acc + row;
   int *O = faces + row;
   int peak = -1, best = 0;  // side == 0: an empty histogram
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(NL) void faces_kernel(const int *__restrict__ acc, 
   O[F_PEAK] = peak;
 }
 
-size_t acc_bytes(int B) { return align_up((size_t)B * NL * FW * sizeof(int), 256); }
+size_t acc_bytes(int B) { return align_up((size_t)B * NUM_IDS * FW * sizeof(int), 256); }
 
 }  // namespace
 }  // namespace uoc
@@ -320,8 +308,8 @@ int uoc_normals(const float *d_xyz, const int32_t *d_labels, const uoc_plane *d_
                        d_unit, (int *)d_ws);
   }
   {
-    ProfScope prof(KC_NORMALS_FACES, st, 0.0, (double)B * NL * FW * 8.0);
-    hipLaunchKernelGGL(faces_kernel, dim3(B), dim3(NL), 0, st, (const int *)d_ws, d_faces);
+    ProfScope prof(KC_NORMALS_FACES, st, 0.0, (double)B * NUM_IDS * FW * 8.0);
+    hipLaunchKernelGGL(faces_kernel, dim3(B), dim3(NUM_IDS), 0, st, (const int *)d_ws, d_faces);
   }
   UOC_LAUNCH_CHECK();
   return UOC_OK;

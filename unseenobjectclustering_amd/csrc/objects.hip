@@ -21,8 +21,8 @@
 // atomics: the only atomics are integer adds and max over order-preserving integer encodings (min = max of the
 // complement).  A frame's chunks and partials do not depend on the other frames of the batch, so frame b's outputs are
 // the same bits alone or in a batch.
-#include "common.h"
 #include "fixed_order.h"
+#include "labelmap.h"
 
 #include <limits.h>
 #include <math.h>
@@ -30,7 +30,6 @@
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;             // ids 0..127; 1..127 are objects
 constexpr int WAVES = 4;            // waves per block
 constexpr int SUB = 1024;           // pixels per wave: a wave owns a contiguous sub-chunk (16 iterations of 64 pixels)
 constexpr int CHUNK = WAVES * SUB;  // pixels per block
@@ -49,15 +48,6 @@ __device__ __forceinline__ unsigned fkey(float f) {
 __device__ __forceinline__ float fdecode(unsigned k) {
   return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu));
 }
-__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
-  v = max(v, (unsigned)dpp_i<0xB1>((int)v));
-  v = max(v, (unsigned)dpp_i<0x4E>((int)v));
-  v = max(v, (unsigned)dpp_i<0x141>((int)v));
-  v = max(v, (unsigned)dpp_i<0x140>((int)v));
-  const unsigned a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
-  const unsigned c = __builtin_amdgcn_readlane((int)v, 32), d = __builtin_amdgcn_readlane((int)v, 48);
-  return max(max(a, b), max(c, d));
-}
 struct Pix {
   int l;       // object id, or -1 for background / out of range
   bool valid;  // valid point
@@ -66,9 +56,8 @@ struct Pix {
 __device__ __forceinline__ Pix load_pix(const int *__restrict__ L, const float *__restrict__ X, int n, int p) {
   Pix q{-1, false, 0.f, 0.f, 0.f};
   if (p < n) {
-    const int l = L[p];
-    if (l >= 1 && l < NL) {
-      q.l = l;
+    q.l = obj_key(L[p]);
+    if (q.l >= 0) {
       q.x = X[p];
       q.y = X[(size_t)n + p];
       q.z = X[2 * (size_t)n + p];
@@ -80,14 +69,14 @@ __device__ __forceinline__ Pix load_pix(const int *__restrict__ L, const float *
 
 // Workspace layout (uoc_objects_workspace_bytes).  The zeroed part comes first.
 struct Ws {
-  unsigned *st;                // [B][NL][NST]            zeroed
-  unsigned long long *ext;     // [B][NL][6]  max key(d_k), max ~key(d_k)   zeroed
-  int *wcnt;                   // [B][nch][WAVES][NL]     valid counts per wave, then rank bases
-  double *psum;                // [B][nch][NL][3]
-  double *pmom;                // [B][nch][NL][6]
-  double *cent;                // [B][NL][3]
-  double *axes;                // [B][NL][9]  row-major, column k = e_k
-  int *info;                   // [B][NL][4]  count, kept, prefix of kept within the frame
+  unsigned *st;                // [B][NUM_IDS][NST]            zeroed
+  unsigned long long *ext;     // [B][NUM_IDS][6]  max key(d_k), max ~key(d_k)   zeroed
+  int *wcnt;                   // [B][nch][WAVES][NUM_IDS]     valid counts per wave, then rank bases
+  double *psum;                // [B][nch][NUM_IDS][3]
+  double *pmom;                // [B][nch][NUM_IDS][6]
+  double *cent;                // [B][NUM_IDS][3]
+  double *axes;                // [B][NUM_IDS][9]  row-major, column k = e_k
+  int *info;                   // [B][NUM_IDS][4]  count, kept, prefix of kept within the frame
   int *ftotal;                 // [B]         kept points of the frame
   size_t zero_bytes, total;
 };
@@ -100,15 +89,15 @@ Ws carve(void *base, int B, int nch) {
     off = align_up(off + bytes, 256);
     return r;
   };
-  w.st = (unsigned *)take((size_t)B * NL * NST * 4);
-  w.ext = (unsigned long long *)take((size_t)B * NL * 6 * 8);
+  w.st = (unsigned *)take((size_t)B * NUM_IDS * NST * 4);
+  w.ext = (unsigned long long *)take((size_t)B * NUM_IDS * 6 * 8);
   w.zero_bytes = off;
-  w.wcnt = (int *)take((size_t)B * nch * WAVES * NL * 4);
-  w.psum = (double *)take((size_t)B * nch * NL * 3 * 8);
-  w.pmom = (double *)take((size_t)B * nch * NL * 6 * 8);
-  w.cent = (double *)take((size_t)B * NL * 3 * 8);
-  w.axes = (double *)take((size_t)B * NL * 9 * 8);
-  w.info = (int *)take((size_t)B * NL * 4 * 4);
+  w.wcnt = (int *)take((size_t)B * nch * WAVES * NUM_IDS * 4);
+  w.psum = (double *)take((size_t)B * nch * NUM_IDS * 3 * 8);
+  w.pmom = (double *)take((size_t)B * nch * NUM_IDS * 6 * 8);
+  w.cent = (double *)take((size_t)B * NUM_IDS * 3 * 8);
+  w.axes = (double *)take((size_t)B * NUM_IDS * 9 * 8);
+  w.info = (int *)take((size_t)B * NUM_IDS * 4 * 4);
   w.ftotal = (int *)take((size_t)B * 4);
   w.total = off;
   return w;
@@ -118,14 +107,14 @@ Ws carve(void *base, int B, int nch) {
 __global__ __launch_bounds__(256) void count_kernel(const int *__restrict__ labels, const float *__restrict__ xyz, int H,
                                                     int W, int nch, unsigned *__restrict__ st, int *__restrict__ wcnt,
                                                     double *__restrict__ psum) {
-  __shared__ unsigned bst[NL][NST];
-  __shared__ int wvc[WAVES][NL];
-  __shared__ double wsum[WAVES][NL][3];
+  __shared__ unsigned bst[NUM_IDS][NST];
+  __shared__ int wvc[WAVES][NUM_IDS];
+  __shared__ double wsum[WAVES][NUM_IDS][3];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = blockIdx.x, b = blockIdx.y, n = H * W;
-  for (int i = tid; i < NL * NST; i += 256) (&bst[0][0])[i] = 0u;
-  for (int i = tid; i < WAVES * NL; i += 256) (&wvc[0][0])[i] = 0;
-  for (int i = tid; i < WAVES * NL * 3; i += 256) (&wsum[0][0][0])[i] = 0.0;
+  for (int i = tid; i < NUM_IDS * NST; i += 256) (&bst[0][0])[i] = 0u;
+  for (int i = tid; i < WAVES * NUM_IDS; i += 256) (&wvc[0][0])[i] = 0;
+  for (int i = tid; i < WAVES * NUM_IDS * 3; i += 256) (&wsum[0][0][0])[i] = 0.0;
   __syncthreads();
   const int *L = labels + (size_t)b * n;
   const float *X = xyz + (size_t)b * 3 * n;
@@ -136,13 +125,8 @@ __global__ __launch_bounds__(256) void count_kernel(const int *__restrict__ labe
     const int p = base + lane;
     const Pix q = load_pix(L, X, n, p);
     const int px = p % W, py = p / W;
-    unsigned long long rem = __ballot(q.l >= 0);
     const unsigned long long vall = __ballot(q.valid);
-    while (rem) {
-      const int first = __ffsll((long long)rem) - 1;
-      const int id = __builtin_amdgcn_readlane(q.l, first);
-      const unsigned long long m = __ballot(q.l == id);
-      rem &= ~m;
+    for_each_wave_key(q.l, [&](int id, unsigned long long m, int first) {
       const unsigned long long vm = m & vall;
       const bool g = (m >> lane) & 1ull, gv = (vm >> lane) & 1ull;
       const int last = 63 - __clzll((long long)m);
@@ -175,11 +159,11 @@ __global__ __launch_bounds__(256) void count_kernel(const int *__restrict__ labe
           }
         }
       }
-    }
+    });
   }
   __syncthreads();
-  unsigned *S = st + (size_t)b * NL * NST;
-  for (int i = tid; i < NL * NST; i += 256) {
+  unsigned *S = st + (size_t)b * NUM_IDS * NST;
+  for (int i = tid; i < NUM_IDS * NST; i += 256) {
     const unsigned v = (&bst[0][0])[i];
     if (v == 0u) continue;
     if (i % NST == ST_PIX)
@@ -187,43 +171,43 @@ __global__ __launch_bounds__(256) void count_kernel(const int *__restrict__ labe
     else
       atomicMax(&S[i], v);
   }
-  int *WC = wcnt + ((size_t)b * nch + c) * WAVES * NL;
-  for (int i = tid; i < WAVES * NL; i += 256) WC[i] = (&wvc[0][0])[i];
-  if (tid < NL) {
-    double *P = psum + (((size_t)b * nch + c) * NL + tid) * 3;
+  int *WC = wcnt + ((size_t)b * nch + c) * WAVES * NUM_IDS;
+  for (int i = tid; i < WAVES * NUM_IDS; i += 256) WC[i] = (&wvc[0][0])[i];
+  if (tid < NUM_IDS) {
+    double *P = psum + (((size_t)b * nch + c) * NUM_IDS + tid) * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) P[k] = ((wsum[0][tid][k] + wsum[1][tid][k]) + wsum[2][tid][k]) + wsum[3][tid][k];
   }
 }
 
 // ---- 2. reduce: centroid, rank bases, kept counts -----------------------------------------------------------------
-__global__ __launch_bounds__(NL) void reduce_kernel(int nch, int max_pts, int *__restrict__ wcnt,
+__global__ __launch_bounds__(NUM_IDS) void reduce_kernel(int nch, int max_pts, int *__restrict__ wcnt,
                                                     const double *__restrict__ psum, double *__restrict__ cent,
                                                     int *__restrict__ info, int *__restrict__ ftotal) {
-  __shared__ int kept_s[NL];
+  __shared__ int kept_s[NUM_IDS];
   const int l = threadIdx.x, b = blockIdx.x;
   // One thread walks all chunks of its label; the loops are unrolled so that the loads of several chunks are in flight
   // together (the additions stay in chunk order).
   int cnt = 0;
 #pragma unroll 8
   for (int c = 0; c < nch; ++c) {
-    int *WC = wcnt + ((size_t)b * nch + c) * WAVES * NL + l;
+    int *WC = wcnt + ((size_t)b * nch + c) * WAVES * NUM_IDS + l;
 #pragma unroll
     for (int w = 0; w < WAVES; ++w) {
-      const int v = WC[w * NL];
-      WC[w * NL] = cnt;  // exclusive scan over (chunk, wave): the rank of the wave's first valid point
+      const int v = WC[w * NUM_IDS];
+      WC[w * NUM_IDS] = cnt;  // exclusive scan over (chunk, wave): the rank of the wave's first valid point
       cnt += v;
     }
   }
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll 8
   for (int c = 0; c < nch; ++c) {
-    const double *P = psum + (((size_t)b * nch + c) * NL + l) * 3;
+    const double *P = psum + (((size_t)b * nch + c) * NUM_IDS + l) * 3;
     s0 += P[0];
     s1 += P[1];
     s2 += P[2];
   }
-  double *C = cent + ((size_t)b * NL + l) * 3;
+  double *C = cent + ((size_t)b * NUM_IDS + l) * 3;
   C[0] = cnt ? s0 / cnt : 0.0;
   C[1] = cnt ? s1 / cnt : 0.0;
   C[2] = cnt ? s2 / cnt : 0.0;
@@ -232,7 +216,7 @@ __global__ __launch_bounds__(NL) void reduce_kernel(int nch, int max_pts, int *_
   __syncthreads();
   if (l == 0) {
     int run = 0;
-    for (int i = 0; i < NL; ++i) {
+    for (int i = 0; i < NUM_IDS; ++i) {
       const int k = kept_s[i];
       kept_s[i] = run;
       run += k;
@@ -240,7 +224,7 @@ __global__ __launch_bounds__(NL) void reduce_kernel(int nch, int max_pts, int *_
     ftotal[b] = run;
   }
   __syncthreads();
-  int *I = info + ((size_t)b * NL + l) * 4;
+  int *I = info + ((size_t)b * NUM_IDS + l) * 4;
   I[0] = cnt;
   I[1] = kept;
   I[2] = kept_s[l];
@@ -261,20 +245,20 @@ __global__ __launch_bounds__(256) void scatter_kernel(const int *__restrict__ la
                                                       const int *__restrict__ ftotal, float *__restrict__ pts,
                                                       float *__restrict__ pattr, int *__restrict__ ppix, long capacity,
                                                       double *__restrict__ pmom) {
-  __shared__ double cs[NL][3];
-  __shared__ double wmom[WAVES][NL][6];
-  __shared__ int wrun[WAVES][NL];
-  __shared__ int off_s[NL], cnt_s[NL];
+  __shared__ double cs[NUM_IDS][3];
+  __shared__ double wmom[WAVES][NUM_IDS][6];
+  __shared__ int wrun[WAVES][NUM_IDS];
+  __shared__ int off_s[NUM_IDS], cnt_s[NUM_IDS];
   __shared__ int fb_s;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = blockIdx.x, b = blockIdx.y, n = H * W;
   if (tid == 0) fb_s = frame_base(ftotal, b);
-  for (int i = tid; i < NL * 3; i += 256) (&cs[0][0])[i] = cent[(size_t)b * NL * 3 + i];
-  for (int i = tid; i < WAVES * NL * 6; i += 256) (&wmom[0][0][0])[i] = 0.0;
-  for (int i = tid; i < WAVES * NL; i += 256) (&wrun[0][0])[i] = wcnt[((size_t)b * nch + c) * WAVES * NL + i];
+  for (int i = tid; i < NUM_IDS * 3; i += 256) (&cs[0][0])[i] = cent[(size_t)b * NUM_IDS * 3 + i];
+  for (int i = tid; i < WAVES * NUM_IDS * 6; i += 256) (&wmom[0][0][0])[i] = 0.0;
+  for (int i = tid; i < WAVES * NUM_IDS; i += 256) (&wrun[0][0])[i] = wcnt[((size_t)b * nch + c) * WAVES * NUM_IDS + i];
   __syncthreads();
-  if (tid < NL) {
-    const int *I = info + ((size_t)b * NL + tid) * 4;
+  if (tid < NUM_IDS) {
+    const int *I = info + ((size_t)b * NUM_IDS + tid) * 4;
     cnt_s[tid] = I[0];
     off_s[tid] = fb_s + I[2];
   }
@@ -288,12 +272,8 @@ __global__ __launch_bounds__(256) void scatter_kernel(const int *__restrict__ la
     if (base >= n) break;
     const int p = base + lane;
     const Pix q = load_pix(L, X, n, p);
-    unsigned long long rem = __ballot(q.valid);  // only valid points are ranked, written and moment-summed
-    while (rem) {
-      const int first = __ffsll((long long)rem) - 1;
-      const int id = __builtin_amdgcn_readlane(q.l, first);
-      const unsigned long long vm = __ballot(q.valid && q.l == id);
-      rem &= ~vm;
+    // only valid points are ranked, written and moment-summed
+    for_each_wave_key(q.valid ? q.l : -1, [&](int id, unsigned long long vm, int) {
       const bool gv = (vm >> lane) & 1ull;
       const int r0 = wrun[w][id];
       if (gv && pts) {
@@ -329,26 +309,26 @@ __global__ __launch_bounds__(256) void scatter_kernel(const int *__restrict__ la
         M[4] += m4;
         M[5] += m5;
       }
-    }
+    });
   }
   __syncthreads();
-  for (int i = tid; i < NL * 6; i += 256) {
+  for (int i = tid; i < NUM_IDS * 6; i += 256) {
     const int l = i / 6, k = i - l * 6;
-    pmom[((size_t)b * nch + c) * NL * 6 + i] = ((wmom[0][l][k] + wmom[1][l][k]) + wmom[2][l][k]) + wmom[3][l][k];
+    pmom[((size_t)b * nch + c) * NUM_IDS * 6 + i] = ((wmom[0][l][k] + wmom[1][l][k]) + wmom[2][l][k]) + wmom[3][l][k];
   }
 }
 
 // ---- 4. covariance, eigen-decomposition, records ----------------------------------------------------------------------
-__global__ __launch_bounds__(NL) void moments_kernel(int B, int H, int W, int nch, const unsigned *__restrict__ st,
+__global__ __launch_bounds__(NUM_IDS) void moments_kernel(int B, int H, int W, int nch, const unsigned *__restrict__ st,
                                                      const double *__restrict__ pmom, const double *__restrict__ cent,
                                                      const int *__restrict__ info, const int *__restrict__ ftotal,
                                                      double *__restrict__ axes_out, uoc_object *__restrict__ objs,
                                                      int *__restrict__ total) {
   const int l = threadIdx.x, b = blockIdx.x;
-  const unsigned *S = st + ((size_t)b * NL + l) * NST;
-  const int *I = info + ((size_t)b * NL + l) * 4;
+  const unsigned *S = st + ((size_t)b * NUM_IDS + l) * NST;
+  const int *I = info + ((size_t)b * NUM_IDS + l) * 4;
   const int cnt = I[0];
-  uoc_object &o = objs[(size_t)b * NL + l];
+  uoc_object &o = objs[(size_t)b * NUM_IDS + l];
   o.pixels = (int)S[ST_PIX];
   o.count = cnt;
   o.box[0] = o.pixels ? W - (int)S[ST_WX] : -1;
@@ -360,12 +340,12 @@ __global__ __launch_bounds__(NL) void moments_kernel(int B, int H, int W, int nc
   double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll 8
   for (int c = 0; c < nch; ++c) {  // chunk order; unrolled so that several chunks' loads are in flight
-    const double *P = pmom + (((size_t)b * nch + c) * NL + l) * 6;
+    const double *P = pmom + (((size_t)b * nch + c) * NUM_IDS + l) * 6;
 #pragma unroll
     for (int k = 0; k < 6; ++k) m[k] += P[k];
   }
-  const double *C = cent + ((size_t)b * NL + l) * 3;
-  double *AX = axes_out + ((size_t)b * NL + l) * 9;
+  const double *C = cent + ((size_t)b * NUM_IDS + l) * 3;
+  double *AX = axes_out + ((size_t)b * NUM_IDS + l) * 9;
   for (int k = 0; k < 3; ++k) o.obb_center[k] = o.obb_half[k] = 0.f;   // obb_kernel fills them
   if (cnt > 0) {
     for (int k = 0; k < 6; ++k) m[k] /= cnt;
@@ -409,14 +389,14 @@ __global__ __launch_bounds__(256) void extent_kernel(const int *__restrict__ lab
                                                      int W, const double *__restrict__ cent,
                                                      const double *__restrict__ axes,
                                                      unsigned long long *__restrict__ ext) {
-  __shared__ double cs[NL][3];
-  __shared__ double ax[NL][9];
-  __shared__ unsigned long long bext[NL][6];
+  __shared__ double cs[NUM_IDS][3];
+  __shared__ double ax[NUM_IDS][9];
+  __shared__ unsigned long long bext[NUM_IDS][6];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = blockIdx.x, b = blockIdx.y, n = H * W;
-  for (int i = tid; i < NL * 3; i += 256) (&cs[0][0])[i] = cent[(size_t)b * NL * 3 + i];
-  for (int i = tid; i < NL * 9; i += 256) (&ax[0][0])[i] = axes[(size_t)b * NL * 9 + i];
-  for (int i = tid; i < NL * 6; i += 256) (&bext[0][0])[i] = 0ull;
+  for (int i = tid; i < NUM_IDS * 3; i += 256) (&cs[0][0])[i] = cent[(size_t)b * NUM_IDS * 3 + i];
+  for (int i = tid; i < NUM_IDS * 9; i += 256) (&ax[0][0])[i] = axes[(size_t)b * NUM_IDS * 9 + i];
+  for (int i = tid; i < NUM_IDS * 6; i += 256) (&bext[0][0])[i] = 0ull;
   __syncthreads();
   const int *L = labels + (size_t)b * n;
   const float *X = xyz + (size_t)b * 3 * n;
@@ -425,12 +405,7 @@ __global__ __launch_bounds__(256) void extent_kernel(const int *__restrict__ lab
     const int base = p0 + it * 64;
     if (base >= n) break;
     const Pix q = load_pix(L, X, n, base + lane);
-    unsigned long long rem = __ballot(q.valid);
-    while (rem) {
-      const int first = __ffsll((long long)rem) - 1;
-      const int id = __builtin_amdgcn_readlane(q.l, first);
-      const unsigned long long vm = __ballot(q.valid && q.l == id);
-      rem &= ~vm;
+    for_each_wave_key(q.valid ? q.l : -1, [&](int id, unsigned long long vm, int) {
       const bool gv = (vm >> lane) & 1ull;
       const double dx = (double)q.x - cs[id][0], dy = (double)q.y - cs[id][1], dz = (double)q.z - cs[id][2];
       double hi[3], lo[3];
@@ -446,23 +421,23 @@ __global__ __launch_bounds__(256) void extent_kernel(const int *__restrict__ lab
           atomicMax(&bext[id][k], dkey(hi[k]));
           atomicMax(&bext[id][3 + k], dkey(lo[k]));
         }
-    }
+    });
   }
   __syncthreads();
-  unsigned long long *E = ext + (size_t)b * NL * 6;
-  for (int i = tid; i < NL * 6; i += 256) {
+  unsigned long long *E = ext + (size_t)b * NUM_IDS * 6;
+  for (int i = tid; i < NUM_IDS * 6; i += 256) {
     const unsigned long long v = (&bext[0][0])[i];
     if (v) atomicMax(&E[i], v);
   }
 }
 
-__global__ __launch_bounds__(NL) void obb_kernel(const double *__restrict__ cent, const double *__restrict__ axes,
+__global__ __launch_bounds__(NUM_IDS) void obb_kernel(const double *__restrict__ cent, const double *__restrict__ axes,
                                                  const unsigned long long *__restrict__ ext, uoc_object *__restrict__ objs) {
   const int l = threadIdx.x, b = blockIdx.x;
-  uoc_object *o = objs + (size_t)b * NL + l;
+  uoc_object *o = objs + (size_t)b * NUM_IDS + l;
   if (o->count <= 0) return;
-  const double *C = cent + ((size_t)b * NL + l) * 3, *A = axes + ((size_t)b * NL + l) * 9;
-  const unsigned long long *E = ext + ((size_t)b * NL + l) * 6;
+  const double *C = cent + ((size_t)b * NUM_IDS + l) * 3, *A = axes + ((size_t)b * NUM_IDS + l) * 9;
+  const unsigned long long *E = ext + ((size_t)b * NUM_IDS + l) * 6;
   double mid[3];
   for (int k = 0; k < 3; ++k) {
     const double hi = ddecode(E[k]), lo = -ddecode(E[3 + k]);
@@ -505,13 +480,13 @@ int uoc_objects(const int32_t *d_labels, const float *d_xyz, const float *d_attr
   UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.zero_bytes, st));
   const dim3 grid(nch, B);
   hipLaunchKernelGGL(count_kernel, grid, dim3(256), 0, st, d_labels, d_xyz, H, W, nch, w.st, w.wcnt, w.psum);
-  hipLaunchKernelGGL(reduce_kernel, dim3(B), dim3(NL), 0, st, nch, M, w.wcnt, w.psum, w.cent, w.info, w.ftotal);
+  hipLaunchKernelGGL(reduce_kernel, dim3(B), dim3(NUM_IDS), 0, st, nch, M, w.wcnt, w.psum, w.cent, w.info, w.ftotal);
   hipLaunchKernelGGL(scatter_kernel, grid, dim3(256), 0, st, d_labels, d_xyz, d_point_attr ? d_attr : nullptr, attr_ch, H,
                      W, nch, M, w.wcnt, w.cent, w.info, w.ftotal, d_points, d_point_attr, d_point_pixel, capacity, w.pmom);
-  hipLaunchKernelGGL(moments_kernel, dim3(B), dim3(NL), 0, st, B, H, W, nch, w.st, w.pmom, w.cent, w.info, w.ftotal,
+  hipLaunchKernelGGL(moments_kernel, dim3(B), dim3(NUM_IDS), 0, st, B, H, W, nch, w.st, w.pmom, w.cent, w.info, w.ftotal,
                      w.axes, d_objects, d_total);
   hipLaunchKernelGGL(extent_kernel, grid, dim3(256), 0, st, d_labels, d_xyz, H, W, w.cent, w.axes, w.ext);
-  hipLaunchKernelGGL(obb_kernel, dim3(B), dim3(NL), 0, st, w.cent, w.axes, w.ext, d_objects);
+  hipLaunchKernelGGL(obb_kernel, dim3(B), dim3(NUM_IDS), 0, st, w.cent, w.axes, w.ext, d_objects);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }

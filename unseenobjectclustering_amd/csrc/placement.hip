@@ -58,11 +58,11 @@ __device__ __forceinline__ bool classify(const Frame &f, const Thresholds &th, i
                                          int &e_cnt, int &e_own) {
   e_cnt = e_own = -1;
   return project_point(f, th.cell_div, th.t_low, G, x, y, z, [&](int i, int j, long long T) {
-    const int id = label_id(l);
+    const int id = obj_id(l);
     const int cell = i * G + j;
     if (id != 0 || T > th.t_obs) {
       e_cnt = cell * 2 + 1;
-      if (id) e_own = cell * NL + id;
+      if (id) e_own = cell * NUM_IDS + id;
     } else if (T <= th.t_tab) {
       e_cnt = cell * 2;
     }
@@ -94,9 +94,9 @@ __global__ __launch_bounds__(256) void raster_kernel(const int *__restrict__ lab
     for (int k = 0; k < K; ++k) out[k] = classify(f, th, G, px.l[k], px.x[k], px.y[k], px.z[k], e_cnt[k], e_own[k]);
     outside += wave_count_set(out);
     wave_distinct<K, false>(e_cnt, none, lane, [&](int code, int total, int) { atomicAdd((code & 1) ? &NO[code >> 1] : &NT[code >> 1], total); });
-    wave_distinct<K, false>(e_own, none, lane, [&](int code, int, int) { atomicMax(&OW[code >> 7], code & (NL - 1)); });
+    wave_distinct<K, false>(e_own, none, lane, [&](int code, int, int) { atomicMax(&OW[code >> 7], code & (NUM_IDS - 1)); });
   }
-  if (lane == 0 && outside) atomicAdd(&counts[(size_t)b * NL], outside);
+  if (lane == 0 && outside) atomicAdd(&counts[(size_t)b * NUM_IDS], outside);
 }
 
 // ---- 2. cells and the column pass ----------------------------------------------------------------------------------------
@@ -106,11 +106,11 @@ __global__ __launch_bounds__(STRIP *SEGS) void column_kernel(const int *__restri
                                                              int *__restrict__ owner, int *__restrict__ g_out,
                                                              int *__restrict__ counts) {
   __shared__ unsigned short s[MAX_G][STRIP];  // bit 15: blocking; after the upward scan the low bits hold the distance up
-  __shared__ int s_hist[NL];
+  __shared__ int s_hist[NUM_IDS];
   const int tid = threadIdx.x, b = blockIdx.y, j0 = blockIdx.x * STRIP;
   const bool found = frame_found_nonzero(frame + (size_t)b * NFR);
   const size_t off = (size_t)b * G * G;
-  if (tid < NL) s_hist[tid] = 0;
+  if (tid < NUM_IDS) s_hist[tid] = 0;
   __syncthreads();
   for (int idx = tid; idx < G * STRIP; idx += STRIP * SEGS) {
     const int i = idx / STRIP, jj = idx % STRIP, j = j0 + jj;
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(STRIP *SEGS) void column_kernel(const int *__restri
     s[i][jj] = (!found || st == 2 || (st == 0 && unknown_blocks)) ? 0x8000u : 0u;
   }
   __syncthreads();
-  if (tid >= 1 && tid < NL && s_hist[tid]) atomicAdd(&counts[(size_t)b * NL + tid], s_hist[tid]);
+  if (tid >= 1 && tid < NUM_IDS && s_hist[tid]) atomicAdd(&counts[(size_t)b * NUM_IDS + tid], s_hist[tid]);
   column_scan(s, G, j0, g_out + off);
 }
 
@@ -270,7 +270,7 @@ int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *
     ProfScope prof(KC_PLACE_RASTER, st, 0.0, (double)B * n * 16.0 + (double)cells * 12.0);
     UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.total, st));
     UOC_HIP_CHECK(hipMemsetAsync(d_owner, 0, cells * sizeof(int32_t), st));
-    UOC_HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)B * NL * sizeof(int32_t), st));
+    UOC_HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)B * NUM_IDS * sizeof(int32_t), st));
     if (vec)
       hipLaunchKernelGGL(raster_kernel<true>, dim3(nch, B), dim3(256), 0, st, d_labels, d_xyz, d_planes, n, G, th, w.n_obs,
                          w.n_table, d_owner, d_counts, (long long *)d_frame);

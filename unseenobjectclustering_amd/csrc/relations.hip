@@ -8,7 +8,7 @@
 //                  pixel at a row end or a chunk end is just another raster index of the frame: no halo).  A wave whose
 //                  lanes all see their own id in every neighbour skips the depth loads and the table work.  The other
 //                  pairs become events on ONE table of 128x128 words in LDS, each distinct event added once per wave
-//                  (ballot + popcount, as track.hip's wave_add_pairs), and every non-zero word leaves the block as
+//                  (for_each_wave_key of common.h), and every non-zero word leaves the block as
 //                  integer atomicAdds: integer adds commute, so the tables do not depend on the order.
 //   derive_kernel  one block per frame: row sums, the occlusion masks (128 x 128 bits), the peeling by one wave (two
 //                  ids per lane, so a round costs two ballots and no barrier), the rank by counting, the records.
@@ -22,7 +22,7 @@
 // into its neighbour (the worst case is a checkerboard of two ids at connectivity 8, where every pair of the block meets
 // in one cell).  Across blocks the sums are int32 in global memory: a table entry is at most the number of pairs of a
 // frame, below 4 * H*W < 2^31 for H*W < 2^29, and so is a row sum of border.
-#include "common.h"
+#include "labelmap.h"
 #include "prof.h"
 
 #include <limits.h>
@@ -30,34 +30,26 @@
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;                   // ids 0..127; 1..127 are objects
-constexpr int TAB = NL * NL;
+constexpr int TAB = NUM_IDS * NUM_IDS;
 constexpr int PAIR_THREADS = 1024;
 constexpr int SPAN = 8192;                // pixels per pair block: 4 * SPAN < 65536, see above
 constexpr int TURNS = SPAN / PAIR_THREADS;
 constexpr int HI = 1 << 14;               // event code: table word | HI when the event counts in the word's high half
-constexpr int CNT_WORDS = 2 * NL;         // workspace per frame: pixels[128], edge[128]
+constexpr int CNT_WORDS = 2 * NUM_IDS;    // workspace per frame: pixels[128], edge[128]
 constexpr int DERIVE_THREADS = 1024;
 constexpr int MAX_PIXELS = (1 << 29) - 1;
 
 static_assert(4 * SPAN < 65536, "a 16-bit counter of a pair block must not wrap");
 static_assert(sizeof(uoc_relation_object) == 11 * sizeof(int32_t), "uoc_relation_object is eleven int32");
 
-__device__ __forceinline__ int obj_id(int l) { return ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0; }
-
 // zq of a valid depth, -1 of an invalid one (NaN fails both comparisons).
 __device__ __forceinline__ int depth_mm(float z) { return (z > 0.0f && z <= 65.0f) ? (int)rintf(z * 1000.0f) : -1; }
 
 // One distinct event per loop turn: the wave's lanes holding it are counted with one ballot and added once.
 __device__ __forceinline__ void wave_add_events(unsigned *__restrict__ s_tab, int code, int lane) {
-  unsigned long long rem = __ballot(code >= 0);
-  while (rem) {
-    const int first = __ffsll((long long)rem) - 1;
-    const int c = __builtin_amdgcn_readlane(code, first);
-    const unsigned long long m = __ballot(code == c);
-    rem &= ~m;
+  for_each_wave_key(code, [&](int c, unsigned long long m, int first) {
     if (lane == first) atomicAdd(&s_tab[c & (TAB - 1)], (unsigned)__popcll(m) << ((c & HI) ? 16 : 0));
-  }
+  });
 }
 
 // ---- 1. pairs ----------------------------------------------------------------------------------------------------------
@@ -84,16 +76,10 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_kernel(const int *__restric
       a = obj_id(L[i]);
       edge = x == 0 || y == 0 || x == W - 1 || y == H - 1;
     }
-    {   // pixels and edge pixels of the ids 1..127, one id per loop turn
-      unsigned long long rem = __ballot(a > 0);
-      while (rem) {
-        const int first = __ffsll((long long)rem) - 1;
-        const int id = __builtin_amdgcn_readlane(a, first);
-        const unsigned long long m = __ballot(a == id), me = __ballot(a == id && edge);
-        rem &= ~m;
-        if (lane == first) atomicAdd(&s_tab[id * (NL + 1)], (unsigned)__popcll(m) + ((unsigned)__popcll(me) << 16));
-      }
-    }
+    for_each_wave_key(a > 0 ? a : -1, [&](int id, unsigned long long m, int first) {   // pixels and edge pixels of the ids 1..127
+      const unsigned long long me = __ballot(a == id && edge);
+      if (lane == first) atomicAdd(&s_tab[id * (NUM_IDS + 1)], (unsigned)__popcll(m) + ((unsigned)__popcll(me) << 16));
+    });
     // forward neighbours: right, down, down-right, down-left; every index is inside the frame when its flag holds
     const bool right = act && x + 1 < W, down = act && y + 1 < H;
     const int nj[4] = {i + 1, i + W, i + W + 1, i + W - 1};
@@ -113,14 +99,14 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_kernel(const int *__restric
       int e_border = -1, e_rel = -1;
       if (nb[d] != a) {
         const int lo = min(a, nb[d]), hi = max(a, nb[d]);
-        e_border = HI | (lo * NL + hi);
+        e_border = HI | (lo * NUM_IDS + hi);
         const int zr = depth_mm(Z[nj[d]]);
         if (zq >= 0 && zr >= 0) {
           const int dz = zq - zr;
           if (abs(dz) < gap_mm)
-            e_rel = HI | (hi * NL + lo);                       // touch
+            e_rel = HI | (hi * NUM_IDS + lo);                            // touch
           else
-            e_rel = dz < 0 ? a * NL + nb[d] : nb[d] * NL + a;  // front[near][far]
+            e_rel = dz < 0 ? a * NUM_IDS + nb[d] : nb[d] * NUM_IDS + a;  // front[near][far]
         }
       }
       wave_add_events(s_tab, e_border, lane);
@@ -133,16 +119,16 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_kernel(const int *__restric
   for (int i = tid; i < TAB; i += PAIR_THREADS) {
     const unsigned v = s_tab[i];
     if (!v) continue;
-    const int r = i >> 7, c = i & (NL - 1), lo = (int)(v & 0xFFFFu), hi = (int)(v >> 16);
+    const int r = i >> 7, c = i & (NUM_IDS - 1), lo = (int)(v & 0xFFFFu), hi = (int)(v >> 16);
     if (r == c) {
       if (lo) atomicAdd(&C[r], lo);
-      if (hi) atomicAdd(&C[NL + r], hi);
+      if (hi) atomicAdd(&C[NUM_IDS + r], hi);
     } else {
       if (lo) atomicAdd(&P[UOC_REL_FRONT * TAB + i], lo);
       if (hi) {
         int *T = P + (r < c ? UOC_REL_BORDER : UOC_REL_TOUCH) * TAB;
         atomicAdd(&T[i], hi);
-        atomicAdd(&T[c * NL + r], hi);
+        atomicAdd(&T[c * NUM_IDS + r], hi);
       }
     }
   }
@@ -151,25 +137,25 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_kernel(const int *__restric
 // ---- 2. relations, layers, order ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(DERIVE_THREADS) void derive_kernel(const int *__restrict__ pairs, const int *__restrict__ cnt,
                                                                 int min_pairs, uoc_relation_object *__restrict__ objs) {
-  __shared__ int s_border[NL], s_ntouch[NL], s_nbelow[NL], s_layer[NL], s_key[NL];
-  __shared__ unsigned long long s_above[NL][2];   // bit a of row b: a occludes b
+  __shared__ int s_border[NUM_IDS], s_ntouch[NUM_IDS], s_nbelow[NUM_IDS], s_layer[NUM_IDS], s_key[NUM_IDS];
+  __shared__ unsigned long long s_above[NUM_IDS][2];   // bit a of row b: a occludes b
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
   const int *P = pairs + (size_t)b * 3 * TAB;
   const int *C = cnt + (size_t)b * CNT_WORDS;
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     s_border[tid] = s_ntouch[tid] = s_nbelow[tid] = s_layer[tid] = 0;
     s_above[tid][0] = s_above[tid][1] = 0ull;
   }
   __syncthreads();
   // the tables are sparse (a frame has a handful of ids), so the LDS atomics below are few
   for (int i = tid; i < TAB; i += DERIVE_THREADS) {
-    const int a = i >> 7, c = i & (NL - 1);
+    const int a = i >> 7, c = i & (NUM_IDS - 1);
     const int bo = P[UOC_REL_BORDER * TAB + i];
     if (bo) atomicAdd(&s_border[a], bo);
     if (a >= 1 && c >= 1) {
       if (P[UOC_REL_TOUCH * TAB + i] >= min_pairs) atomicAdd(&s_ntouch[a], 1);
       const int f = P[UOC_REL_FRONT * TAB + i];
-      if (f >= min_pairs && f > P[UOC_REL_FRONT * TAB + c * NL + a]) {   // a occludes c
+      if (f >= min_pairs && f > P[UOC_REL_FRONT * TAB + c * NUM_IDS + a]) {   // a occludes c
         atomicAdd(&s_nbelow[a], 1);
         atomicOr(&s_above[c][a >> 6], 1ull << (a & 63));
       }
@@ -196,20 +182,20 @@ __global__ __launch_bounds__(DERIVE_THREADS) void derive_kernel(const int *__res
     if (p1 && l1 == 0) l1 = -1;
     s_layer[lane] = l0;
     s_layer[lane + 64] = l1;
-    s_key[lane] = p0 ? (l0 < 0 ? NL : l0) * NL + lane : INT_MAX;
-    s_key[lane + 64] = p1 ? (l1 < 0 ? NL : l1) * NL + lane + 64 : INT_MAX;
+    s_key[lane] = p0 ? (l0 < 0 ? NUM_IDS : l0) * NUM_IDS + lane : INT_MAX;
+    s_key[lane + 64] = p1 ? (l1 < 0 ? NUM_IDS : l1) * NUM_IDS + lane + 64 : INT_MAX;
   }
   __syncthreads();
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     uoc_relation_object o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int key = s_key[tid];
     if (key != INT_MAX) {
       int rank = 1;
-      for (int j = 0; j < NL; ++j) rank += s_key[(j + tid) & (NL - 1)] < key;
+      for (int j = 0; j < NUM_IDS; ++j) rank += s_key[(j + tid) & (NUM_IDS - 1)] < key;
       o.pixels = C[tid];
-      o.edge = C[NL + tid];
+      o.edge = C[NUM_IDS + tid];
       o.border = s_border[tid];
-      o.border_bg = P[UOC_REL_BORDER * TAB + tid * NL];
+      o.border_bg = P[UOC_REL_BORDER * TAB + tid * NUM_IDS];
       o.hidden = P[UOC_REL_FRONT * TAB + tid];
       o.n_touch = s_ntouch[tid];
       o.n_above = (int)(__popcll(s_above[tid][0]) + __popcll(s_above[tid][1]));
@@ -218,7 +204,7 @@ __global__ __launch_bounds__(DERIVE_THREADS) void derive_kernel(const int *__res
       o.free = o.n_above == 0 && o.hidden < min_pairs && o.edge == 0;
       o.order = rank;
     }
-    objs[(size_t)b * NL + tid] = o;
+    objs[(size_t)b * NUM_IDS + tid] = o;
   }
 }
 

@@ -400,7 +400,7 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
                 v[2]);
     UOC_REQUIRE((v[3] == -1 && v[4] == -1) || (v[3] >= 0 && v[3] < G && v[4] >= 0 && v[4] < G),
                 "uoc_routes: query %d: target (ti, tj) = (%d, %d) is neither inside the grid nor (-1, -1)", q, v[3], v[4]);
-    UOC_REQUIRE(v[5] >= 0 && v[5] < NL, "uoc_routes: query %d: ignore = %d outside [0, 127]", q, v[5]);
+    UOC_REQUIRE(v[5] >= 0 && v[5] < NUM_IDS, "uoc_routes: query %d: ignore = %d outside [0, 127]", q, v[5]);
     UOC_REQUIRE(v[6] == 0 && v[7] == 0, "uoc_routes: query %d: reserved words (%d, %d) are not zero", q, v[6], v[7]);
     int m = 0;
     while (m < NM && !(p.ignore.v[m] == v[5] && p.need2[m] == v[0])) ++m;

@@ -11,7 +11,7 @@
 //
 // One step is three launches on grids (block, stream):
 //   cont_kernel   cont[mem][cur] over the pixels: a 128x128 table privatised in LDS per block, a wave adds each distinct
-//                 pair once (ballot + popcount), blocks flush with integer atomics — integer adds commute, so the table
+//                 pair once (wave_add_keys), blocks flush with integer atomics — integer adds commute, so the table
 //                 does not depend on the order
 //   match_kernel  one block of 1024 threads per stream: row / column sums, the candidate list (inter * 65536 >= q * union), greedy
 //                 matching by exact IoU (cross-multiplied 64-bit integers; ties: larger inter, lower track, lower id) run by
@@ -20,22 +20,21 @@
 //   apply_kernel  out = lut[cur]; mem' = out where out != 0, else mem where its track is kept, else 0
 //
 // The pixel kernels read and write int4 when H*W is a multiple of 4 and the maps are 16-byte aligned, else one int.
-#include "common.h"
+#include "labelmap.h"
 
 #include <limits.h>
 
 namespace uoc {
 namespace {
 
-constexpr int NL = 128;                     // ids 0..127; 1..127 are objects / track slots
 constexpr int HDR_WORDS = 1024;             // header words per stream
-constexpr int META = NL * 5;                // header word of {uids handed out, step, dropped}
-constexpr int CONT_WORDS = NL * NL;
+constexpr int META = NUM_IDS * 5;           // header word of {uids handed out, step, dropped}
+constexpr int CONT_WORDS = NUM_IDS * NUM_IDS;
 constexpr int CONT_THREADS = 1024;
 constexpr int PIX_PER_BLOCK = CONT_THREADS * 8;   // pixels per contingency block until MAX_BLOCKS is reached
 constexpr int MAX_BLOCKS = 64;              // pixel-kernel blocks per stream (grid-stride beyond)
 constexpr int MATCH_THREADS = 1024;
-constexpr int PLAN_WORDS = 2 * NL;          // workspace per stream: lut[128], keep[128]
+constexpr int PLAN_WORDS = 2 * NUM_IDS;     // workspace per stream: lut[128], keep[128]
 
 static_assert(sizeof(uoc_track) == 5 * sizeof(int32_t), "uoc_track is five int32");
 
@@ -44,23 +43,8 @@ inline size_t state_stride(long long n) {
 }
 __device__ __forceinline__ int *state_hdr(void *state, size_t stride, int b) { return (int *)((char *)state + stride * b); }
 
-// Object id of a raw label: 1..127, anything else (negatives included) is background.
-__device__ __forceinline__ int obj_id(int l) { return ((unsigned)(l - 1) < (unsigned)(NL - 1)) ? l : 0; }
-
 // Table index of a pixel.  The memory map only ever holds 0..127; the mask keeps a state that was never reset in bounds.
-__device__ __forceinline__ int pair_key(int m, int l) { return (m & (NL - 1)) * NL + obj_id(l); }
-
-// One distinct (mem, cur) pair per loop turn: the wave's lanes holding it are counted with one ballot and added once.
-__device__ __forceinline__ void wave_add_pairs(int *__restrict__ s_cont, int key, int weight, int lane) {
-  unsigned long long rem = __ballot(key >= 0);
-  while (rem) {
-    const int first = __ffsll((long long)rem) - 1;
-    const int id = __builtin_amdgcn_readlane(key, first);
-    const unsigned long long m = __ballot(key == id);
-    rem &= ~m;
-    if (lane == first) atomicAdd(&s_cont[id], weight * (int)__popcll(m));
-  }
-}
+__device__ __forceinline__ int pair_key(int m, int l) { return (m & (NUM_IDS - 1)) * NUM_IDS + obj_id(l); }
 
 // ---- 1. contingency ------------------------------------------------------------------------------------------------
 template <int V>
@@ -88,16 +72,16 @@ __global__ __launch_bounds__(CONT_THREADS) void cont_kernel(const int *__restric
       const int k0 = act ? pair_key(m.x, l.x) : -1, k1 = act ? pair_key(m.y, l.y) : -1;
       const int k2 = act ? pair_key(m.z, l.z) : -1, k3 = act ? pair_key(m.w, l.w) : -1;
       if (__all(k0 == k1 && k1 == k2 && k2 == k3)) {   // the usual case: every lane's four pixels are one pair
-        wave_add_pairs(s_cont, k0, 4, lane);
+        wave_add_keys(s_cont, k0, 4, lane);
       } else {
-        wave_add_pairs(s_cont, k0, 1, lane);
-        wave_add_pairs(s_cont, k1, 1, lane);
-        wave_add_pairs(s_cont, k2, 1, lane);
-        wave_add_pairs(s_cont, k3, 1, lane);
+        wave_add_keys(s_cont, k0, 1, lane);
+        wave_add_keys(s_cont, k1, 1, lane);
+        wave_add_keys(s_cont, k2, 1, lane);
+        wave_add_keys(s_cont, k3, 1, lane);
       }
     } else {
       const int k = act ? pair_key(M[i], L[i]) : -1;
-      wave_add_pairs(s_cont, k, 1, lane);
+      wave_add_keys(s_cont, k, 1, lane);
     }
   }
   __syncthreads();
@@ -143,9 +127,6 @@ __device__ __forceinline__ Cand wave_best(Cand v) {
   if (better(r3, r)) r = r3;
   return r;
 }
-__device__ __forceinline__ int lane_rank(unsigned long long mask) {  // set bits of mask below this lane
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__ state, size_t stride, int q, int max_age,
                                                               int *__restrict__ plan, int *__restrict__ lut_out,
@@ -153,8 +134,9 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
   extern __shared__ int s_dyn[];
   int *s_cont = s_dyn;                                              // [128][128]
   unsigned short *s_list = (unsigned short *)(s_dyn + CONT_WORDS);  // candidate keys, at most 127 * 127
-  __shared__ int area_mem[NL], area_cur[NL], s_uid[NL], match_t[NL], match_c[NL], s_lut[NL], s_keep[NL];
-  __shared__ int slot_of_rank[NL], born_uid[NL], born_area[NL];
+  __shared__ int area_mem[NUM_IDS], area_cur[NUM_IDS], s_uid[NUM_IDS], match_t[NUM_IDS], match_c[NUM_IDS];
+  __shared__ int s_lut[NUM_IDS], s_keep[NUM_IDS];
+  __shared__ int slot_of_rank[NUM_IDS], born_uid[NUM_IDS], born_area[NUM_IDS];
   __shared__ int s_nlist, s_cnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
   int *hdr = state_hdr(state, stride, b);
@@ -162,7 +144,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
 
   // the slot this thread owns (tid < 128)
   int uid = 0, age = 0, hits = 0, area = 0, born = 0;
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     uid = hdr[tid * 5 + 0];
     age = hdr[tid * 5 + 1];
     hits = hdr[tid * 5 + 2];
@@ -187,20 +169,20 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
   }
   __syncthreads();
 
-  if (tid < NL) {   // row sums; the column index is rotated by the row so that the lanes fall on different banks
+  if (tid < NUM_IDS) {   // row sums; the column index is rotated by the row so that the lanes fall on different banks
     int s = 0;
-    for (int j = 0; j < NL; ++j) s += s_cont[tid * NL + ((j + tid) & (NL - 1))];
+    for (int j = 0; j < NUM_IDS; ++j) s += s_cont[tid * NUM_IDS + ((j + tid) & (NUM_IDS - 1))];
     area_mem[tid] = s;
-  } else if (tid < 2 * NL) {   // column sums
-    const int c = tid - NL;
+  } else if (tid < 2 * NUM_IDS) {   // column sums
+    const int c = tid - NUM_IDS;
     int s = 0;
-    for (int t = 0; t < NL; ++t) s += s_cont[t * NL + c];
+    for (int t = 0; t < NUM_IDS; ++t) s += s_cont[t * NUM_IDS + c];
     area_cur[c] = s;
   }
   __syncthreads();
 
   for (int i = tid; i < CONT_WORDS; i += MATCH_THREADS) {   // candidates
-    const int t = i >> 7, c = i & (NL - 1), inter = s_cont[i];
+    const int t = i >> 7, c = i & (NUM_IDS - 1), inter = s_cont[i];
     if (t >= 1 && c >= 1 && inter > 0 && s_uid[t] != 0) {
       const long long uni = (long long)area_mem[t] + area_cur[c] - inter;
       if ((long long)inter * 65536 >= (long long)q * uni) s_list[atomicAdd(&s_nlist, 1)] = (unsigned short)i;
@@ -214,7 +196,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
     for (;;) {
       Cand best{0, 1, INT_MAX};
       for (int k = lane; k < nlist; k += 64) {
-        const int key = s_list[k], t = key >> 7, c = key & (NL - 1);
+        const int key = s_list[k], t = key >> 7, c = key & (NUM_IDS - 1);
         if ((((t & 64 ? mt1 : mt0) >> (t & 63)) | ((c & 64 ? mc1 : mc0) >> (c & 63))) & 1ull) continue;
         const int inter = s_cont[key];
         const Cand cand{inter, area_mem[t] + (area_cur[c] - inter), key};
@@ -222,7 +204,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
       }
       best = wave_best(best);
       if (best.inter == 0) break;   // the same in every lane
-      const int t = best.key >> 7, c = best.key & (NL - 1);
+      const int t = best.key >> 7, c = best.key & (NUM_IDS - 1);
       (t & 64 ? mt1 : mt0) |= 1ull << (t & 63);
       (c & 64 ? mc1 : mc0) |= 1ull << (c & 63);
       if (lane == 0) {
@@ -233,7 +215,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
   }
   __syncthreads();
 
-  if (tid >= 1 && tid < NL && uid != 0) {   // ageing
+  if (tid >= 1 && tid < NUM_IDS && uid != 0) {   // ageing
     const int c = match_t[tid];
     if (c) {
       age = 0;
@@ -252,8 +234,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
   __syncthreads();
 
   // births: the unmatched present ids in ascending order take the free slots in ascending order
-  const bool is_new = tid >= 1 && tid < NL && area_cur[tid] > 0 && match_c[tid] == 0;
-  const bool is_free = tid >= 1 && tid < NL && s_uid[tid] == 0;
+  const bool is_new = tid >= 1 && tid < NUM_IDS && area_cur[tid] > 0 && match_c[tid] == 0;
+  const bool is_free = tid >= 1 && tid < NUM_IDS && s_uid[tid] == 0;
   const unsigned long long bal_new = __ballot(is_new), bal_free = __ballot(is_free);
   if (wave < 2 && lane == 0) {
     s_cnt[wave] = (int)__popcll(bal_new);
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
   }
   __syncthreads();
 
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     if (born_uid[tid]) {
       uid = born_uid[tid];
       age = 0;
@@ -286,10 +268,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
     hdr[tid * 5 + 2] = hits;
     hdr[tid * 5 + 3] = area;
     hdr[tid * 5 + 4] = born;
-    if (tracks_out) tracks_out[(size_t)b * NL + tid] = uoc_track{uid, age, hits, area, born};
+    if (tracks_out) tracks_out[(size_t)b * NUM_IDS + tid] = uoc_track{uid, age, hits, area, born};
     plan[(size_t)b * PLAN_WORDS + tid] = s_lut[tid];
-    plan[(size_t)b * PLAN_WORDS + NL + tid] = s_keep[tid];
-    if (lut_out) lut_out[(size_t)b * NL + tid] = s_lut[tid];
+    plan[(size_t)b * PLAN_WORDS + NUM_IDS + tid] = s_keep[tid];
+    if (lut_out) lut_out[(size_t)b * NUM_IDS + tid] = s_lut[tid];
   }
   if (tid == 0) {
     const int births = n_new < n_free ? n_new : n_free;
@@ -303,11 +285,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(void *__restrict__
 template <int V>
 __global__ __launch_bounds__(256) void apply_kernel(const int *__restrict__ labels, void *__restrict__ state, size_t stride,
                                                     int n, const int *__restrict__ plan, int *__restrict__ out) {
-  __shared__ int s_lut[NL], s_keep[NL];
+  __shared__ int s_lut[NUM_IDS], s_keep[NUM_IDS];
   const int tid = threadIdx.x, b = blockIdx.y;
-  if (tid < NL) {
+  if (tid < NUM_IDS) {
     s_lut[tid] = plan[(size_t)b * PLAN_WORDS + tid];
-    s_keep[tid] = plan[(size_t)b * PLAN_WORDS + NL + tid];
+    s_keep[tid] = plan[(size_t)b * PLAN_WORDS + NUM_IDS + tid];
   }
   __syncthreads();
   int *M = state_hdr(state, stride, b) + HDR_WORDS + CONT_WORDS;
@@ -316,7 +298,7 @@ __global__ __launch_bounds__(256) void apply_kernel(const int *__restrict__ labe
   const long long nv = n / V, step = (long long)gridDim.x * 256;
   auto one = [&](int l, int m, int &o, int &mm) {
     o = s_lut[obj_id(l)];
-    mm = o ? o : (s_keep[m & (NL - 1)] ? m : 0);
+    mm = o ? o : (s_keep[m & (NUM_IDS - 1)] ? m : 0);
   };
   for (long long i = (long long)blockIdx.x * 256 + tid; i < nv; i += step) {
     if (V == 4) {

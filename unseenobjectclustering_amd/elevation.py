@@ -37,13 +37,10 @@ _BAND = (-32768, 32767)
 Spot = collections.namedtuple("Spot", "cell clearance_m height_m xyz")
 
 
-class ElevationResult:
+class ElevationResult(_native.Fields):
     """Device tensors.  elev, owner, pts, near, dist2: [B,G,G] int32; tops [B,128,8] int32 (TOPS_FIELDS per id); info [B,4]
     int32 (INFO_FIELDS); answers [B,Q,4] int32, one (i, j, dist2, ok) per query, (-1, -1, 0, 0) without a candidate; frame
     [B,16] int64, the integer frame records used (placement.FRAME_FIELDS)."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def elevation_records(labels, xyz, frame, grid, cell_mm, tau_mm, step_mm, min_pts, queries=()):
@@ -106,27 +103,14 @@ def heights(labels, xyz, placed, step=0.005, min_pts=2, queries=None) -> Elevati
     for mm, name in ((cell_mm, "cell_mm"), (tau_mm, "tau_mm")):
         if not 1 <= mm <= _native.PLACE_MAX_MM:
             raise ValueError(f"{name} = {mm} outside 1..{_native.PLACE_MAX_MM} mm")
-    for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _native.on_gpu(t):
-            raise _native.NativeError(f"heights: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if labels.dim() == 2:
-        labels = labels[None]
-    if xyz.dim() == 3:
-        xyz = xyz[None]
-    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
-            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
-        raise _native.NativeError(f"heights: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
-                                  "([B,H,W] and [B,3,H,W])")
-    if xyz.device != labels.device:
-        raise _native.NativeError("heights: labels and xyz are on different devices")
+    labels, xyz = _native.frame_inputs("heights", labels, xyz)
     B = int(labels.shape[0])
     frame = getattr(placed, "frame", None)
     if not _native.on_gpu(frame) or frame.device != labels.device or frame.dtype != torch.int64 or tuple(frame.shape) != (B, 16):
         raise _native.NativeError(f"heights: the frame records of `placed` do not match the {B} frames on {labels.device}")
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
     frame = frame.contiguous()
     elev, owner, pts, near, dist2, tops, info, answers = elevation_records(
-        lab, xyz.to(torch.float32).contiguous(), frame, G, cell_mm, tau_mm, step_mm, int(min_pts), qs)
+        labels, xyz, frame, G, cell_mm, tau_mm, step_mm, int(min_pts), qs)
     return ElevationResult(elev=elev, owner=owner, pts=pts, near=near, dist2=dist2, tops=tops, info=info, answers=answers,
                            frame=frame, queries=qs, grid=G, cell_mm=cell_mm, tau_mm=tau_mm, step_mm=step_mm, min_pts=int(min_pts))
 

@@ -30,14 +30,11 @@ INFLATE = 184                     # 0.71875 cell in units of 1/256: half a cell'
 FootprintPose = namedtuple("FootprintPose", "center axis k angle cell dist2")
 
 
-class FootprintResult:
+class FootprintResult(_native.Fields):
     """Device tensors.  fits [B,F,G,G] int32: bit k of a word is set when rectangle f fits at the cell along direction k;
     count [B,F,32] int32: the cells per direction; best [B,F,8] int32: BEST_FIELDS per rectangle.  dirs: the direction
     table [A,2] and rects: the records [F,8] (host, numpy).  grid, cell_mm, planes: of the placement result the grids came
     from."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def _radius(HL, HW):

@@ -30,13 +30,10 @@ BEST_FIELDS = ("ok", "k", "m", "tlo", "w", "ax", "ay", "n_ok")
 GraspPose = namedtuple("GraspPose", "center axis width_m opening_m k m")
 
 
-class GraspResult:
+class GraspResult(_native.Fields):
     """Device tensors.  cand [B,128,A,2M+1,2] int32: (code, tlo) per id, direction k and offset m (index m + M); best
     [B,128,8] int32: BEST_FIELDS per id.  dirs: the direction table [A,2] (host, numpy).  angles, offsets, max_open, gap,
     finger, pad: A, M, Wmax, gap, F, Hp in cells; grid, cell_mm, planes: of the placement result the grids came from."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def direction_table(angles):

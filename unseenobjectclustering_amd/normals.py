@@ -32,14 +32,11 @@ FACE_FIELDS = ("pixels", "with_normal", "up", "side", "oblique", "down", "grazin
 _PLANE_WORDS = ctypes.sizeof(_native.UocPlane) // 4
 
 
-class NormalsResult:
+class NormalsResult(_native.Fields):
     """Device tensors.  n [B,H,W,3] int32: the integer normal n', zero without one; info [B,H,W] int32 = class | grazing
     << 3 | bin << 8 | nX << 16 | nY << 24, zero without a normal; unit [B,3,H,W] float32 (NaN without a normal) or None;
     faces [B,128,40] int32: FACE_FIELDS and the azimuth histogram [32] per id.  dirs: the direction table [A,2] (host,
     numpy).  packed: n and info as the kernel wrote them, [B,H,W,4]."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def direction_table(angles):
@@ -131,7 +128,7 @@ def estimate(xyz, labels=None, fitted=None, step=2, window=2, jump=0.030, min_pa
         if labels.dim() != 3 or labels.shape[0] != B or tuple(labels.shape[1:]) != tuple(xyz.shape[2:]):
             raise _native.NativeError(f"normals: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
                                       "([B,H,W] and [B,3,H,W])")
-        lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
+        lab = _native.as_labels(labels)
     planes = None
     if fitted is not None:
         if isinstance(fitted, (tuple, list)):

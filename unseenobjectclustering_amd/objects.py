@@ -22,7 +22,7 @@ _F = {name: (getattr(_native.UocObject, name).offset // 4, getattr(_native.UocOb
 _COV_INDEX = [0, 1, 2, 1, 3, 4, 2, 4, 5]   # xx, xy, xz, yy, yz, zz -> 3x3
 
 
-class ObjectSet:
+class ObjectSet(_native.Fields):
     """Objects of the (frame, id) pairs with pixels > 0 and count >= min_points, in ascending (frame, id) order.
     Every tensor lives on the device of the inputs; K = len(self).
 
@@ -31,21 +31,12 @@ class ObjectSet:
     points [P,3]; pixel_index [P] int32 (raster index y*W + x in its frame); attrs [P,C] or None; offsets [K+1] int64:
     the rows of object k are points[offsets[k]:offsets[k+1]]."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
-
     def __len__(self):
         return int(self.frame.shape[0])
 
     def cloud(self, k):
         """Points of object k, [n,3]."""
         return self.points[self._offsets_host[k]:self._offsets_host[k + 1]]
-
-
-def _device_tensor(t, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise _native.NativeError(f"extract_objects: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    return t
 
 
 def _workspace(dev, nbytes):
@@ -88,24 +79,11 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
     xyz: [B,3,H,W] or [3,H,W] float metres (sample['depth']); attrs: optional [B,C,H,W] / [C,H,W], C <= 8, gathered
     verbatim per point.  max_points_per_object = M keeps the points of in-object rank floor(j*count/M), j < M, of an
     object with count > M.  Objects with pixels > 0 and count >= min_points are returned."""
-    _device_tensor(labels, "labels")
-    _device_tensor(xyz, "xyz")
-    if labels.dim() == 2:
-        labels = labels[None]
-    if xyz.dim() == 3:
-        xyz = xyz[None]
-    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
-            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
-        raise _native.NativeError(f"extract_objects: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
-                                  "([B,H,W] and [B,3,H,W])")
-    dev = labels.device
-    if xyz.device != dev:
-        raise _native.NativeError("extract_objects: labels and xyz are on different devices")
-    lab = labels if labels.dtype == torch.int32 else labels.to(torch.int32)
-    lab = lab.contiguous()
-    xyz = xyz.to(torch.float32).contiguous()
+    lab, xyz = _native.frame_inputs("extract_objects", labels, xyz)
+    dev = lab.device
     if attrs is not None:
-        _device_tensor(attrs, "attrs")
+        if not _native.on_gpu(attrs):
+            raise _native.NativeError("extract_objects: attrs must be a tensor on the GPU (there is no CPU fallback)")
         if attrs.dim() == 3:
             attrs = attrs[None]
         if attrs.dim() != 4 or attrs.shape[0] != lab.shape[0] or tuple(attrs.shape[2:]) != tuple(lab.shape[1:]) \

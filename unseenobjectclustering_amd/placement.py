@@ -32,13 +32,10 @@ _OFF = {name: getattr(_native.UocPlane, name).offset // 4 for name, _ in _native
 FRAME_FIELDS = {"N": slice(0, 3), "D": 3, "U": slice(4, 7), "V": slice(7, 10), "qc": slice(10, 13), "found": 13}
 
 
-class PlacementResult:
+class PlacementResult(_native.Fields):
     """Device tensors.  state, owner, dist2: [B,G,G] int32; cells [B,128] int32 (obstacle cells per owner id 1..127; word 0
     is the frame's `outside` counter); outside [B] int32; frame [B,16] int64 (FRAME_FIELDS); answers [B,Q,4] int32, one
     (i, j, dist2, ok) per query, (-1, -1, 0, 0) without a candidate; planes [B,21] int32, the uoc_plane records used."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def pack_planes(normal, d, centroid, u, v, frames=None):
@@ -119,19 +116,7 @@ def free_space(labels, xyz, plane, grid=256, cell=0.010, h_obs=0.010, tau=0.010,
     if not 1 <= int(min_pts) <= _native.PLACE_MAX_MIN_PTS:
         raise ValueError(f"min_pts = {min_pts} outside 1..{_native.PLACE_MAX_MIN_PTS}")
     qs = _check_queries(queries)
-    for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _native.on_gpu(t):
-            raise _native.NativeError(f"free_space: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if labels.dim() == 2:
-        labels = labels[None]
-    if xyz.dim() == 3:
-        xyz = xyz[None]
-    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
-            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
-        raise _native.NativeError(f"free_space: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
-                                  "([B,H,W] and [B,3,H,W])")
-    if xyz.device != labels.device:
-        raise _native.NativeError("free_space: labels and xyz are on different devices")
+    labels, xyz = _native.frame_inputs("free_space", labels, xyz)
     B = int(labels.shape[0])
     if isinstance(plane, (tuple, list)):
         planes = torch.from_numpy(pack_planes(*plane, frames=B)).to(labels.device)
@@ -142,9 +127,8 @@ def free_space(labels, xyz, plane, grid=256, cell=0.010, h_obs=0.010, tau=0.010,
     if not _native.on_gpu(planes) or planes.device != labels.device or planes.dtype != torch.int32 \
             or tuple(planes.shape) != (B, _PLANE_WORDS):
         raise _native.NativeError(f"free_space: the plane records do not match the {B} frames on {labels.device}")
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
     state, owner, dist2, counts, frame, answers = placement_records(
-        lab, xyz.to(torch.float32).contiguous(), planes.contiguous(), G, cell_mm, h_obs_mm, tau_mm, int(min_pts),
+        labels, xyz, planes.contiguous(), G, cell_mm, h_obs_mm, tau_mm, int(min_pts),
         1 if unknown_blocks else 0, qs)
     return PlacementResult(state=state, owner=owner, dist2=dist2, cells=counts, outside=counts[:, 0], frame=frame,
                            answers=answers, planes=planes, queries=qs, grid=G, cell_mm=cell_mm, h_obs_mm=h_obs_mm,

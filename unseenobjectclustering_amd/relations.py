@@ -22,12 +22,9 @@ OBJECT_FIELDS = tuple(name for name, _ in _native.UocRelationObject._fields_)
 TABLES = ("border", "touch", "front")
 
 
-class RelationResult:
+class RelationResult(_native.Fields):
     """Device tensors, all int32.  border, touch, front: [B,128,128]; pixels, edge, border_sum (the record's `border`),
     border_bg, hidden, n_touch, n_above, n_below, layer, free, order: [B,128]."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def relation_records(labels, xyz, connectivity, gap_mm, min_pairs):
@@ -61,21 +58,8 @@ def relate(labels, xyz, connectivity=4, gap=0.015, min_pairs=8) -> RelationResul
         raise ValueError(f"gap = {gap} m is {gap_mm} mm, outside 1..{_native.REL_MAX_GAP_MM} mm")
     if int(min_pairs) < 1:
         raise ValueError(f"min_pairs = {min_pairs} is below 1")
-    for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _native.on_gpu(t):
-            raise _native.NativeError(f"relate: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if labels.dim() == 2:
-        labels = labels[None]
-    if xyz.dim() == 3:
-        xyz = xyz[None]
-    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
-            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
-        raise _native.NativeError(f"relate: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
-                                  "([B,H,W] and [B,3,H,W])")
-    if xyz.device != labels.device:
-        raise _native.NativeError("relate: labels and xyz are on different devices")
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
-    pairs, objs = relation_records(lab, xyz.to(torch.float32).contiguous(), connectivity, gap_mm, min_pairs)
+    lab, xyz = _native.frame_inputs("relate", labels, xyz)
+    pairs, objs = relation_records(lab, xyz, connectivity, gap_mm, min_pairs)
     fields = {("border_sum" if k == "border" else k): objs[..., i] for i, k in enumerate(OBJECT_FIELDS)}
     fields.update(border=pairs[:, _native.REL_BORDER], touch=pairs[:, _native.REL_TOUCH], front=pairs[:, _native.REL_FRONT])
     return RelationResult(connectivity=int(connectivity), gap_mm=gap_mm, min_pairs=int(min_pairs), **fields)

@@ -31,14 +31,11 @@ COST_ORTH, COST_DIAG = 5, 7
 Waypoints = namedtuple("Waypoints", "cells truncated reached_target cost")
 
 
-class RoutesResult:
+class RoutesResult(_native.Fields):
     """Device tensors.  cost [B,Q,G,G] int32: the least cost from the source of query q, -1 where the cell is not passable
     or not reached; info [B,Q,8] int32: INFO_FIELDS per query; path [B,Q,max_path,2] int32: the cells from the
     closest-approach cell back to the source, (-1, -1) past the end.  queries: the records [Q,8] (host, numpy).  grid,
     cell_mm, planes: of the placement result the grids came from."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def _check_queries(queries, G=None):

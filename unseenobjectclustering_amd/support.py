@@ -40,14 +40,11 @@ PLANE_FIELDS = tuple(_PLANE)
 OBJECT_FIELDS = tuple(_OBJECT)
 
 
-class PlaneResult:
+class PlaneResult(_native.Fields):
     """Device tensors.  Per frame: found, candidates, inliers, hyp [B] int32; normal, centroid, eig, u, v [B,3]; d, rms [B].
     Per (frame, id): count [B,128] int32; height_min, height_max [B,128]; foot, axis [B,128,2]; cov2, half, center
     [B,128,3].  height: [B,H,W] (NaN where there is no valid point) with height_map=True, else None.  records: the
     uoc_plane records themselves, [B,21] int32 (what placement.free_space reads in place)."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 def _view(rec, layout, name, integer):
@@ -55,9 +52,6 @@ def _view(rec, layout, name, integer):
     v = rec[..., o:o + n]
     v = v if integer else v.view(torch.float32)
     return v[..., 0] if n == 1 else v
-
-
-_on_gpu = _native.on_gpu      # under a name of this module: the host tests stub it here
 
 
 def plane_records(labels, xyz, num_hyp, tau_mm, seed, height_map=False):
@@ -91,21 +85,8 @@ def fit_plane(labels, xyz, num_hyp=256, tau=0.010, seed=1, height_map=False) -> 
     tau_mm = int(round(float(tau) * 1000))
     if not 1 <= tau_mm <= _native.PLANE_MAX_TAU_MM:
         raise ValueError(f"tau = {tau} m is {tau_mm} mm, outside 1..{_native.PLANE_MAX_TAU_MM} mm")
-    for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _on_gpu(t):
-            raise _native.NativeError(f"fit_plane: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if labels.dim() == 2:
-        labels = labels[None]
-    if xyz.dim() == 3:
-        xyz = xyz[None]
-    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
-            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
-        raise _native.NativeError(f"fit_plane: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
-                                  "([B,H,W] and [B,3,H,W])")
-    if xyz.device != labels.device:
-        raise _native.NativeError("fit_plane: labels and xyz are on different devices")
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
-    planes, objs, height = plane_records(lab, xyz.to(torch.float32).contiguous(), num_hyp, tau_mm, seed, height_map)
+    lab, xyz = _native.frame_inputs("fit_plane", labels, xyz)
+    planes, objs, height = plane_records(lab, xyz, num_hyp, tau_mm, seed, height_map)
     fields = {k: _view(planes, _PLANE, k, k in PLANE_INT_FIELDS) for k in PLANE_FIELDS}
     fields.update({k: _view(objs, _OBJECT, k, k == "count") for k in OBJECT_FIELDS})
     return PlaneResult(height=height, num_hyp=int(num_hyp), tau_mm=tau_mm, seed=int(seed) & 0xFFFFFFFF, records=planes,
@@ -138,16 +119,13 @@ INFO_INT_FIELDS = ("round_candidates", "removed")
 INFO_FIELDS = tuple(_INFO)
 
 
-class PlanesResult:
+class PlanesResult(_native.Fields):
     """Device tensors.  count [B] int32: the planes found.  Per (frame, plane): every uoc_plane field as in PlaneResult
     with a plane axis ([B,K] / [B,K,3]); round_candidates, removed [B,K] int32; cos0, offset0 [B,K]; extent [B,K,4].  Per
     (frame, plane, id): every uoc_plane_object field, [B,K,128,...] (zeros with objects=False); its point count is named
     obj_count here, count being the number of planes.  index [B,H,W] int32: -2
     not a candidate, k an inlier of plane k, 16 + k the removal fringe of plane k, -1 a candidate no plane took.
     records [B,K,21] int32, the uoc_plane records themselves."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
     def plane(self, k) -> PlaneResult:
         """Plane k of every frame as a PlaneResult (contiguous [B,21] records, the object fields, height=None): what every
@@ -216,23 +194,10 @@ def fit_planes(labels, xyz, max_planes=4, num_hyp=256, tau=0.010, remove=None, m
         raise ValueError(f"remove = {remove} m is {rem_mm} mm, outside tau = {tau_mm}..{_native.PLANE_MAX_TAU_MM} mm")
     if min_inliers is not None and int(min_inliers) < 3:
         raise ValueError(f"min_inliers = {min_inliers} below 3")
-    for t, what in ((labels, "labels"), (xyz, "xyz")):
-        if not _on_gpu(t):
-            raise _native.NativeError(f"fit_planes: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if labels.dim() == 2:
-        labels = labels[None]
-    if xyz.dim() == 3:
-        xyz = xyz[None]
-    if labels.dim() != 3 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != labels.shape[0] \
-            or tuple(xyz.shape[2:]) != tuple(labels.shape[1:]):
-        raise _native.NativeError(f"fit_planes: labels {tuple(labels.shape)} and xyz {tuple(xyz.shape)} do not match "
-                                  "([B,H,W] and [B,3,H,W])")
-    if xyz.device != labels.device:
-        raise _native.NativeError("fit_planes: labels and xyz are on different devices")
-    B, H, W = (int(v) for v in labels.shape)
+    lab, xyz = _native.frame_inputs("fit_planes", labels, xyz)
+    B, H, W = (int(v) for v in lab.shape)
     mi = max(3, H * W // 50) if min_inliers is None else int(min_inliers)
-    lab = (labels if labels.dtype == torch.int32 else labels.to(torch.int32)).contiguous()
-    count, planes, info, index, objs = planes_records(lab, xyz.to(torch.float32).contiguous(), max_planes, num_hyp, tau_mm,
+    count, planes, info, index, objs = planes_records(lab, xyz, max_planes, num_hyp, tau_mm,
                                                       rem_mm, mi, seed, objects)
     if objs is None:
         objs = torch.zeros((B, int(max_planes), NUM_IDS, _OW), dtype=torch.int32, device=lab.device)

@@ -83,12 +83,6 @@ class Tracker:
         self._tracks[sel] = 0
 
     # ---- stepping ------------------------------------------------------------------------------------
-    def _prepare(self, labels, what):
-        if not isinstance(labels, torch.Tensor) or labels.device.type != "cuda":
-            raise _native.NativeError(f"{what}: labels must be a tensor on the GPU (there is no CPU fallback)")
-        lab = labels if labels.dtype == torch.int32 else labels.to(torch.int32)
-        return lab.contiguous()
-
     def _step(self, lab, out, lut, tracks):
         dev, B, H, W = self._key
         with torch.cuda.device(dev):
@@ -100,7 +94,7 @@ class Tracker:
     def update(self, labels):
         """labels: device tensor [H,W] (one stream) or [streams,H,W] of int32 / int64 / float ids.  Returns the tracked
         map, int32, same shape: 0 = background, else the track slot in 1..127."""
-        lab = self._prepare(labels, "Tracker.update")
+        lab = _native.label_input("Tracker.update", labels)
         squeeze = lab.dim() == 2
         if squeeze:
             lab = lab[None]
@@ -159,7 +153,7 @@ def track_sequence(labels, min_iou=0.3, max_age=5, tracker=None):
     tr = tracker if tracker is not None else Tracker(min_iou, max_age, streams=1)
     if tr.streams != 1:
         raise ValueError("track_sequence steps one stream")
-    lab = tr._prepare(labels, "track_sequence")
+    lab = _native.label_input("track_sequence", labels)
     if lab.dim() != 3:
         raise _native.NativeError(f"track_sequence: labels {tuple(labels.shape)} must be [T,H,W]")
     T, H, W = (int(v) for v in lab.shape)
