@@ -200,6 +200,43 @@ int uoc_conv2d_nhwc_algo(const float *d_in, const float *d_w, const float *d_bia
                          int G, int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu,
                          int algo, void *stream);
 
+/* Test entries of the convolution kernels: every tile instantiation, and the stem, the pooling and the head on their own.
+ * The conv kernels are families of template instantiations chosen at run time (by a static cost model, and in the network
+ * by a tuner that times them); all instantiations of one algorithm sum every output in the same order and are
+ * bit-identical, which tests/test_conv_tiles_gpu.py asserts through these entries.
+ * uoc_conv2d_tile_list writes min(cap, n) pairs (cfg, bm) to out_pairs and returns n, the number of instantiations of
+ *   `algo` (generated from the table that drives the dispatch).  UOC_CONV_DIRECT: cfg = tile family 0..3 (0: 2x4 waves
+ *   x 128 output channels, 1: 1x8 x 128, 2: 2x4 x 64, 3: 1x4 x 64), bm = pixels per tile.  UOC_CONV_WINOGRAD4 and
+ *   UOC_CONV_WINOGRAD4_BF16X3: cfg = BN, the plane GEMM's output channels per tile (64 or 128), bm = its tiles per block
+ *   tile; the fp32 plane GEMM has each pair with and without its pair loop, which follows from Cin (an even number, four or
+ *   more, of 32-channel chunks) as in the network.
+ * uoc_conv2d_nhwc_tile is uoc_conv2d_nhwc_algo running exactly the instantiation (cfg, bm), on the grid the library uses
+ *   for that tile.  UOC_EINVAL if the list has no such pair or the shape does not admit it (Cout % BN != 0, a shape the
+ *   algorithm refuses, a group above 2 GB).  It neither reads nor writes the tuner's table and launches nothing to time.
+ * uoc_conv2d_tile_choice: the pair the static model picks for a shape (pad = dil for K = 3, 0 for K = 1), host arithmetic
+ *   (the Winograd model reads the device's CU count, 256 without a device).  UOC_CONV_DIRECT also fills family_bm[4] (unless
+ *   NULL) with the height each family would run at, 0 where Cout does not admit the family: the network's tuner may
+ *   take any of them.
+ * uoc_net_stem: d_nchw [G][B][3][H][W] -> d_out [G][B][H1][W1][64], H1 = (H-1)/2 + 1: the NCHW -> NHWC4 kernel and the
+ *   7x7 stride-2 pad-3 instantiation.  h_w [G][64][3][7][7] and h_bias [G][64] are HOST memory (as uoc_net_load_param
+ *   takes them; re-laid out by the function uoc_net_finalize uses); h_bias NULL = zero, as in the first pass of the
+ *   early-fusion stem, whose second pass takes the first as d_res [G][B][H1][W1][64].  Allocates, synchronises, frees.
+ * uoc_maxpool3x3s2_nhwc: [n_img][H][W][C] -> [n_img][(H-1)/2+1][(W-1)/2+1][C], kernel 3, stride 2, padding 1 (taps outside
+ *   the image are skipped), C % 4 == 0.
+ * uoc_head: d_fa, d_fb [B][h][w][64] -> unit-norm d_embed [B][H*W][64] = normalize(bilinear(fa + fb), align_corners) (d_fb
+ *   may be NULL), or with cat != 0 [B][2][H*W][64], the two upsampled branches normalised over all 128 channels. */
+int uoc_conv2d_tile_list(int algo, int32_t *out_pairs, int cap);
+int uoc_conv2d_nhwc_tile(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out,
+                         int G, int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu,
+                         int algo, void *stream, int cfg, int bm);
+int uoc_conv2d_tile_choice(int G, int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int algo,
+                           int32_t *cfg, int32_t *bm, int32_t *family_bm);
+int uoc_net_stem(const float *d_nchw, const float *h_w, const float *h_bias, const float *d_res, int G, int B, int H,
+                 int W, int relu, float *d_out, void *stream);
+int uoc_maxpool3x3s2_nhwc(const float *d_in, float *d_out, int n_img, int H, int W, int C, void *stream);
+int uoc_head(const float *d_fa, const float *d_fb, float *d_embed, int B, int h, int w, int H, int W, int cat,
+             void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Two-stage glue — replaces lib/fcn/test_dataset.py:62-198 (filter_labels_depth, crop_rois,

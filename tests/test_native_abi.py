@@ -101,6 +101,46 @@ def test_shipped_library_has_no_result_affecting_knobs():
     assert lib.uoc_conv2d_nhwc_algo(None, None, None, None, None, 1, 1, 8, 8, 32, 64, 5, 1, 1, 1, 0, 0, None) == -22
 
 
+def test_conv_tile_entries_validate_without_gpu():
+    """The tile lists and the static model are host arithmetic; the single-tile entry and the stand-alone stem / pooling / head
+    entries refuse bad arguments before any HIP call."""
+    lib = _native.lib()
+    lists = {}
+    for algo, n in ((_native.CONV_DIRECT, 14), (_native.CONV_WINOGRAD4, 8), (_native.CONV_WINOGRAD4_BF16X3, 6)):
+        assert lib.uoc_conv2d_tile_list(algo, None, 0) == n
+        buf = (ctypes.c_int32 * (2 * n))()
+        assert lib.uoc_conv2d_tile_list(algo, buf, n) == n
+        lists[algo] = [(buf[2 * i], buf[2 * i + 1]) for i in range(n)]
+        assert len(set(lists[algo])) == n
+        short = (ctypes.c_int32 * 4)(-1, -1, -1, -1)                  # a short array is filled as far as it goes, no further
+        assert lib.uoc_conv2d_tile_list(algo, short, 1) == n and (short[0], short[1]) == lists[algo][0] and short[2] == -1
+    assert lib.uoc_conv2d_tile_list(1, None, 0) == -22
+    assert set(c for c, _ in lists[_native.CONV_DIRECT]) == {0, 1, 2, 3}
+    assert set(c for c, _ in lists[_native.CONV_WINOGRAD4]) == {64, 128}
+    cfg, bm, fam = ctypes.c_int32(), ctypes.c_int32(), (ctypes.c_int32 * 4)()
+    # the fc layer at 480x640: Cout = 64 admits the two 64-wide families only
+    assert lib.uoc_conv2d_tile_choice(2, 1, 60, 80, 512, 64, 1, 1, 1, _native.CONV_DIRECT, ctypes.byref(cfg), ctypes.byref(bm), fam) == 0
+    assert (cfg.value, bm.value) in lists[_native.CONV_DIRECT] and fam[0] == fam[1] == 0 and fam[cfg.value] == bm.value
+    assert all((i, fam[i]) in lists[_native.CONV_DIRECT] for i in (2, 3))
+    assert lib.uoc_conv2d_tile_choice(2, 1, 60, 80, 256, 256, 3, 1, 2, _native.CONV_WINOGRAD4, ctypes.byref(cfg), ctypes.byref(bm), None) == 0
+    assert (cfg.value, bm.value) in lists[_native.CONV_WINOGRAD4]
+    assert lib.uoc_conv2d_tile_choice(2, 1, 60, 80, 256, 256, 3, 2, 1, _native.CONV_WINOGRAD4, ctypes.byref(cfg), ctypes.byref(bm), None) == -22
+    assert lib.uoc_conv2d_tile_choice(2, 1, 60, 80, 48, 64, 3, 1, 1, _native.CONV_DIRECT, ctypes.byref(cfg), ctypes.byref(bm), None) == -22
+    one = ctypes.c_void_p(16)                                            # never dereferenced: every call below is refused first
+    tile = lambda algo, Cout, c, b: lib.uoc_conv2d_nhwc_tile(one, one, None, None, one, 1, 1, 8, 8, 32, Cout, 3, 1, 1, 1, 0, algo, None, c, b)
+    assert tile(_native.CONV_DIRECT, 128, 0, 64) == -22 and b"no tile" in lib.uoc_last_error().lower()
+    assert tile(_native.CONV_DIRECT, 64, 0, 96) == -22                  # Cout = 64 under a 128-wide family
+    assert tile(_native.CONV_WINOGRAD4, 128, 128, 80) == -22
+    assert tile(_native.CONV_WINOGRAD4, 64, 128, 96) == -22
+    assert tile(_native.CONV_WINOGRAD4_BF16X3, 128, 128, 192) == -22
+    assert lib.uoc_conv2d_nhwc_tile(None, None, None, None, None, 1, 1, 8, 8, 32, 64, 3, 1, 1, 1, 0, 0, None, 3, 64) == -22
+    assert lib.uoc_net_stem(None, None, None, None, 1, 1, 8, 8, 1, None, None) == -22
+    assert lib.uoc_maxpool3x3s2_nhwc(None, None, 1, 8, 8, 64, None) == -22
+    assert lib.uoc_maxpool3x3s2_nhwc(one, ctypes.c_void_p(32), 1, 8, 8, 6, None) == -22      # C % 4 != 0
+    assert lib.uoc_head(None, None, None, 1, 1, 1, 8, 8, 0, None) == -22
+    assert lib.uoc_head(one, None, one, 1, 1, 1, 8, 8, 1, None) == -22                       # cat needs both branches
+
+
 def test_product_path_refuses_cpu_tensors():
     import torch
     from unseenobjectclustering_amd.utils.mean_shift import mean_shift_smart_init

@@ -72,6 +72,15 @@ def _declare(lib):
     lib.uoc_conv2d_nhwc.argtypes = [P, P, P, P, P] + [c_int] * 11 + [P]
     lib.uoc_conv2d_nhwc_algo.argtypes = [P, P, P, P, P] + [c_int] * 12 + [P]
     lib.uoc_conv2d_nhwc_algo.restype = c_int
+    # test entries: one tile instantiation at a time; stem, pooling and head on their own
+    lib.uoc_conv2d_tile_list.argtypes = [c_int, P, c_int]
+    lib.uoc_conv2d_nhwc_tile.argtypes = [P, P, P, P, P] + [c_int] * 12 + [P, c_int, c_int]
+    lib.uoc_conv2d_tile_choice.argtypes = [c_int] * 10 + [P, P, P]
+    lib.uoc_net_stem.argtypes = [P, P, P, P] + [c_int] * 5 + [P, P]
+    lib.uoc_maxpool3x3s2_nhwc.argtypes = [P, P] + [c_int] * 4 + [P]
+    lib.uoc_head.argtypes = [P, P, P] + [c_int] * 6 + [P]
+    for name in TILE_SYMBOLS:
+        getattr(lib, name).restype = c_int
     for name in ("uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_forward",
                  "uoc_conv2d_nhwc"):
         getattr(lib, name).restype = c_int
@@ -172,6 +181,10 @@ METRIC_SYMBOLS = ("uoc_ms_select_seeds_ex", "uoc_ms_hill_climb_ex", "uoc_ms_seed
                   "uoc_ms_cluster_ex", "uoc_ms_cluster_wide_ex")
 
 
+TILE_SYMBOLS = ("uoc_conv2d_tile_list", "uoc_conv2d_nhwc_tile", "uoc_conv2d_tile_choice", "uoc_net_stem",
+                "uoc_maxpool3x3s2_nhwc", "uoc_head")
+
+
 def metric_code(metric) -> int:
     """cfg.TRAIN.EMBEDDING_METRIC / the reference's metric= string -> the C ABI's metric argument."""
     if metric not in METRICS:
@@ -187,6 +200,7 @@ EXPORTED_SYMBOLS = (
     "uoc_net_embed_dim",
     "uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_workspace_bytes",
     "uoc_net_forward", "uoc_net_set_split_precision", "uoc_conv2d_nhwc", "uoc_conv2d_nhwc_algo",
+) + TILE_SYMBOLS + (
     "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
     "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
     "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",

@@ -25,19 +25,43 @@ struct ConvParams {
 };
 
 int launch_conv(const ConvParams &p, hipStream_t st);
+// Tile-level entries of the direct kernel (tests): the (family, height) pairs of every non-stem instantiation (returns their
+// number, writes at most `cap` pairs), the static model's choice for a shape (fam_bm: the height of each of the 4 families,
+// 0 where Cout does not admit it), and a launch of exactly one instantiation (never touches the tuner's table).
+int conv_tile_list(int *out_pairs, int cap);
+int conv_tile_choice(const ConvParams &p, int *cfg, int *bm, int *fam_bm);
+int launch_conv_tile(const ConvParams &p, hipStream_t st, int cfg, int bm);
 
+// A plane-GEMM tile of the Winograd F(4x4) path named by a caller (tests): BM tiles x BN output channels.
+struct W4Tile {
+  int bm, bn;
+};
+// (BN, BM) pairs of the fp32 plane GEMM (split = false) or of the split-precision one; what the static model picks
+int wino4_tile_list(bool split, int *out_pairs, int cap);
+void wino4_tile_choice(bool split, int NT, int Cout, int planes, int *bn, int *bm);
+int wino4_split_tile_list(int *out_pairs, int cap);
+void wino4_split_tile_choice(int NT, int Cout, int planes, int *bn, int *bm);
+// the shared cost model over a tile list {BM, BN} (the first of equal costs wins; bm / bn keep their value if no tile admits
+// Cout) and the grid of a plane GEMM with a given tile
+void wino4_pick_tile(const int (*tiles)[2], int n, int NT, int Cout, int planes, int &bm, int &bn);
+int wino4_plane_grid(int NT, int Cout, int planes, int bm, int bn);
 
 // Winograd F(4x4,3x3) path (csrc/wino4.hip): U = transformed weights [G*36][Cout][Cin] (launch_wino4_weights, computed
 // in double), ws = scratch of wino4_ws_floats() floats (the V and M frequency planes).
 bool wino4_eligible(const ConvParams &p);
 bool wino4_channels_ok(int Cin, int Cout);
 size_t wino4_ws_floats(int G, int B, int H, int W, int d, int Cin, int Cout);
+int wino4_num_tiles(int B, int H, int W, int d);   // NT of the layer's geometry
 int launch_wino4_weights(const float *w, float *U, int G, int Cout, int Cin, hipStream_t st);
 // U3 != nullptr: the split-precision ("bf16x3") plane GEMM of csrc/wino4_split.hip with the weights split by
 // launch_wino4_split_weights ([G*36][3][Cout][Cin] bf16) — an experiment, never the default
-int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3 = nullptr);
+// tile != nullptr: the plane GEMM runs exactly that instantiation (UOC_EINVAL if there is none or Cout % bn != 0) instead of
+// the static model's choice; pair loop and grid follow the library's own rules for the tile
+int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3 = nullptr,
+                      const W4Tile *tile = nullptr);
 int launch_wino4_split_weights(const float *U, unsigned short *U3, int G, int Cout, int Cin, hipStream_t st);
-int launch_wino4_slice_split(const ConvParams &p0, int Bg, int b0, const unsigned short *U3, float *ws, hipStream_t st);
+int launch_wino4_slice_split(const ConvParams &p0, int Bg, int b0, const unsigned short *U3, float *ws, hipStream_t st,
+                             const W4Tile *tile = nullptr);
 struct Wino4Geom;
 int w4_stage_output(const ConvParams &p, const Wino4Geom &geo, const float *Mw, hipStream_t st);
 long wino4_elem_blocks(long items);

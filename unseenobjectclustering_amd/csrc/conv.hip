@@ -429,43 +429,65 @@ static int pick_bm(int M, int ntiles, int G, int BN, const int *cands, int n) {
   return best;
 }
 
+// Every non-stem instantiation of conv_glds_kernel, ONE list: X(family, BM, BN, waves m, waves n).  The dispatch below, the
+// list the tests walk (conv_tile_list) and the single-tile test entry (launch_conv_tile) are all generated from it, so an
+// instantiation added here cannot be missed by the tests.  Families are the rows of kCfgs; their heights are kBmWide / kBmNarrow.
+#define UOC_DIRECT_TILES(X)                                                                  \
+  X(0, 96, 128, 2, 4) X(0, 128, 128, 2, 4) X(0, 160, 128, 2, 4) X(0, 192, 128, 2, 4)         \
+  X(1, 64, 128, 1, 8) X(1, 80, 128, 1, 8) X(1, 96, 128, 1, 8)                                \
+  X(2, 96, 64, 2, 4) X(2, 128, 64, 2, 4) X(2, 160, 64, 2, 4) X(2, 192, 64, 2, 4)             \
+  X(3, 64, 64, 1, 4) X(3, 80, 64, 1, 4) X(3, 96, 64, 1, 4)
+static const int kCfgProfClass[kNumCfg] = {KC_GLDS_160x128, KC_GLDS_80x128, KC_GLDS_160x64, KC_GLDS_80x64};
+
+// exactly the instantiation (family cfg, height bm); UOC_EINVAL if the list has no such tile
+static int launch_tile(const ConvParams &p, hipStream_t st, int cfg, int bm) {
+#define X(C, BM, BN, WM_, WN_) \
+  if (cfg == C && bm == BM) return launch_glds<BM, BN, WM_, WN_, false>(p, st, kCfgProfClass[C]);
+  UOC_DIRECT_TILES(X)
+#undef X
+  set_error("conv: no tile cfg=%d bm=%d", cfg, bm);
+  return UOC_EINVAL;
+}
+
+// Each tile family (wave layout x BN) is instantiated for several pixel-tile heights; the one
+// that packs (m-tiles x n-tiles x branches) best into whole rounds of 256 CUs is used, so the
+// stage-2 shapes (784 x #ROIs pixels) do not lose 30-45 % to tile quantisation.
+static int family_bm(const ConvParams &p, int cfg) {
+  const int M = p.B * p.Ho * p.Wo, BN = kCfgs[cfg].BN;
+  const bool wide = cfg == 0 || cfg == 2;
+  return pick_bm(M, p.Cout / BN, p.G, BN, wide ? kBmWide : kBmNarrow, wide ? 4 : 3);
+}
+
 static int launch_choice(const ConvParams &p, hipStream_t st, Choice c) {
-  if (c.glds) {
-    // Each tile family (wave layout x BN) is instantiated for several pixel-tile heights; the one
-    // that packs (m-tiles x n-tiles x branches) best into whole rounds of 256 CUs is used, so the
-    // stage-2 shapes (784 x #ROIs pixels) do not lose 30-45 % to tile quantisation.
-    const int M = p.B * p.Ho * p.Wo;
-    switch (c.cfg) {
-      case 0:
-        switch (pick_bm(M, p.Cout / 128, p.G, 128, kBmWide, 4)) {
-          case 96: return launch_glds<96, 128, 2, 4, false>(p, st, KC_GLDS_160x128);
-          case 128: return launch_glds<128, 128, 2, 4, false>(p, st, KC_GLDS_160x128);
-          case 192: return launch_glds<192, 128, 2, 4, false>(p, st, KC_GLDS_160x128);
-          default: return launch_glds<160, 128, 2, 4, false>(p, st, KC_GLDS_160x128);
-        }
-      case 1:
-        switch (pick_bm(M, p.Cout / 128, p.G, 128, kBmNarrow, 3)) {
-          case 64: return launch_glds<64, 128, 1, 8, false>(p, st, KC_GLDS_80x128);
-          case 96: return launch_glds<96, 128, 1, 8, false>(p, st, KC_GLDS_80x128);
-          default: return launch_glds<80, 128, 1, 8, false>(p, st, KC_GLDS_80x128);
-        }
-      case 2:
-        switch (pick_bm(M, p.Cout / 64, p.G, 64, kBmWide, 4)) {
-          case 96: return launch_glds<96, 64, 2, 4, false>(p, st, KC_GLDS_160x64);
-          case 128: return launch_glds<128, 64, 2, 4, false>(p, st, KC_GLDS_160x64);
-          case 192: return launch_glds<192, 64, 2, 4, false>(p, st, KC_GLDS_160x64);
-          default: return launch_glds<160, 64, 2, 4, false>(p, st, KC_GLDS_160x64);
-        }
-      case 3:
-        switch (pick_bm(M, p.Cout / 64, p.G, 64, kBmNarrow, 3)) {
-          case 64: return launch_glds<64, 64, 1, 4, false>(p, st, KC_GLDS_80x64);
-          case 96: return launch_glds<96, 64, 1, 4, false>(p, st, KC_GLDS_80x64);
-          default: return launch_glds<80, 64, 1, 4, false>(p, st, KC_GLDS_80x64);
-        }
-    }
-  }
+  if (c.glds && c.cfg >= 0 && c.cfg < kNumCfg) return launch_tile(p, st, c.cfg, family_bm(p, c.cfg));
   set_error("conv: bad choice cfg=%d", c.cfg);
   return UOC_EINVAL;
+}
+
+int conv_tile_list(int *out_pairs, int cap) {
+  int n = 0;
+#define X(C, BM, BN, WM_, WN_)      \
+  if (out_pairs && n < cap) {       \
+    out_pairs[2 * n] = C;           \
+    out_pairs[2 * n + 1] = BM;      \
+  }                                 \
+  ++n;
+  UOC_DIRECT_TILES(X)
+#undef X
+  return n;
+}
+
+// what the static model picks (host arithmetic only): the family, its height, and the height of each of the four families
+// (0 where Cout does not admit the family's BN) — the tuner may take any of them
+int conv_tile_choice(const ConvParams &p, int *cfg, int *bm, int *fam_bm) {
+  UOC_REQUIRE(p.Cin % BK == 0 && p.Cout % 64 == 0, "conv: Cin %% 32 or Cout %% 64 != 0");
+  const int c = pick_cfg(p);
+  UOC_REQUIRE(c >= 0, "conv: no tile configuration for Cout=%d", p.Cout);
+  if (cfg) *cfg = c;
+  if (bm) *bm = family_bm(p, c);
+  if (fam_bm)
+    for (int f = 0; f < kNumCfg; ++f) fam_bm[f] = p.Cout % kCfgs[f].BN ? 0 : family_bm(p, f);
+  return UOC_OK;
 }
 
 struct TuneKey {
@@ -638,6 +660,22 @@ int launch_conv(const ConvParams &p, hipStream_t st) {
     return UOC_EINVAL;
   }
   return launch_choice(p, st, ch);
+}
+
+// Test entry: exactly one instantiation, no tuner table read or written, no timing launches, no batch split.
+int launch_conv_tile(const ConvParams &p, hipStream_t st, int cfg, int bm) {
+  UOC_REQUIRE(p.in && p.w && p.out && !p.stem, "conv tile: null pointer or stem");
+  UOC_REQUIRE(p.G >= 1 && p.B >= 1 && p.H >= 1 && p.W >= 1 && p.Ho >= 1 && p.Wo >= 1, "conv tile: bad shape");
+  UOC_REQUIRE((long)p.B * p.H * p.W * p.Cin < (1l << 31) && (long)p.B * p.Ho * p.Wo * p.Cout < (1l << 31),
+              "conv tile: tensor too large for 32-bit indexing");
+  UOC_REQUIRE(p.Cin % BK == 0 && p.Cin >= BK, "conv tile: Cin=%d must be a multiple of %d", p.Cin, BK);
+  UOC_REQUIRE(cfg >= 0 && cfg < kNumCfg, "conv tile: no tile family %d", cfg);
+  UOC_REQUIRE(p.Cout >= kCfgs[cfg].BN && p.Cout % kCfgs[cfg].BN == 0, "conv tile: Cout=%d is not a multiple of the family's BN=%d",
+              p.Cout, kCfgs[cfg].BN);
+  const size_t halo = (size_t)(p.pad * p.W + p.pad) * p.Cin * 4;
+  UOC_REQUIRE((size_t)p.B * p.H * p.W * p.Cin * 4 + halo < (1ull << 31),
+              "conv tile: a group's input exceeds the 2 GB a 32-bit buffer offset addresses");
+  return launch_tile(p, st, cfg, bm);
 }
 
 // ---- NCHW(3) -> NHWC4 ------------------------------------------------------------------

@@ -121,6 +121,25 @@ static const std::vector<float> *find(const uoc_net *n, const std::string &key, 
   return &it->second;
 }
 
+// One group's weights w [Cout][Cin][K][K], each output channel scaled by scale[cout], into the layout the kernels read:
+// [tap][cout][cin], or for the stem [set][kh][cout][kw(8)][ch(4)] with set = cin / 3 (w_per_group floats per set; dst is
+// zero-filled by the caller: the stem's 8th column and 4th channel stay zero).
+static void relayout_weights(const float *w, const double *scale, int Cout, int Cin, int K, bool stem, size_t w_per_group,
+                             float *dst) {
+  for (int co = 0; co < Cout; ++co)
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int kh = 0; kh < K; ++kh)
+        for (int kw = 0; kw < K; ++kw) {
+          const double v = (double)w[(((size_t)co * Cin + ci) * K + kh) * K + kw] * scale[co];
+          size_t o;
+          if (stem)  // [set][kh][cout][kw(8)][ch(4)]
+            o = (size_t)(ci / 3) * w_per_group + ((size_t)kh * Cout + co) * 32 + kw * 4 + ci % 3;
+          else  // [tap][cout][cin]
+            o = ((size_t)(kh * K + kw) * Cout + co) * Cin + ci;
+          dst[o] = (float)v;
+        }
+}
+
 static int finalize_layer(uoc_net *n, ConvLayer &L) {
   const int G = n->G;
   const int T = L.stem ? 7 : L.K * L.K;
@@ -153,19 +172,8 @@ static int finalize_layer(uoc_net *n, ConvLayer &L) {
       if (!bi) return UOC_ENOENT;
       for (int c = 0; c < L.Cout; ++c) shift[c] += (double)(*bi)[c];
     }
-    float *dst = hw.data() + (size_t)g * sets * L.w_per_group;
-    for (int co = 0; co < L.Cout; ++co)
-      for (int ci = 0; ci < L.Cin; ++ci)
-        for (int kh = 0; kh < L.K; ++kh)
-          for (int kw = 0; kw < L.K; ++kw) {
-            const double v = (double)(*w)[(((size_t)co * L.Cin + ci) * L.K + kh) * L.K + kw] * scale[co];
-            size_t o;
-            if (L.stem)  // [set][kh][cout][kw(8)][ch(4)]
-              o = (size_t)(ci / 3) * L.w_per_group + ((size_t)kh * L.Cout + co) * 32 + kw * 4 + ci % 3;
-            else  // [tap][cout][cin]
-              o = ((size_t)(kh * L.K + kw) * L.Cout + co) * L.Cin + ci;
-            dst[o] = (float)v;
-          }
+    relayout_weights(w->data(), scale.data(), L.Cout, L.Cin, L.K, L.stem, L.w_per_group,
+                     hw.data() + (size_t)g * sets * L.w_per_group);
     for (int c = 0; c < L.Cout; ++c) hb[(size_t)g * L.Cout + c] = (float)shift[c];
   }
   UOC_HIP_CHECK(hipMalloc(&L.d_w, hw.size() * sizeof(float)));
@@ -409,18 +417,11 @@ int uoc_net_forward(uoc_net *n, const float *d_rgb, const float *d_xyz, int B, i
 /* Generic NHWC convolution entry (unit tests / integration): G independent groups stacked on the
  * leading dimension; per group: weights [T][Cout][Cin] with BN folded.  `algo` names the algorithm; nothing in the
  * environment decides it. */
-int uoc_conv2d_nhwc_algo(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out, int G,
-                         int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu, int algo,
-                         void *stream) {
-  UOC_REQUIRE(K == 1 || K == 3, "K=%d (only 1 or 3)", K);
-  UOC_REQUIRE(d_res == nullptr || d_res != d_out, "conv2d: the residual must not alias the output");
+static ConvParams entry_params(int G, int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu) {
   ConvParams p;
   p.tune = 0;   // static tile choice: no timing launches into the caller's buffers, no host-side sync
-  p.in = d_in;
-  p.w = d_w;
-  p.bias = d_bias;
-  p.res = d_res;
-  p.out = d_out;
+  p.in = p.w = p.bias = p.res = nullptr;
+  p.out = nullptr;
   p.G = G;
   p.B = B;
   p.H = H;
@@ -435,14 +436,41 @@ int uoc_conv2d_nhwc_algo(const float *d_in, const float *d_w, const float *d_bia
   p.stem = 0;
   p.Ho = (H + 2 * pad - dil * (K - 1) - 1) / stride + 1;
   p.Wo = (W + 2 * pad - dil * (K - 1) - 1) / stride + 1;
+  return p;
+}
+
+// tile = {cfg, bm} of uoc_conv2d_nhwc_tile, or nullptr: the library's own choice
+static int conv2d_entry(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out, int G,
+                        int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu, int algo,
+                        void *stream, const int *tile) {
+  UOC_REQUIRE(K == 1 || K == 3, "K=%d (only 1 or 3)", K);
+  UOC_REQUIRE(G >= 1 && B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && stride >= 1 && dil >= 1 && pad >= 0,
+              "conv2d: bad shape");
+  UOC_REQUIRE(d_res == nullptr || d_res != d_out, "conv2d: the residual must not alias the output");
+  ConvParams p = entry_params(G, B, H, W, Cin, Cout, K, stride, dil, pad, relu);
+  p.in = d_in;
+  p.w = d_w;
+  p.bias = d_bias;
+  p.res = d_res;
+  p.out = d_out;
   hipStream_t st = (hipStream_t)stream;
-  if (algo == UOC_CONV_DIRECT) return launch_conv(p, st);
+  if (algo == UOC_CONV_DIRECT) return tile ? launch_conv_tile(p, st, tile[0], tile[1]) : launch_conv(p, st);
+  const W4Tile w4tile = {tile ? tile[1] : 0, tile ? tile[0] : 0};   // Winograd: cfg = BN, bm = the GEMM tile height
+  const W4Tile *wt = tile ? &w4tile : nullptr;
   // scratch owned by this entry (kept between calls, grown on demand; the network path gets its scratch from the caller):
   // one caller thread at a time, as the header says — the mutex makes a violation slow instead of wrong
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_BF16X3) {
     UOC_REQUIRE(wino4_eligible(p), "conv2d: shape not eligible for Winograd F(4x4,3x3)");
+    if (tile) {   // refuse an unknown tile before any device work
+      int pairs[2 * 32];
+      const int n = wino4_tile_list(algo == UOC_CONV_WINOGRAD4_BF16X3, pairs, 32);
+      bool listed = false;
+      for (int i = 0; i < n && i < 32; ++i) listed = listed || (pairs[2 * i] == tile[0] && pairs[2 * i + 1] == tile[1]);
+      UOC_REQUIRE(listed, "conv2d tile: the plane GEMM has no tile BN=%d BM=%d", tile[0], tile[1]);
+      UOC_REQUIRE(Cout % tile[0] == 0, "conv2d tile: Cout=%d is not a multiple of BN=%d", Cout, tile[0]);
+    }
     static float *U4 = nullptr, *ws4 = nullptr;
     static unsigned short *U3 = nullptr;
     static size_t ucap4 = 0, wcap4 = 0, ucap3 = 0;
@@ -466,12 +494,116 @@ int uoc_conv2d_nhwc_algo(const float *d_in, const float *d_w, const float *d_bia
         ucap3 = 3 * un;
       }
       if (int rc = launch_wino4_split_weights(U4, U3, G, Cout, Cin, st)) return rc;
-      return launch_wino4_conv(p, U4, ws4, st, U3);
+      return launch_wino4_conv(p, U4, ws4, st, U3, wt);
     }
-    return launch_wino4_conv(p, U4, ws4, st);
+    return launch_wino4_conv(p, U4, ws4, st, nullptr, wt);
   }
   set_error("conv2d: unknown algorithm %d", algo);
   return UOC_EINVAL;
+}
+
+int uoc_conv2d_nhwc_algo(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out, int G,
+                         int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu, int algo,
+                         void *stream) {
+  return conv2d_entry(d_in, d_w, d_bias, d_res, d_out, G, B, H, W, Cin, Cout, K, stride, dil, pad, relu, algo, stream, nullptr);
+}
+
+int uoc_conv2d_nhwc_tile(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out, int G,
+                         int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu, int algo,
+                         void *stream, int cfg, int bm) {
+  UOC_REQUIRE(d_in && d_w && d_out, "conv2d tile: null pointer");
+  const int tile[2] = {cfg, bm};
+  return conv2d_entry(d_in, d_w, d_bias, d_res, d_out, G, B, H, W, Cin, Cout, K, stride, dil, pad, relu, algo, stream, tile);
+}
+
+int uoc_conv2d_tile_list(int algo, int32_t *out_pairs, int cap) {
+  UOC_REQUIRE(cap >= 0 && (out_pairs || cap == 0), "tile list: null array");
+  if (algo == UOC_CONV_DIRECT) return conv_tile_list(out_pairs, cap);
+  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_BF16X3)
+    return wino4_tile_list(algo == UOC_CONV_WINOGRAD4_BF16X3, out_pairs, cap);
+  set_error("tile list: unknown algorithm %d", algo);
+  return UOC_EINVAL;
+}
+
+int uoc_conv2d_tile_choice(int G, int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int algo, int32_t *cfg,
+                           int32_t *bm, int32_t *family_bm) {
+  UOC_REQUIRE(cfg && bm, "tile choice: null pointer");
+  UOC_REQUIRE(K == 1 || K == 3, "K=%d (only 1 or 3)", K);
+  UOC_REQUIRE(G >= 1 && B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && stride >= 1 && dil >= 1, "tile choice: bad shape");
+  const ConvParams p = entry_params(G, B, H, W, Cin, Cout, K, stride, dil, K == 3 ? dil : 0, 0);
+  if (algo == UOC_CONV_DIRECT) return conv_tile_choice(p, cfg, bm, family_bm);
+  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_BF16X3) {
+    UOC_REQUIRE(wino4_eligible(p), "tile choice: shape not eligible for Winograd F(4x4,3x3)");
+    int bn_ = 0, bm_ = 0;
+    wino4_tile_choice(algo == UOC_CONV_WINOGRAD4_BF16X3, wino4_num_tiles(B, H, W, dil), Cout, 36 * G, &bn_, &bm_);
+    *cfg = bn_;
+    *bm = bm_;
+    return UOC_OK;
+  }
+  set_error("tile choice: unknown algorithm %d", algo);
+  return UOC_EINVAL;
+}
+
+/* The stem alone (tests): NCHW(3) -> NHWC4, then the 7x7 s2 p3 instantiation, with host weights re-laid out by the function
+ * uoc_net_finalize uses.  Scratch is allocated and freed inside (the call synchronises the stream). */
+int uoc_net_stem(const float *d_nchw, const float *h_w, const float *h_bias, const float *d_res, int G, int B, int H, int W,
+                 int relu, float *d_out, void *stream) {
+  UOC_REQUIRE(d_nchw && h_w && d_out, "stem: null pointer");
+  UOC_REQUIRE(G >= 1 && B >= 1 && H >= 1 && W >= 1, "stem: bad shape");
+  UOC_REQUIRE(d_res == nullptr || d_res != d_out, "stem: the residual must not alias the output");
+  UOC_REQUIRE((long)G * B * H * W * 4 < (1l << 31), "stem: input too large");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t wpg = (size_t)7 * 64 * 32;
+  std::vector<float> hw((size_t)G * wpg, 0.f), hb((size_t)G * 64, 0.f);   // a NULL bias = all-zero rows
+  const std::vector<double> one(64, 1.0);
+  for (int g = 0; g < G; ++g) relayout_weights(h_w + (size_t)g * 64 * 3 * 49, one.data(), 64, 3, 7, true, wpg, hw.data() + g * wpg);
+  if (h_bias) hb.assign(h_bias, h_bias + (size_t)G * 64);
+  float *d_w = nullptr, *d_b = nullptr, *d_in4 = nullptr;
+  int rc = UOC_OK;
+  auto run = [&]() -> int {
+    UOC_HIP_CHECK(hipMalloc(&d_w, hw.size() * sizeof(float)));
+    UOC_HIP_CHECK(hipMalloc(&d_b, hb.size() * sizeof(float)));
+    UOC_HIP_CHECK(hipMalloc(&d_in4, (size_t)G * B * H * W * 4 * sizeof(float)));
+    UOC_HIP_CHECK(hipMemcpyAsync(d_w, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    UOC_HIP_CHECK(hipMemcpyAsync(d_b, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    if (int r = launch_nchw3_to_nhwc4(d_nchw, d_in4, G * B, H, W, st)) return r;
+    ConvLayer L;
+    L.Cin = 3;
+    L.Cout = 64;
+    L.K = 7;
+    L.stride = 2;
+    L.dil = 1;
+    L.pad = 3;
+    L.relu = relu;
+    L.has_bn = L.has_bias = false;
+    L.stem = true;
+    L.d_w = d_w;
+    L.d_b = d_b;
+    const Dims d = dims(H, W);
+    if (int r = run_conv(G, L, d_in4, d_res, d_out, B, H, W, d.H1, d.W1, st)) return r;
+    UOC_HIP_CHECK(hipStreamSynchronize(st));
+    return UOC_OK;
+  };
+  rc = run();
+  if (rc != UOC_OK) (void)hipStreamSynchronize(st);
+  if (d_w) (void)hipFree(d_w);
+  if (d_b) (void)hipFree(d_b);
+  if (d_in4) (void)hipFree(d_in4);
+  return rc;
+}
+
+int uoc_maxpool3x3s2_nhwc(const float *d_in, float *d_out, int n_img, int H, int W, int C, void *stream) {
+  UOC_REQUIRE(d_in && d_out && d_in != d_out, "maxpool: null or aliasing pointer");
+  UOC_REQUIRE(n_img >= 1 && H >= 1 && W >= 1 && C >= 4, "maxpool: bad shape");
+  UOC_REQUIRE((long)n_img * H * W * C < (1l << 31), "maxpool: tensor too large for 32-bit indexing");
+  return launch_maxpool3x3s2(d_in, d_out, n_img, H, W, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1, (hipStream_t)stream);
+}
+
+int uoc_head(const float *d_fa, const float *d_fb, float *d_embed, int B, int h, int w, int H, int W, int cat, void *stream) {
+  UOC_REQUIRE(d_fa && d_embed && (d_fb || !cat), "head: null pointer");
+  UOC_REQUIRE(B >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "head: bad shape");
+  UOC_REQUIRE((long)B * h * w * 64 < (1l << 31) && (long)B * H * W < (1l << 31) / 128, "head: tensor too large");
+  return launch_head(d_fa, d_fb, d_embed, B, h, w, H, W, cat, (hipStream_t)stream);
 }
 
 int uoc_conv2d_nhwc(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out, int G,

@@ -417,37 +417,58 @@ static int launch_wino4_gemm_t(const float *V, const float *U, float *Mo, int NT
 // Tile choice (static cost model, never timing: every candidate sums each output in the same cin order, so the result
 // does not depend on it): steps of the slowest block x tile area, mild preference for large tiles (fewer operand
 // bytes per MFMA).  One block per CU (the 110 KB LDS ring), grid = 8 XCDs x 32.
-static const int kW4Bm[4] = {96, 128, 160, 192};
-static void pick_wino4_tile(int NT, int Cout, int planes, int &bm, int &bn, int &nblocks) {
-  const int ncu = device_num_cu() > 0 ? device_num_cu() : 256;
-  const int per_xcd = ncu / 8 > 0 ? ncu / 8 : 1;
-  double best = -1;
-  bm = 160;
-  bn = Cout % 128 == 0 ? 128 : 64;
-  for (int n = 0; n < 2; ++n) {
-    const int BN = n ? 64 : 128;
-    if (Cout % BN) continue;
-    for (int i = 0; i < 4; ++i) {
-      const int BM = kW4Bm[i];
-      const long items = (long)planes * ((NT + BM - 1) / BM) * (Cout / BN);
-      const long S = (items + 7) / 8;
-      const long steps = (S + per_xcd - 1) / per_xcd;
-      const double cost = (double)steps * BM * BN * (1.0 + 0.05 * (192.0 / BM - 1.0)) * (BN == 64 ? 1.06 : 1.0);
-      if (best < 0 || cost < best) {
-        best = cost;
-        bm = BM;
-        bn = BN;
-      }
-    }
-  }
-  const long items = (long)planes * ((NT + bm - 1) / bm) * (Cout / bn);
-  const long S = (items + 7) / 8;
-  nblocks = 8 * (int)(S < per_xcd ? S : per_xcd);
+// Every (BM, BN) of wino4_gemm_kernel, ONE list, in the order the cost model walks it (the first of equal costs wins); each is
+// instantiated with and without the pair loop.  The dispatch, wino4_tile_list and the tests' single-tile entry come from it.
+#define UOC_W4_TILES(X) \
+  X(96, 128) X(128, 128) X(160, 128) X(192, 128) X(96, 64) X(128, 64) X(160, 64) X(192, 64)
+static const int kW4Tiles[][2] = {
+#define X(A, B) {A, B},
+    UOC_W4_TILES(X)
+#undef X
+};
+
+static int plane_per_xcd() {
+  const int dev = device_num_cu(), ncu = dev > 0 ? dev : 256;
+  return ncu / 8 > 0 ? ncu / 8 : 1;
 }
 
-static int launch_wino4_gemm(const float *V, const float *U, float *Mo, int NT, int Cin, int Cout, int planes, hipStream_t st) {
-  int bm, bn, nblocks;
-  pick_wino4_tile(NT, Cout, planes, bm, bn, nblocks);
+void wino4_pick_tile(const int (*tiles)[2], int n, int NT, int Cout, int planes, int &bm, int &bn) {
+  const int per_xcd = plane_per_xcd();
+  double best = -1;
+  for (int i = 0; i < n; ++i) {
+    const int BM = tiles[i][0], BN = tiles[i][1];
+    if (Cout % BN) continue;
+    const long items = (long)planes * ((NT + BM - 1) / BM) * (Cout / BN);
+    const long S = (items + 7) / 8;
+    const long steps = (S + per_xcd - 1) / per_xcd;
+    const double cost = (double)steps * BM * BN * (1.0 + 0.05 * (192.0 / BM - 1.0)) * (BN == 64 ? 1.06 : 1.0);
+    if (best < 0 || cost < best) {
+      best = cost;
+      bm = BM;
+      bn = BN;
+    }
+  }
+}
+
+// grid of a plane GEMM with tile (bm, bn): every XCD takes an eighth of the items, at most one block per CU
+int wino4_plane_grid(int NT, int Cout, int planes, int bm, int bn) {
+  const int per_xcd = plane_per_xcd();
+  const long items = (long)planes * ((NT + bm - 1) / bm) * (Cout / bn);
+  const long S = (items + 7) / 8;
+  return 8 * (int)(S < per_xcd ? S : per_xcd);
+}
+
+static int launch_wino4_gemm(const float *V, const float *U, float *Mo, int NT, int Cin, int Cout, int planes, hipStream_t st,
+                             const W4Tile *tile) {
+  int bm = 160, bn = Cout % 128 == 0 ? 128 : 64;
+  if (tile) {
+    bm = tile->bm;
+    bn = tile->bn;
+    UOC_REQUIRE((bn == 64 || bn == 128) && Cout % bn == 0, "winograd F(4x4): Cout=%d does not admit BN=%d", Cout, bn);
+  } else {
+    wino4_pick_tile(kW4Tiles, (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0])), NT, Cout, planes, bm, bn);
+  }
+  const int nblocks = wino4_plane_grid(NT, Cout, planes, bm, bn);
   // Pair loop (4-stage ring, one barrier per two K-chunks) against the 3-stage ring with one barrier per chunk, per launch shape,
   // same box: layer4 383 -> 377 / 569 -> 551 / 533 -> 516 us, layer3 117.4 -> 115.8 / 165 -> 161 / 150.5 -> 147 us, layer2
   // equal, the 2-chunk items of layer1 45.0 -> 45.6 us (worse: they keep the single-chunk loop); class average 154 -> 151.5 us
@@ -455,15 +476,31 @@ static int launch_wino4_gemm(const float *V, const float *U, float *Mo, int NT, 
   const bool pair = cpt % 2 == 0 && cpt >= 4;
   // 8 waves per block (two per SIMD: the younger wave's MFMAs cover the older one's vmcnt / barrier wait; the one-wave-per-SIMD
   // variant NW = 4 measured 15-25 % slower in round 5, HISTORY.md)
-#define W4_CASE(A, B)                                                                                                \
+#define X(A, B)                                                                                                      \
   if (bm == A && bn == B)                                                                                            \
     return pair ? launch_wino4_gemm_t<A, B, true, 8>(V, U, Mo, NT, Cin, Cout, planes, nblocks, st)                    \
                 : launch_wino4_gemm_t<A, B, false, 8>(V, U, Mo, NT, Cin, Cout, planes, nblocks, st);
-  W4_CASE(96, 128) W4_CASE(128, 128) W4_CASE(160, 128) W4_CASE(192, 128)
-  W4_CASE(96, 64) W4_CASE(128, 64) W4_CASE(160, 64) W4_CASE(192, 64)
-#undef W4_CASE
+  UOC_W4_TILES(X)
+#undef X
   set_error("winograd F(4x4): no GEMM tile %dx%d", bm, bn);
   return UOC_EINVAL;
+}
+
+int wino4_tile_list(bool split, int *out_pairs, int cap) {
+  if (split) return wino4_split_tile_list(out_pairs, cap);
+  const int n = (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0]));
+  for (int i = 0; i < n && i < cap && out_pairs; ++i) {
+    out_pairs[2 * i] = kW4Tiles[i][1];       // cfg = BN
+    out_pairs[2 * i + 1] = kW4Tiles[i][0];   // bm
+  }
+  return n;
+}
+
+void wino4_tile_choice(bool split, int NT, int Cout, int planes, int *bn, int *bm) {
+  if (split) return wino4_split_tile_choice(NT, Cout, planes, bn, bm);
+  *bm = 160;
+  *bn = Cout % 128 == 0 ? 128 : 64;
+  wino4_pick_tile(kW4Tiles, (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0])), NT, Cout, planes, *bm, *bn);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -478,6 +515,8 @@ bool wino4_eligible(const ConvParams &p) {
   return !p.stem && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == p.dil && wino4_channels_ok(p.Cin, p.Cout) &&
          p.Ho == p.H && p.Wo == p.W;
 }
+
+int wino4_num_tiles(int B, int H, int W, int d) { return make_geom4(B, H, W, d).NT; }
 
 size_t wino4_ws_floats(int G, int B, int H, int W, int d, int Cin, int Cout) {
   const Wino4Geom geo = make_geom4(B, H, W, d);
@@ -504,9 +543,9 @@ long wino4_elem_blocks(long items) {
   return (blocks + 7) / 8 * 8;     // a multiple of 8: the input transform deals its blocks to the XCDs in contiguous eighths
 }
 
-static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st);
+static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st, const W4Tile *tile);
 
-int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3) {
+int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3, const W4Tile *tile) {
   UOC_REQUIRE(wino4_eligible(p), "winograd F(4x4): layer not eligible");
   UOC_REQUIRE(U && ws && p.in && p.out, "winograd F(4x4): null tensor/weight/workspace pointer");
   const int planes = 36 * p.G;
@@ -522,11 +561,11 @@ int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_
     for (int b0 = 0; b0 < p.B; b0 += bmax) {
       ConvParams q = p;
       q.B = p.B - b0 < bmax ? p.B - b0 : bmax;
-      if (int rc = U3 ? launch_wino4_slice_split(q, p.B, b0, U3, ws, st) : launch_wino4_slice(q, p.B, b0, U, ws, st)) return rc;
+      if (int rc = U3 ? launch_wino4_slice_split(q, p.B, b0, U3, ws, st, tile) : launch_wino4_slice(q, p.B, b0, U, ws, st, tile)) return rc;
     }
     return UOC_OK;
   }
-  return U3 ? launch_wino4_slice_split(p, p.B, 0, U3, ws, st) : launch_wino4_slice(p, p.B, 0, U, ws, st);
+  return U3 ? launch_wino4_slice_split(p, p.B, 0, U3, ws, st, tile) : launch_wino4_slice(p, p.B, 0, U, ws, st, tile);
 }
 
 // ---- the three stages of one layer ---------------------------------------------------------------------------------
@@ -543,7 +582,8 @@ static int w4_stage_input(const ConvParams &p, const Wino4Geom &geo, float *V, h
   return UOC_OK;
 }
 
-static int w4_stage_gemm(const ConvParams &p, const Wino4Geom &geo, const float *U, float *V, float *Mw, hipStream_t st) {
+static int w4_stage_gemm(const ConvParams &p, const Wino4Geom &geo, const float *U, float *V, float *Mw, hipStream_t st,
+                         const W4Tile *tile) {
   const int planes = 36 * p.G;
   const double Mpix = (double)p.B * p.H * p.W;
   const ProfTag tag = {{geo.NT, p.Cin, p.Cout, p.dil}};
@@ -552,7 +592,7 @@ static int w4_stage_gemm(const ConvParams &p, const Wino4Geom &geo, const float 
   const double gflops = 2.0 * Mpix * p.Cout * p.Cin * 9.0 * p.G;
   const double gbytes = 4.0 * planes * ((double)geo.NT * p.Cin + (double)p.Cout * p.Cin + (double)geo.NT * p.Cout);
   ProfScope prof(KC_WINO4_GEMM, st, gflops, gbytes, tag);
-  return launch_wino4_gemm(V, U, Mw, geo.NT, p.Cin, p.Cout, planes, st);
+  return launch_wino4_gemm(V, U, Mw, geo.NT, p.Cin, p.Cout, planes, st, tile);
 }
 
 int w4_stage_output(const ConvParams &p, const Wino4Geom &geo, const float *Mw, hipStream_t st) {
@@ -567,7 +607,7 @@ int w4_stage_output(const ConvParams &p, const Wino4Geom &geo, const float *Mw, 
 }
 
 // images b0 .. b0 + p.B - 1 of a batch of Bg (activation tensors [g][Bg][H][W][C])
-static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st) {
+static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st, const W4Tile *tile) {
   ConvParams p = p0;
   const size_t img_in = (size_t)p.H * p.W * p.Cin, img_out = (size_t)p.H * p.W * p.Cout;
   p.in += (size_t)b0 * img_in;
@@ -577,7 +617,7 @@ static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float 
   geo.Bg = Bg;
   float *V = ws, *Mw = ws + (size_t)36 * p.G * geo.NT * p.Cin;
   if (int rc = w4_stage_input(p, geo, V, st)) return rc;
-  if (int rc = w4_stage_gemm(p, geo, U, V, Mw, st)) return rc;
+  if (int rc = w4_stage_gemm(p, geo, U, V, Mw, st, tile)) return rc;
   return w4_stage_output(p, geo, Mw, st);
 }
 

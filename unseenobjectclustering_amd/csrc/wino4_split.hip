@@ -424,34 +424,46 @@ static int launch_gemm3_t(const unsigned short *V3, const unsigned short *U3, fl
   return UOC_OK;
 }
 
-// Tile choice: the static cost model of csrc/wino4.hip over the tiles whose 3-stage ring fits 160 KB (BM + BN <= 256)
-static const int kW3Tiles[6][2] = {{128, 128}, {96, 128}, {192, 64}, {160, 64}, {128, 64}, {96, 64}};
-static int launch_gemm3(const unsigned short *V3, const unsigned short *U3, float *Mo, int NT, int Cin, int Cout, int planes,
-                        hipStream_t st) {
-  const int ncu = device_num_cu() > 0 ? device_num_cu() : 256;
-  const int per_xcd = ncu / 8 > 0 ? ncu / 8 : 1;
-  double best = -1;
-  int bm = 128, bn = Cout % 128 == 0 ? 128 : 64;
-  for (const auto &tl : kW3Tiles) {
-    const int BM = tl[0], BN = tl[1];
-    if (Cout % BN) continue;
-    const long items = (long)planes * ((NT + BM - 1) / BM) * (Cout / BN);
-    const long S = (items + 7) / 8;
-    const long steps = (S + per_xcd - 1) / per_xcd;
-    const double cost = (double)steps * BM * BN * (1.0 + 0.05 * (192.0 / BM - 1.0)) * (BN == 64 ? 1.06 : 1.0);
-    if (best < 0 || cost < best) {
-      best = cost;
-      bm = BM;
-      bn = BN;
-    }
+// Tile choice: the static cost model of csrc/wino4.hip over the tiles whose 3-stage ring fits 160 KB (BM + BN <= 256).  ONE list
+// of the instantiations of wino4_gemm3_kernel, in the order the cost model walks it: dispatch, wino4_split_tile_list and the
+// tests' single-tile entry come from it.
+#define UOC_W3_TILES(X) X(128, 128) X(96, 128) X(192, 64) X(160, 64) X(128, 64) X(96, 64)
+static const int kW3Tiles[][2] = {
+#define X(A, B) {A, B},
+    UOC_W3_TILES(X)
+#undef X
+};
+constexpr int kNumW3Tiles = (int)(sizeof(kW3Tiles) / sizeof(kW3Tiles[0]));
+
+int wino4_split_tile_list(int *out_pairs, int cap) {
+  for (int i = 0; i < kNumW3Tiles && i < cap && out_pairs; ++i) {
+    out_pairs[2 * i] = kW3Tiles[i][1];       // cfg = BN
+    out_pairs[2 * i + 1] = kW3Tiles[i][0];   // bm
   }
-  const long items = (long)planes * ((NT + bm - 1) / bm) * (Cout / bn);
-  const long S = (items + 7) / 8;
-  const int nblocks = 8 * (int)(S < per_xcd ? S : per_xcd);
-#define W3_CASE(A, B) \
+  return kNumW3Tiles;
+}
+
+void wino4_split_tile_choice(int NT, int Cout, int planes, int *bn, int *bm) {
+  *bm = 128;
+  *bn = Cout % 128 == 0 ? 128 : 64;
+  wino4_pick_tile(kW3Tiles, kNumW3Tiles, NT, Cout, planes, *bm, *bn);
+}
+
+static int launch_gemm3(const unsigned short *V3, const unsigned short *U3, float *Mo, int NT, int Cin, int Cout, int planes,
+                        hipStream_t st, const W4Tile *tile) {
+  int bm, bn;
+  if (tile) {
+    bm = tile->bm;
+    bn = tile->bn;
+    UOC_REQUIRE((bn == 64 || bn == 128) && Cout % bn == 0, "winograd F(4x4) bf16x3: Cout=%d does not admit BN=%d", Cout, bn);
+  } else {
+    wino4_split_tile_choice(NT, Cout, planes, &bn, &bm);
+  }
+  const int nblocks = wino4_plane_grid(NT, Cout, planes, bm, bn);
+#define X(A, B) \
   if (bm == A && bn == B) return launch_gemm3_t<A, B>(V3, U3, Mo, NT, Cin, Cout, planes, nblocks, st);
-  W3_CASE(128, 128) W3_CASE(96, 128) W3_CASE(192, 64) W3_CASE(160, 64) W3_CASE(128, 64) W3_CASE(96, 64)
-#undef W3_CASE
+  UOC_W3_TILES(X)
+#undef X
   set_error("winograd F(4x4) bf16x3: no GEMM tile %dx%d", bm, bn);
   return UOC_EINVAL;
 }
@@ -467,7 +479,8 @@ int launch_wino4_split_weights(const float *U, unsigned short *U3, int G, int Co
 
 // images b0 .. b0 + p.B - 1 of a batch of Bg: the three stages with the split-precision GEMM.  ws layout: V3 (1.5 halves of
 // wino4_ws_floats's unit) then M.
-int launch_wino4_slice_split(const ConvParams &p0, int Bg, int b0, const unsigned short *U3, float *ws, hipStream_t st) {
+int launch_wino4_slice_split(const ConvParams &p0, int Bg, int b0, const unsigned short *U3, float *ws, hipStream_t st,
+                             const W4Tile *tile) {
   ConvParams p = p0;
   const size_t img_in = (size_t)p.H * p.W * p.Cin, img_out = (size_t)p.H * p.W * p.Cout;
   p.in += (size_t)b0 * img_in;
@@ -493,7 +506,7 @@ int launch_wino4_slice_split(const ConvParams &p0, int Bg, int b0, const unsigne
     const double gflops = 2.0 * Mpix * p.Cout * p.Cin * 9.0 * p.G;
     const double gbytes = (double)planes * (6.0 * geo.NT * p.Cin + 6.0 * p.Cout * p.Cin + 4.0 * geo.NT * p.Cout);
     ProfScope prof(KC_WINO4_GEMM, st, gflops, gbytes, tag);
-    if (int rc = launch_gemm3(V3, U3, Mw, geo.NT, p.Cin, p.Cout, planes, st)) return rc;
+    if (int rc = launch_gemm3(V3, U3, Mw, geo.NT, p.Cin, p.Cout, planes, st, tile)) return rc;
   }
   return w4_stage_output(p, geo, Mw, st);
 }
