@@ -281,7 +281,8 @@ int uoc_roi_match_stats(const int32_t *d_labels_crop, const float *d_mask_crops,
 
 /* match_label_crop part 2 (:156-177): d_map[k][c] = global id of kept cluster c (0 = dropped),
  * d_order = ROI paint order (far to near); nearest-resize each crop back to its box and paste
- * non-zeros, later ROIs overwrite earlier ones.  d_refined [H*W] is fully written. */
+ * non-zeros, later ROIs overwrite earlier ones.  d_refined [H*W] is fully written.  K in 1..127, S, H, W >= 1:
+ * UOC_EINVAL before any launch otherwise, like the other ROI calls. */
 int uoc_roi_paste(const int32_t *d_labels_crop, const uoc_roi_table *d_table, const int32_t *d_map,
                   const int32_t *d_order, int K, int S, int H, int W, int32_t *d_refined, void *stream);
 

@@ -557,7 +557,8 @@ int uoc_roi_match_stats(const int32_t *d_labels_crop, const float *d_mask_crops,
 int uoc_roi_paste(const int32_t *d_labels_crop, const uoc_roi_table *d_table, const int32_t *d_map,
                   const int32_t *d_order, int K, int S, int H, int W, int32_t *d_refined, void *stream) {
   UOC_REQUIRE(d_labels_crop && d_table && d_map && d_order && d_refined, "null pointer");
-  UOC_REQUIRE(K >= 1 && K < NL, "K=%d out of range", K);
+  // S = 0 would clamp the source index to S - 1 = -1 and read in front of the crop
+  UOC_REQUIRE(K >= 1 && K < NL && S >= 1 && H >= 1 && W >= 1, "K=%d S=%d H=%d W=%d out of range", K, S, H, W);
   hipLaunchKernelGGL(paste_kernel, dim3(grid_for(H * W)), dim3(256), 0, (hipStream_t)stream, d_labels_crop, d_table,
                      d_map, d_order, K, S, H, W, d_refined);
   UOC_LAUNCH_CHECK();
