@@ -1,0 +1,354 @@
+"""The cosine clustering kernels (csrc/meanshift.hip) through the C ABI, stage by stage, against the float64 restatement
+tests/ms_cosine_reference.py.
+
+Decisions (farthest-point sampling, seed components, assignment, the swap, the whole call without iterations) run on inputs
+whose fp32 arithmetic is exact in every summation order (tests/ms_cosine_cases.py; proved on the CPU in
+test_ms_cosine_host.py): every integer is compared exactly, no pixel is exempt.  Hill climbing is compared with float64
+under a tolerance measured per case: K_CLIMB x the larger deviation from float64 of two other fp32 evaluations (the torch
+oracle and a 16-pixel-tile summation).  profiles/ms_cosine_error.md holds the measured deviations; one lost or repeated pixel
+moves every case by at least 10 x its tolerance (test_ms_cosine_host.py)."""
+import numpy as np
+import pytest
+import torch
+
+from tests import ms_cosine_cases as CS
+from tests import ms_cosine_reference as R
+from tests.golden.cases import EPSILON, KAPPA
+from unseenobjectclustering_amd import _native
+from unseenobjectclustering_amd.utils import mean_shift as MS
+
+pytestmark = pytest.mark.gpu
+assert KAPPA == CS.KAPPA
+
+
+def to_dev(a, device):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+# ---- the stage entry points ------------------------------------------------------------------------------------------
+def hill_climb_raw(X, Z0, iters, n=None):
+    """uoc_ms_hill_climb on device tensors X [B, >= n, 64] (n rows are read), Z0 [B, m, 64] -> the new seeds."""
+    L = _native.lib()
+    batch, m = X.shape[0], Z0.shape[1]
+    n = X.shape[1] if n is None else n
+    assert batch == 1 or n == X.shape[1]
+    ws = MS._workspace(X.device, L.uoc_ms_workspace_bytes(batch, n, m))
+    Z = Z0.clone()
+    with torch.cuda.device(X.device):
+        rc = L.uoc_ms_hill_climb(_native.ptr(X), batch, n, _native.ptr(Z), m, KAPPA, iters, _native.ptr(ws), ws.numel(),
+                                 _native.stream_ptr(X.device))
+    _native.check(rc, "uoc_ms_hill_climb")
+    torch.cuda.synchronize(X.device)
+    return Z
+
+
+def select_raw(device, X, m, first=None, init=None, num_init=0):
+    """uoc_ms_select_seeds (no init) / uoc_ms_select_seeds_from on X [B, n, 64] -> (indices [B, m], seeds [B, m, 64]) numpy."""
+    L = _native.lib()
+    Xd = to_dev(X, device)
+    B, n = X.shape[0], X.shape[1]
+    seeds = torch.full((B, m, 64), 9.0, device=device) if init is None else to_dev(init, device)
+    idx = torch.full((B, m), -7, dtype=torch.int32, device=device)
+    firstd = None if first is None else torch.tensor(first, dtype=torch.int32, device=device)
+    ws = MS._workspace(device, L.uoc_ms_workspace_bytes(B, n, m))
+    with torch.cuda.device(device):
+        if init is None:
+            rc = L.uoc_ms_select_seeds(_native.ptr(Xd), B, n, m, _native.ptr(firstd), _native.ptr(seeds), _native.ptr(idx),
+                                       _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
+        else:
+            rc = L.uoc_ms_select_seeds_from(_native.ptr(Xd), B, n, m, num_init, _native.ptr(firstd), _native.ptr(seeds),
+                                            _native.ptr(idx), _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
+        _native.check(rc, "uoc_ms_select_seeds")
+        _native.check(L.uoc_ms_check(_native.stream_ptr(device)), "uoc_ms_check")
+    return idx.cpu().numpy(), seeds.cpu().numpy()
+
+
+def both_sampling_kernels(fn):
+    """fn() with the on-chip persistent kernel, then with the one-launch-per-step kernel; the setting is restored."""
+    L = _native.lib()
+    try:
+        for on in (1, 0):
+            L.uoc_ms_set_persistent_fps(on)
+            fn("on-chip" if on else "streaming")
+    finally:
+        L.uoc_ms_set_persistent_fps(1)
+
+
+def components_raw(device, Z, eps):
+    """uoc_ms_seed_components on Z [B, m, 64] -> (labels [B, m], num_unique [B]) numpy."""
+    L = _native.lib()
+    Zd = to_dev(Z, device)
+    B, m = Z.shape[0], Z.shape[1]
+    out = torch.full((B, m), -7, dtype=torch.int32, device=device)
+    nu = torch.full((B,), -7, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        rc = L.uoc_ms_seed_components(_native.ptr(Zd), B, m, float(eps), _native.ptr(out), _native.ptr(nu), _native.stream_ptr(device))
+    _native.check(rc, "uoc_ms_seed_components")
+    return out.cpu().numpy(), nu.cpu().numpy()
+
+
+def assign_raw(device, X, Z, sl, nu):
+    """uoc_ms_assign and uoc_ms_confidence on X [B, n, 64], Z [B, m, 64], seed labels [B, m], num_unique [B]
+    -> ((labels, closest) of the assignment, (labels, closest) of the confidence call), numpy [B, n]."""
+    L = _native.lib()
+    Xd, Zd = to_dev(X, device), to_dev(Z, device)
+    sld, nud = to_dev(np.asarray(sl, np.int32), device), to_dev(np.asarray(nu, np.int32), device)
+    B, n, m = X.shape[0], X.shape[1], Z.shape[1]
+    la, ca, lc, cc = (torch.full((B, n), -7, dtype=torch.int32, device=device) for _ in range(4))
+    margin = torch.empty((B, n), device=device)
+    ws = MS._workspace(device, L.uoc_ms_workspace_bytes(B, n, m))
+    nws = L.uoc_ms_confidence_workspace_bytes(B, n, m, 1)
+    cws = torch.empty(nws, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        rc = L.uoc_ms_assign(_native.ptr(Xd), B, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, _native.ptr(la),
+                             _native.ptr(ca), _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
+        _native.check(rc, "uoc_ms_assign")
+        rc = L.uoc_ms_confidence(_native.ptr(Xd), 1, B, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, 0, _native.ptr(lc),
+                                 _native.ptr(margin), None, _native.ptr(cc), None, _native.ptr(cws), nws, _native.stream_ptr(device))
+        _native.check(rc, "uoc_ms_confidence")
+    return (la.cpu().numpy(), ca.cpu().numpy()), (lc.cpu().numpy(), cc.cpu().numpy())
+
+
+# ---- 3a. hill climbing against float64 ---------------------------------------------------------------------------------
+def climb_rows(what, got, fields, seeds, iters, check=None):
+    """Per checked field: (name, kernel deviation from float64, the oracle's, the tile order's, the tolerance)."""
+    rows = []
+    for b in (range(len(fields)) if check is None else check):
+        ref, dev_o, dev_t = CS.climb_yardstick(fields[b], seeds[b], KAPPA, iters)
+        err = float(np.abs(got[b].astype(np.float64) - ref).max())
+        rows.append((what if len(fields) == 1 else "%s field %d" % (what, b), err, dev_o, dev_t, CS.climb_tolerance(dev_o, dev_t)))
+    return rows
+
+
+def run_climb(device, what, fields, seeds, iters, check=None):
+    got = hill_climb_raw(to_dev(np.stack(fields), device), to_dev(np.stack(seeds), device), iters).cpu().numpy()
+    assert np.isfinite(got).all()
+    return climb_rows(what, got, fields, seeds, iters, check)
+
+
+def tile_case(device, m, iters):
+    X = CS.hc_field(1961)
+    return run_climb(device, "n 1961 m %d iters %d" % (m, iters), [X], [CS.hc_seeds(X, m)[0]], iters)
+
+
+def edge_case(device, n, m):
+    fields = [CS.hc_field(n, seed=1 + k) for k in range(3 if n == 4097 else 1)]
+    return run_climb(device, "n %d m %d" % (n, m), fields, [CS.hc_seeds(X, m, k)[0] for k, X in enumerate(fields)], 10)
+
+
+def strided_case(device):
+    batch, n, m = CS.HC_STRIDED
+    fields = [CS.hc_field(n, seed=100 + b) for b in range(batch)]
+    return run_climb(device, "batch %d n %d" % (batch, n), fields, [CS.hc_seeds(X, m, b)[0] for b, X in enumerate(fields)], 10)
+
+
+def affine_case(device):
+    batch, n, m, check = CS.HC_AFFINE
+    fields = [CS.hc_affine_field(b) for b in range(batch)]
+    return run_climb(device, "batch %d n %d" % (batch, n), fields, [CS.hc_seeds(X, m, b)[0] for b, X in enumerate(fields)], 10, check)
+
+
+def wide_case(device, n, m):
+    X = CS.hc_field(n, seed=7, channels=128)
+    Xd = MS.to_planes(to_dev(X, device)[None])
+    _, idx, Z, _ = MS.cluster_batch(Xd, [CS.WIDE_FIRST], KAPPA, m, 10, EPSILON, return_parts=True, metric="cosine")
+    torch.cuda.synchronize(device)
+    idx = idx[0].cpu().numpy()
+    assert idx[0] == CS.WIDE_FIRST and idx.min() >= 0 and idx.max() < n
+    got = Z[0].permute(1, 0, 2).reshape(m, 128).cpu().numpy()
+    return climb_rows("128-d n %d m %d" % (n, m), [got], [X], [X[idx]], 10)
+
+
+def climb_cases():
+    """Every 3a case: name -> function(device) -> rows.  scripts/ms_cosine_error.py prints them all."""
+    out = {}
+    for iters in CS.HC_TILE_ITERS:
+        for m in CS.HC_TILE_M:
+            out["tile m%d iters%d" % (m, iters)] = lambda device, m=m, iters=iters: tile_case(device, m, iters)
+    for m in CS.HC_EDGE_M:
+        for n in CS.HC_EDGE_N + [4097]:
+            out["edge n%d m%d" % (n, m)] = lambda device, n=n, m=m: edge_case(device, n, m)
+    out["strided"] = strided_case
+    out["affine"] = affine_case
+    for n, m in CS.HC_WIDE:
+        out["wide n%d m%d" % (n, m)] = lambda device, n=n, m=m: wide_case(device, n, m)
+    return out
+
+
+def assert_rows(rows):
+    for name, err, dev_o, dev_t, tol in rows:
+        print("%-32s kernel %.3e  oracle %.3e  tiles %.3e  ratio %.2f  (K = %g)" % (name, err, dev_o, dev_t, err / max(dev_o, dev_t), CS.K_CLIMB))
+    for name, err, dev_o, dev_t, tol in rows:
+        assert err <= tol, "%s: %.3e from float64, allowed %.3e = %g x max(oracle %.3e, tiles %.3e)" % (name, err, tol, CS.K_CLIMB, dev_o, dev_t)
+
+
+@pytest.mark.parametrize("iters", CS.HC_TILE_ITERS)
+@pytest.mark.parametrize("m", CS.HC_TILE_M)
+def test_climb_every_seed_tile_count(device, m, iters):
+    """hc_iter_flat_kernel<ST, QUAD> for ST = 1..8, QUAD where the last seed tile holds 1..4 seeds (m = 16k + 2), not QUAD at
+    16k + 9, and the full-tile boundaries 16k: n = 37 x 53, one and ten iterations."""
+    assert_rows(tile_case(device, m, iters))
+
+
+@pytest.mark.parametrize("m", CS.HC_EDGE_M)
+@pytest.mark.parametrize("n", CS.HC_EDGE_N + [4097])
+def test_climb_pixel_count_edges(device, n, m):
+    """One partial tile, waves without a tile, the step from one virtual block to two at 1024 | 1025; n = 4097 as three fields."""
+    assert_rows(edge_case(device, n, m))
+
+
+def test_climb_more_items_than_blocks(device):
+    """300 fields of 144 pixels: the strided item walk; every field against its own float64 run."""
+    rows = strided_case(device)
+    assert len(rows) == CS.HC_STRIDED[0]
+    assert_rows(rows)
+
+
+def test_climb_two_virtual_blocks_per_field(device):
+    """256 fields of 2048 pixels (two virtual blocks each, 512 items): neighbours point opposite ways, so a seed fragment or a
+    pixel tile of the wrong field is an O(1) error."""
+    rows = affine_case(device)
+    assert len(rows) == 5
+    assert_rows(rows)
+
+
+@pytest.mark.parametrize("n,m", CS.HC_WIDE)
+def test_climb_128d(device, n, m):
+    """hc_iter_kernel (two planes) through the whole call: the returned Z against the float64 climb from the returned indices."""
+    assert_rows(wide_case(device, n, m))
+
+
+@pytest.mark.parametrize("n", CS.HC_OVERREAD_N)
+def test_climb_reads_no_row_beyond_n(device, n):
+    """The field inside a larger buffer whose rows from n on are (a) the opposite of the field's dominant direction, (b) seed 0
+    itself, which a kernel that read them would weigh e^20: bit for bit the result of the tight buffer."""
+    m = 100
+    X = CS.hc_field(n, seed=7)
+    Z0 = to_dev(CS.hc_seeds(X, m)[0][None], device)
+    tight = hill_climb_raw(to_dev(X[None], device), Z0, 10)
+    mean = X.astype(np.float64).sum(axis=0)
+    for fill in (-(mean / np.linalg.norm(mean)), CS.hc_seeds(X, m)[0][0]):
+        buf = np.empty((1, n + 2048, 64), np.float32)
+        buf[0, :n] = X
+        buf[0, n:] = fill.astype(np.float32)
+        got = hill_climb_raw(to_dev(buf, device), Z0, 10, n=n)
+        assert torch.equal(got, tight)
+    assert torch.isfinite(tight).all() and not torch.equal(tight, Z0)
+
+
+# ---- 3b. farthest-point sampling, exact ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(CS.fps_cases()))
+def test_sampling_exact_ties(device, name):
+    """Exact ties between pixels of one 16-lane row group, of two waves, of two blocks of either kernel: the lower index."""
+    c = CS.fps_cases()[name]
+    want, _ = R.select_seeds(c["X"], c["m"], c["first"])
+
+    def check(kernel):
+        idx, seeds = select_raw(device, c["X"][None], c["m"], [c["first"]])
+        assert np.array_equal(idx[0], want), kernel
+        assert np.array_equal(seeds[0], R.seed_rows(c["X"], want)), kernel
+    both_sampling_kernels(check)
+
+
+@pytest.mark.parametrize("name", list(CS.fps_continuation_cases()))
+def test_sampling_continuation_exact(device, name):
+    c = CS.fps_continuation_cases()[name]
+    want, _ = R.select_seeds(c["X"], c["m"], None, c["init"], c["num_init"])
+
+    def check(kernel):
+        idx, seeds = select_raw(device, c["X"][None], c["m"], None, c["init"][None], c["num_init"])
+        assert np.array_equal(idx[0], want), kernel
+        assert np.array_equal(seeds[0], R.seed_rows(c["X"], want, c["init"])), kernel
+    both_sampling_kernels(check)
+
+
+def test_sampling_batch_exact(device):
+    c = CS.fps_batch_case()
+    want = [R.select_seeds(c["X"][b], c["m"], c["first"][b])[0] for b in range(3)]
+
+    def check(kernel):
+        idx, seeds = select_raw(device, c["X"], c["m"], c["first"])
+        for b in range(3):
+            assert np.array_equal(idx[b], want[b]), (kernel, b)
+            assert np.array_equal(seeds[b], R.seed_rows(c["X"][b], want[b])), (kernel, b)
+    both_sampling_kernels(check)
+
+
+# ---- 3c. seed components, exact -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("eps", [CS.EPS_EXACT, CS.EPS_PRODUCT])
+@pytest.mark.parametrize("name", list(CS.cc_cases()))
+def test_components_exact(device, name, eps):
+    """Pairs exactly at eps are members (<=); the mode of the labels present, ties to the smallest; members are overwritten."""
+    Z, _ = CS.cc_cases()[name]
+    want, _ = R.seed_components(Z, eps)
+    got, nu = components_raw(device, Z[None], eps)
+    assert np.array_equal(got[0], want) and nu[0] == len(np.unique(want))
+
+
+@pytest.mark.parametrize("m", [m for m in CS.CC_M if m > 5])
+def test_components_batch_exact(device, m):
+    Zb = np.stack([CS.cc_chain(m, "low", "tied"), CS.cc_chain(m, "high", "majority"), CS.cc_chain(m, "high", "tied")])
+    got, nu = components_raw(device, Zb, CS.EPS_EXACT)
+    for b in range(3):
+        want, _ = R.seed_components(Zb[b], CS.EPS_EXACT)
+        assert np.array_equal(got[b], want) and nu[b] == len(np.unique(want)), b
+
+
+# ---- 3d. assignment and the swap, exact ------------------------------------------------------------------------------------
+def check_assignment(device, X, Z, sl, nu):
+    """Batched inputs through both calls: closest and labels exact against the reference, the confidence call's equal."""
+    (la, ca), (lc, cc) = assign_raw(device, X, Z, sl, nu)
+    for b in range(X.shape[0]):
+        labels, closest, _ = R.assign(X[b], Z[b], sl[b], nu[b])
+        assert np.array_equal(ca[b], closest), "closest, field %d" % b
+        assert np.array_equal(la[b], labels), "labels, field %d" % b
+    assert np.array_equal(lc, la) and np.array_equal(cc, ca), "uoc_ms_confidence differs from uoc_ms_assign"
+
+
+@pytest.mark.parametrize("n", CS.ASSIGN_N)
+@pytest.mark.parametrize("m", CS.ASSIGN_M)
+def test_assignment_exact_ties(device, m, n):
+    """A pixel equidistant from two seeds of one 16-seed tile, of two tiles on one lane, of two tiles and lanes, in every pixel
+    slot of a lane: the lower seed.  Three fields: the pixels rotated, the seed labels shifted."""
+    Z = CS.assign_seeds(m)
+    sl, nu = CS.assign_labels(m)
+    X = CS.assign_pixels(n)
+    Xb = np.stack([np.roll(X, b, axis=0) for b in range(3)])
+    slb = np.stack([(sl + b) % nu for b in range(3)]).astype(np.int32)
+    check_assignment(device, Xb, np.stack([Z] * 3), slb, [nu] * 3)
+
+
+@pytest.mark.parametrize("m", CS.PAD_M)
+def test_assignment_padding_rows_never_win(device, m):
+    """Every real seed is farther than 1/2 from every pixel: a zero padding row of the last seed tile, unmasked, would win."""
+    X, Z = CS.padding_case(m)
+    sl = (np.arange(m) % 3).astype(np.int32)
+    (la, ca), _ = assign_raw(device, X[None], Z[None], sl[None], [len(np.unique(sl))])
+    assert ca.min() >= 0 and ca.max() < m
+    check_assignment(device, X[None], Z[None], sl[None], [len(np.unique(sl))])
+
+
+@pytest.mark.parametrize("name", list(CS.swap_cases()))
+def test_swap_exact(device, name):
+    """The largest cluster becomes 0: equal counts (the first wins), a largest label that is not 0, labels with a gap."""
+    X, Z, sl, nu = CS.swap_cases()[name]
+    check_assignment(device, X[None], Z[None], sl[None], [nu])
+
+
+# ---- 3e. the whole call on exact inputs --------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,m,wide,batch", CS.WHOLE)
+def test_whole_call_exact(device, n, m, wide, batch):
+    """No iteration: the seeds stay rows of the field, so sampling, components, assignment and swap are all exact."""
+    fields = [CS.whole_field(n, k, wide) for k in range(batch)]
+    firsts = [(37 * k + 11) % n for k in range(batch)]
+    Xd = to_dev(np.stack(fields), device)
+    labels, idx, Z, sl = MS.cluster_batch(MS.to_planes(Xd) if wide else Xd, firsts, KAPPA, m, 0, EPSILON, return_parts=True,
+                                          metric="cosine")
+    torch.cuda.synchronize(device)
+    for k in range(batch):
+        wl, wi, _, ws = R.cluster(fields[k], KAPPA, m, 0, EPSILON, firsts[k])
+        assert np.array_equal(idx[k].cpu().numpy(), wi), "indices, field %d" % k
+        rows = fields[k][wi]
+        assert np.array_equal(Z[k].cpu().numpy(), R.planes(rows) if wide else rows), "Z, field %d" % k
+        assert np.array_equal(sl[k].cpu().numpy(), ws), "seed labels, field %d" % k
+        assert np.array_equal(labels[k].cpu().numpy(), wl), "labels, field %d" % k
