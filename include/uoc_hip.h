@@ -100,7 +100,10 @@ int uoc_ms_seed_components(const float *d_Z, int batch, int m, float epsilon, in
                            int32_t *d_num_unique, void *stream);
 
 /* Nearest-seed assignment + "largest cluster becomes label 0" — mean_shift.py:211-227.
- * d_labels [batch][n] int32; d_closest (nullable) [batch][n] int32 = argmin seed. */
+ * d_labels [batch][n] int32; d_closest (nullable) [batch][n] int32 = argmin seed.
+ * A pixel no seed wins (a non-finite row of d_X or only non-finite seeds: no distance compares below +inf) gets label 0,
+ * is counted under label 0 for the swap, and closest = INT_MAX.  A seed label outside 0..127 is written to d_labels as
+ * it is and left out of the counts.  The same holds for uoc_ms_assign_ex with either metric. */
 int uoc_ms_assign(const float *d_X, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
                   const int32_t *d_num_unique, int m, int32_t *d_labels, int32_t *d_closest,
                   void *d_ws, size_t ws_bytes, void *stream);
@@ -879,10 +882,10 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
  *   second(p) = the same swap applied to seed_labels[rival], or -1
  *   closest(p) = best(p)
  * d_labels [batch][n] int32 and d_margin [batch][n] float are required; d_second, d_closest, d_rival [batch][n] int32 are
- * nullable.  d_labels and d_closest are bit-identical to what uoc_ms_assign writes for the same inputs, for finite rows of
- * d_X and d_Z and seed labels in 0..127; outside that uoc_ms_assign indexes its tables out of range while this call
- * writes label 0 for a pixel no seed wins (a NaN row; closest is then INT_MAX) and leaves labels outside 0..127 out of the
- * histogram.  Minima over a fixed set with index tie-breaks: the result does not depend on launch order or batch.
+ * nullable.  d_labels and d_closest are bit-identical to what uoc_ms_assign writes for the same inputs (the two
+ * kernels share the code that computes and stores them).  A pixel no seed wins (a NaN row) gets label 0 and closest = INT_MAX as there, and margin = 1.0f,
+ * second = rival = -1; labels outside 0..127 are left out of the histogram.  Minima over a fixed set with index
+ * tie-breaks: the result does not depend on launch order or batch.
  * metric must be UOC_METRIC_COSINE; UOC_METRIC_EUCLIDEAN is not built (the square root near zero needs its own error
  * analysis) and returns UOC_EINVAL saying so.
  * Returns UOC_EINVAL before any device work for null required pointers, bad ranges, d_X or d_Z not 16-byte aligned, a

@@ -311,3 +311,33 @@ def whole_field(n, k, wide):
             X = np.where((np.arange(n) % 2 == 0)[:, None], X, line_pts)
     X = np.ascontiguousarray(X, np.float32)
     return R.widen(X, R.wide_positions(np.random.default_rng(3))) if wide else X
+
+
+# ---- 3f. the pixel no seed wins ------------------------------------------------------------------------------------------------
+NOSEED = [(33, 17, False), (17, 17, True)]      # n, m, 128-d: two seed tiles; one full pixel tile and (n = 33) a partial one
+
+
+def noseed_rows(n):
+    """The two non-finite rows: one in a full 16-pixel tile, the last one (n = 33: in the partial tile)."""
+    return (5, n - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def noseed_case(n, m, wide):
+    """-> (X [n, 64 | 128] with rows noseed_rows(n) NaN, Z [m, 64 | 128], seed labels, num_unique = 2).  Seed s is the line
+    point p(4 s), every finite pixel a p(k) with k odd: its two neighbouring seeds are 1/64 and 3/64 away, never a tie.  Every
+    seed carries label 0 but the last, p(4 (m - 1)), which carries 1 and wins the pixels at k = 4 (m - 1) - 1 only (rows 0 and
+    9): component 0 holds the majority and the swap does nothing."""
+    assert 4 * (m - 1) <= 64 and n > 9
+    rng = np.random.default_rng(95 + n)
+    ks = 4 * rng.integers(0, m - 1, n) + rng.choice([1, 3], n)
+    ks[[0, 9]] = 4 * (m - 1) - 1
+    X = R.line(_base(9), ks)
+    Z = R.line(_base(9), 4 * np.arange(m))
+    if wide:
+        pos = R.wide_positions(np.random.default_rng(3))
+        X, Z = R.widen(X, pos), R.widen(Z, pos)
+    X[list(noseed_rows(n))] = np.nan
+    sl = np.zeros(m, np.int32)
+    sl[m - 1] = 1
+    return X, Z, sl, 2

@@ -352,3 +352,45 @@ def test_whole_call_exact(device, n, m, wide, batch):
         assert np.array_equal(Z[k].cpu().numpy(), R.planes(rows) if wide else rows), "Z, field %d" % k
         assert np.array_equal(sl[k].cpu().numpy(), ws), "seed labels, field %d" % k
         assert np.array_equal(labels[k].cpu().numpy(), wl), "labels, field %d" % k
+
+
+# ---- 3f. the pixel no seed wins ------------------------------------------------------------------------------------------------
+def confidence_all(device, X, Z, sl, nu, halves):
+    """uoc_ms_confidence with all five outputs on one field, X [n, 64] or planes [2, n, 64] -> numpy arrays."""
+    L = _native.lib()
+    Xd, Zd = to_dev(X[None], device), to_dev(Z[None], device)
+    sld, nud = to_dev(np.asarray(sl, np.int32)[None], device), to_dev(np.asarray([nu], np.int32), device)
+    n, m = X.shape[-2], Z.shape[-2]
+    labels, second, closest, rival = (torch.full((1, n), -7, dtype=torch.int32, device=device) for _ in range(4))
+    margin = torch.full((1, n), -7.0, device=device)
+    nws = L.uoc_ms_confidence_workspace_bytes(1, n, m, halves)
+    cws = torch.empty(nws, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        rc = L.uoc_ms_confidence(_native.ptr(Xd), halves, 1, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, 0,
+                                 _native.ptr(labels), _native.ptr(margin), _native.ptr(second), _native.ptr(closest),
+                                 _native.ptr(rival), _native.ptr(cws), nws, _native.stream_ptr(device))
+    _native.check(rc, "uoc_ms_confidence")
+    return [t[0].cpu().numpy() for t in (labels, margin, second, closest, rival)]
+
+
+@pytest.mark.parametrize("n,m,wide", CS.NOSEED)
+def test_pixel_no_seed_wins(device, n, m, wide):
+    """A non-finite row compares below no distance: label 0, counted under label 0, closest = INT_MAX; margin 1, second and
+    rival -1.  Every other pixel as the float64 restatement has it on the finite rows, and both calls agree on every pixel.
+    uoc_ms_assign has no 128-d form: the 128-d field goes through uoc_ms_confidence (two planes) and must reproduce what
+    uoc_ms_assign gives on the 64-d field it was widened from (widening keeps every dot product)."""
+    X, Z, sl, nu = CS.noseed_case(n, m, wide)
+    X64, Z64, _, _ = CS.noseed_case(n, m, False)
+    bad = list(CS.noseed_rows(n))
+    fin = np.setdiff1d(np.arange(n), bad)
+    (la, ca), _ = assign_raw(device, X64[None], Z64[None], sl[None], [nu])
+    lc, margin, second, cc, rival = confidence_all(device, R.planes(X) if wide else X, R.planes(Z) if wide else Z, sl, nu,
+                                                   2 if wide else 1)
+    for labels, closest in ((la[0], ca[0]), (lc, cc)):
+        assert (labels[bad] == 0).all() and (closest[bad] == 2147483647).all()
+    assert (margin[bad] == 1.0).all() and (second[bad] == -1).all() and (rival[bad] == -1).all()
+    want_labels, want_closest, _ = R.assign(X64[fin], Z64, sl, nu)
+    for labels, closest in ((la[0], ca[0]), (lc, cc)):
+        assert np.array_equal(closest[fin], want_closest) and np.array_equal(labels[fin], want_labels)
+    assert np.array_equal(lc, la[0]) and np.array_equal(cc, ca[0]), "uoc_ms_confidence differs from uoc_ms_assign"
+    assert (margin[fin] > 0).all() and (second[fin] == 1 - want_labels).all()

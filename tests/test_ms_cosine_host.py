@@ -325,3 +325,25 @@ def test_climb_wide_and_overread_cases_are_sensitive(n, m):
     # the 128-d cases climb from the seeds the whole call samples itself
     Z0 = X[R.select_seeds(X, m, CS.WIDE_FIRST)[0]] if wide else CS.hc_seeds(X, m)[0]
     assert_sensitive("n %d m %d %s" % (n, m, "128-d" if wide else "over-read"), X, Z0, 10)
+
+
+@pytest.mark.parametrize("n,m,wide", CS.NOSEED)
+def test_no_seed_case(n, m, wide):
+    """As built: two non-finite rows (one in a full pixel tile, the last one), two seed tiles, component 0 in the majority
+    even without the two rows that are counted under it, no finite pixel on a tie, and the 128-d field decides as the 64-d."""
+    X, Z, sl, nu = CS.noseed_case(n, m, wide)
+    bad = list(CS.noseed_rows(n))
+    fin = np.setdiff1d(np.arange(n), bad)
+    assert bad[0] < 16 and bad[1] == n - 1 and (n - 1) // 16 == (n + 15) // 16 - 1 and (m + 15) // 16 == 2
+    assert np.isnan(X[bad]).all() and exactly_unit(X[fin], Z) and X.shape[1] == (128 if wide else 64)
+    assert sl.tolist() == [0] * (m - 1) + [1] and nu == 2
+    labels, closest, nties = R.assign(X[fin], Z, sl, nu)
+    assert (nties == 1).all()
+    raw = sl[closest]
+    assert np.array_equal(labels, raw) and 0 < (raw == 1).sum() < (raw == 0).sum()
+    lo, co = O.assign_to_seeds(T(X[fin]), T(Z), T(sl.astype(np.int64)))
+    assert np.array_equal(closest, co.numpy()) and np.array_equal(labels, lo.numpy())
+    X64, Z64, _, _ = CS.noseed_case(n, m, False)
+    assert np.array_equal(R.assign(X64[fin], Z64, sl, nu)[1], closest)
+    D = 0.5 * (1 - X[fin].astype(np.float64) @ Z.astype(np.float64).T)      # best at 1/64, the runner-up at 3/64
+    assert (np.sort(D, axis=1)[:, :2] == np.array([1.0, 3.0]) / 64).all()

@@ -9,6 +9,7 @@
 //   mean_shift_smart_init    :211-227  -> assign_kernel          (fp32 MFMA + row argmin + histogram)
 //                                         + relabel_swap_kernel  (largest cluster <-> label 0)
 //   (no counterpart)                   -> confidence_kernel      (the assignment + the runner-up component and its margin)
+//   assign_kernel and confidence_kernel share their staging, tile load, S, guarded store and host code.
 //
 // Data layout: X is pixel-major [batch][n][64] fp32 (256 B per pixel), seeds Z [batch][m][64].
 // All reductions have a fixed order, so results are run-to-run deterministic.
@@ -1495,6 +1496,132 @@ __global__ __launch_bounds__(64) void seed_cc_kernel(const float *__restrict__ Z
 // -------------------------------------------------------------------------------------------
 // MS_EUCLIDEAN: d = sqrt(max(||x||^2 + ||z||^2 - 2 S, 0)), the square root taken before the argmin like the reference's
 // torch.norm (mean_shift.py:211-212).
+//
+// Label confidence (include/uoc_hip.h; cosine metric only) is the same scan with a wider running
+// state: per pixel also the nearest seed of ANOTHER seed component (the rival) and the margin d(p, rival) - d(p, best).
+// The two kernels are made of the same pieces (scan_stage, scan_load_tile, scan_dots, scan_store_label,
+// scan_count_label), so best / labels / the histogram are the same bits by construction; what each kernel keeps for
+// itself is its running state per pixel slot and the cross-lane merge of it.  One merged body was measured and not kept:
+// it cost assign_kernel registers and time (profiles/confidence.md).
+//   best only (assign_kernel, bd / bi): the lexicographic minimum (d, s) over the seeds seen; (INFINITY, INT_MAX) = none.
+//   ConfState (confidence_kernel): that as (d1, s1), its component c1, and the lexicographic minimum (d2, s2) over the
+//              seen seeds of a component other than c1.
+//   a seed (d, s, c) enters:  it beats (d1, s1)  -> the old best, the minimum over ALL seen seeds, is the minimum over those
+//                             outside c too: it becomes the rival if c != c1, and (d, s, c) the best;
+//                             otherwise it is a rival candidate if c != c1.
+//   two states A < B merge:   best = A's; B's seeds outside A.c1 are led by B's best if B.c1 != A.c1, else by B's rival.
+// Both are exact minima over a fixed set with index tie-breaks: the result does not depend on the merge order.
+// -------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool conf_less(float da, int sa, float db, int sb) { return da < db || (da == db && sa < sb); }
+// One cross-lane step of the best-only state (d, i): merge with the lane the DPP control names.
+template <int CTRL>
+__device__ __forceinline__ void best_min_step(float &d, int &i) {
+  const float od = dpp_f<CTRL>(d);
+  const int oi = dpp_i<CTRL>(i);
+  if (od < d || (od == d && oi < i)) {
+    d = od;
+    i = oi;
+  }
+}
+struct ConfState {
+  static constexpr bool RIVAL = true;
+  float d1 = INFINITY, d2 = INFINITY;
+  int s1 = INT_MAX, s2 = INT_MAX, c1 = -1;
+  __device__ __forceinline__ void enter(float d, int seed, int comp) {
+    if (d < d1) {  // seeds ascend: strict '<' keeps the lowest seed index
+      if (comp != c1) {
+        d2 = d1;
+        s2 = s1;
+      }
+      d1 = d;
+      s1 = seed;
+      c1 = comp;
+    } else if (comp != c1 && d < d2) {
+      d2 = d;
+      s2 = seed;
+    }
+  }
+  __device__ __forceinline__ void merge(const ConfState &o) {
+    if (conf_less(o.d1, o.s1, d1, s1)) {
+      // the other side wins: this side's seeds outside o.c1 are led by its best (c1 differs) or its rival (c1 equal)
+      const bool same = c1 == o.c1;
+      const float rd = same ? d2 : d1;
+      const int rs = same ? s2 : s1;
+      const bool take = conf_less(rd, rs, o.d2, o.s2);
+      d2 = take ? rd : o.d2;
+      s2 = take ? rs : o.s2;
+      d1 = o.d1;
+      s1 = o.s1;
+      c1 = o.c1;
+    } else {
+      const bool same = c1 == o.c1;
+      const float rd = same ? o.d2 : o.d1;
+      const int rs = same ? o.s2 : o.s1;
+      if (conf_less(rd, rs, d2, s2)) {
+        d2 = rd;
+        s2 = rs;
+      }
+    }
+  }
+  template <int CTRL>
+  __device__ __forceinline__ void min_step() {
+    ConfState o;
+    o.d1 = dpp_f<CTRL>(d1);
+    o.d2 = dpp_f<CTRL>(d2);
+    o.s1 = dpp_i<CTRL>(s1);
+    o.s2 = dpp_i<CTRL>(s2);
+    o.c1 = dpp_i<CTRL>(c1);
+    merge(o);
+  }
+};
+
+// ---- the pieces both kernels are made of (no __restrict__ here: the kernels' own parameters carry it) ----
+// Block prologue: the seeds, their labels and an empty histogram into LDS.
+template <int ST, int NH>
+__device__ __forceinline__ void scan_stage(const float *Z, const int *seed_labels, int m, int tid, float *Zs, int *slab,
+                                           int *hist) {
+  lds_stage_seeds<ST, NH>(Z, m, tid, Zs);
+  if (tid < NLAB) {
+    slab[tid] = tid < m ? seed_labels[tid] : 0;
+    hist[tid] = 0;
+  }
+  __syncthreads();
+}
+// The A fragments of a 16-pixel tile: pixel pa, channels 16 (v & 3) + 4 q .. + 3 of half v >> 2; zeros beyond n.
+template <int NH>
+__device__ __forceinline__ void scan_load_tile(const float *X, int n, int pa, int q, float4 (&xa)[NH * 4]) {
+#pragma unroll
+  for (int v = 0; v < NH * 4; ++v)
+    xa[v] = (pa < n) ? *reinterpret_cast<const float4 *>(X + ((size_t)(v >> 2) * n + pa) * C + 16 * (v & 3) + 4 * q)
+                     : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// S = X Z^T of the tile against seed tile s: S[r] is pixel 4 q + r against seed 16 s + t.
+template <int ST, int NH>
+__device__ __forceinline__ f32x4 scan_dots(const float4 (&xa)[NH * 4], int s, int t, int q) {
+  extern __shared__ __attribute__((aligned(16))) float Zs[];  // the kernel's own: [NH][ST * 16][ZP]
+  f32x4 S = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int v = 0; v < NH * 4; ++v) {
+    const float4 zb = *reinterpret_cast<const float4 *>(Zs + ((v >> 2) * ST * 16 + 16 * s + t) * ZP + 16 * (v & 3) + 4 * q);
+    S = mfma4(xa[v].x, zb.x, S);
+    S = mfma4(xa[v].y, zb.y, S);
+    S = mfma4(xa[v].z, zb.z, S);
+    S = mfma4(xa[v].w, zb.w, S);
+  }
+  return S;
+}
+// The guarded store: no seed won (a non-finite row leaves sel = INT_MAX) -> label 0, counted under label 0; a seed
+// label outside 0..127 is stored as it is and not counted.  slab[] and hist[] never see an unchecked index.
+__device__ __forceinline__ int scan_store_label(const int *slab, int *labels, int *closest, int p, int sel) {
+  const int lab = (unsigned)sel < (unsigned)NLAB ? slab[sel] : 0;
+  labels[p] = lab;
+  if (closest) closest[p] = sel;
+  return lab;
+}
+__device__ __forceinline__ void scan_count_label(int *hist, int lab) {
+  if ((unsigned)lab < (unsigned)NLAB) atomicAdd(&hist[lab], 1);
+}
+
 template <int ST, int NH, int MET>
 __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restrict__ X, int n,
                                                             const float *__restrict__ Z,
@@ -1515,12 +1642,7 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = lane & 15, q = lane >> 4;
-  lds_stage_seeds<ST, NH>(Z, m, tid, Zs);
-  if (tid < NLAB) {
-    slab[tid] = tid < m ? seed_labels[tid] : 0;
-    hist[tid] = 0;
-  }
-  __syncthreads();
+  scan_stage<ST, NH>(Z, seed_labels, m, tid, Zs, slab, hist);
   if constexpr (MET == MS_EUCLIDEAN) {
     lds_seed_norms<ST, NH>(Zs, tid, zzs);
     __syncthreads();
@@ -1528,28 +1650,15 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
 
   const int ntile = (n + 15) >> 4;
   for (int tile = blockIdx.x * (HC_THREADS / 64) + wave; tile < ntile; tile += gridDim.x * (HC_THREADS / 64)) {
-    const int pa = tile * 16 + t;
     float4 xa[NH * 4];
-#pragma unroll
-    for (int v = 0; v < NH * 4; ++v)
-      xa[v] = (pa < n) ? *reinterpret_cast<const float4 *>(X + ((size_t)(v >> 2) * n + pa) * C + 16 * (v & 3) + 4 * q)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+    scan_load_tile<NH>(X, n, tile * 16 + t, q, xa);
     float xx[4] = {};   // MS_EUCLIDEAN: ||x||^2 of pixels 4q .. 4q+3
     if constexpr (MET == MS_EUCLIDEAN) lds_pixel_norms<NH>(xa, q, xx);
     float bd[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
     int bi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
 #pragma unroll
     for (int s = 0; s < ST; ++s) {
-      f32x4 S = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int v = 0; v < NH * 4; ++v) {
-        const float4 zb =
-            *reinterpret_cast<const float4 *>(Zs + ((v >> 2) * ST * 16 + 16 * s + t) * ZP + 16 * (v & 3) + 4 * q);
-        S = mfma4(xa[v].x, zb.x, S);
-        S = mfma4(xa[v].y, zb.y, S);
-        S = mfma4(xa[v].z, zb.z, S);
-        S = mfma4(xa[v].w, zb.w, S);
-      }
+      const f32x4 S = scan_dots<ST, NH>(xa, s, t, q);
       const int seed = 16 * s + t;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1563,83 +1672,17 @@ __global__ __launch_bounds__(HC_THREADS) void assign_kernel(const float *__restr
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float d = bd[r];
-      int i = bi[r];
-#define UOC_MIN_STEP(CTRL)                                   \
-  {                                                          \
-    const float od = dpp_f<CTRL>(d);                         \
-    const int oi = dpp_i<CTRL>(i);                           \
-    if (od < d || (od == d && oi < i)) {                     \
-      d = od;                                                \
-      i = oi;                                                \
-    }                                                        \
-  }
-      UOC_MIN_STEP(0xB1) UOC_MIN_STEP(0x4E) UOC_MIN_STEP(0x141) UOC_MIN_STEP(0x140)
-#undef UOC_MIN_STEP
-      bi[r] = i;
+      best_min_step<0xB1>(bd[r], bi[r]);
+      best_min_step<0x4E>(bd[r], bi[r]);
+      best_min_step<0x141>(bd[r], bi[r]);
+      best_min_step<0x140>(bd[r], bi[r]);
     }
     const int sel = (t == 0) ? bi[0] : (t == 1) ? bi[1] : (t == 2) ? bi[2] : bi[3];
     const int p = tile * 16 + 4 * q + t;
-    if (t < 4 && p < n) {
-      const int lab = slab[sel];
-      labels[p] = lab;
-      if (closest) closest[p] = sel;
-      atomicAdd(&hist[lab], 1);
-    }
+    if (t < 4 && p < n) scan_count_label(hist, scan_store_label(slab, labels, closest, p, sel));
   }
   __syncthreads();
   if (tid < NLAB && hist[tid]) atomicAdd(&counts[tid], hist[tid]);
-}
-
-// -------------------------------------------------------------------------------------------
-// Label confidence: the assignment above plus, per pixel, the nearest seed of ANOTHER seed component (the rival) and the
-// margin d(p, rival) - d(p, best) (include/uoc_hip.h).  Cosine metric only.
-// Same staging, MFMA sequence and d = 0.5 (1 - S) as assign_kernel, so best / labels / the histogram are bit-identical
-// (for finite rows and seed labels in 0..127; see the guards at the stores).
-// Running state per pixel slot: the lexicographic minimum (d1, s1) over the seeds seen, its component c1, and the
-// lexicographic minimum (d2, s2) over the seen seeds of a component other than c1; (INFINITY, INT_MAX) = none.
-//   a seed (d, s, c) enters:  it beats (d1, s1)  -> the old best, the minimum over ALL seen seeds, is the minimum over those
-//                             outside c too: it becomes the rival if c != c1, and (d, s, c) the best;
-//                             otherwise it is a rival candidate if c != c1.
-//   two states A < B merge:   best = A's; B's seeds outside A.c1 are led by B's best if B.c1 != A.c1, else by B's rival.
-// Both are exact minima over a fixed set with index tie-breaks: the result does not depend on the merge order.
-// -------------------------------------------------------------------------------------------
-struct ConfState {
-  float d1, d2;
-  int s1, s2, c1;
-};
-__device__ __forceinline__ bool conf_less(float da, int sa, float db, int sb) { return da < db || (da == db && sa < sb); }
-__device__ __forceinline__ void conf_merge(ConfState &a, const ConfState &o) {
-  if (conf_less(o.d1, o.s1, a.d1, a.s1)) {
-    // the other side wins: this side's seeds outside o.c1 are led by its best (c1 differs) or its rival (c1 equal)
-    const bool same = a.c1 == o.c1;
-    const float rd = same ? a.d2 : a.d1;
-    const int rs = same ? a.s2 : a.s1;
-    const bool take = conf_less(rd, rs, o.d2, o.s2);
-    a.d2 = take ? rd : o.d2;
-    a.s2 = take ? rs : o.s2;
-    a.d1 = o.d1;
-    a.s1 = o.s1;
-    a.c1 = o.c1;
-  } else {
-    const bool same = a.c1 == o.c1;
-    const float rd = same ? o.d2 : o.d1;
-    const int rs = same ? o.s2 : o.s1;
-    if (conf_less(rd, rs, a.d2, a.s2)) {
-      a.d2 = rd;
-      a.s2 = rs;
-    }
-  }
-}
-template <int CTRL>
-__device__ __forceinline__ void conf_min_step(ConfState &a) {   // one UOC_MIN_STEP of assign_kernel on the wider state
-  ConfState o;
-  o.d1 = dpp_f<CTRL>(a.d1);
-  o.d2 = dpp_f<CTRL>(a.d2);
-  o.s1 = dpp_i<CTRL>(a.s1);
-  o.s2 = dpp_i<CTRL>(a.s2);
-  o.c1 = dpp_i<CTRL>(a.c1);
-  conf_merge(a, o);
 }
 
 template <int ST, int NH>
@@ -1665,64 +1708,28 @@ __global__ __launch_bounds__(HC_THREADS) void confidence_kernel(const float *__r
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int t = lane & 15, q = lane >> 4;
-  lds_stage_seeds<ST, NH>(Z, m, tid, Zs);
-  if (tid < NLAB) {
-    slab[tid] = tid < m ? seed_labels[tid] : 0;
-    hist[tid] = 0;
-  }
-  __syncthreads();
+  scan_stage<ST, NH>(Z, seed_labels, m, tid, Zs, slab, hist);
 
   const int ntile = (n + 15) >> 4;
   for (int tile = blockIdx.x * (HC_THREADS / 64) + wave; tile < ntile; tile += gridDim.x * (HC_THREADS / 64)) {
-    const int pa = tile * 16 + t;
     float4 xa[NH * 4];
-#pragma unroll
-    for (int v = 0; v < NH * 4; ++v)
-      xa[v] = (pa < n) ? *reinterpret_cast<const float4 *>(X + ((size_t)(v >> 2) * n + pa) * C + 16 * (v & 3) + 4 * q)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+    scan_load_tile<NH>(X, n, tile * 16 + t, q, xa);
     ConfState cs[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) cs[r] = ConfState{INFINITY, INFINITY, INT_MAX, INT_MAX, -1};
-#pragma unroll
     for (int s = 0; s < ST; ++s) {
-      f32x4 S = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int v = 0; v < NH * 4; ++v) {
-        const float4 zb =
-            *reinterpret_cast<const float4 *>(Zs + ((v >> 2) * ST * 16 + 16 * s + t) * ZP + 16 * (v & 3) + 4 * q);
-        S = mfma4(xa[v].x, zb.x, S);
-        S = mfma4(xa[v].y, zb.y, S);
-        S = mfma4(xa[v].z, zb.z, S);
-        S = mfma4(xa[v].w, zb.w, S);
-      }
+      const f32x4 S = scan_dots<ST, NH>(xa, s, t, q);
       const int seed = 16 * s + t;
       const int comp = slab[seed];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = 0.5f * (1.0f - S[r]);
-        ConfState &c = cs[r];
-        if (seed < m) {
-          if (d < c.d1) {  // s ascends: strict '<' keeps the lowest seed index
-            if (comp != c.c1) {
-              c.d2 = c.d1;
-              c.s2 = c.s1;
-            }
-            c.d1 = d;
-            c.s1 = seed;
-            c.c1 = comp;
-          } else if (comp != c.c1 && d < c.d2) {
-            c.d2 = d;
-            c.s2 = seed;
-          }
-        }
-      }
+      for (int r = 0; r < 4; ++r)
+        if (seed < m) cs[r].enter(0.5f * (1.0f - S[r]), seed, comp);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      conf_min_step<0xB1>(cs[r]);
-      conf_min_step<0x4E>(cs[r]);
-      conf_min_step<0x141>(cs[r]);
-      conf_min_step<0x140>(cs[r]);
+      cs[r].template min_step<0xB1>();
+      cs[r].template min_step<0x4E>();
+      cs[r].template min_step<0x141>();
+      cs[r].template min_step<0x140>();
     }
 #define UOC_CONF_PICK(F) ((t == 0) ? cs[0].F : (t == 1) ? cs[1].F : (t == 2) ? cs[2].F : cs[3].F)
     const int sel = UOC_CONF_PICK(s1), riv = UOC_CONF_PICK(s2);
@@ -1730,16 +1737,12 @@ __global__ __launch_bounds__(HC_THREADS) void confidence_kernel(const float *__r
 #undef UOC_CONF_PICK
     const int p = tile * 16 + 4 * q + t;
     if (t < 4 && p < n) {
-      // No seed won (a NaN row leaves sel = INT_MAX): label 0.  assign_kernel indexes slab[] with that value, out of bounds,
-      // and adds to hist[] unguarded; bit-identity with it is claimed for finite rows and seed labels in 0..127 only.
-      const int lab = (unsigned)sel < (unsigned)NLAB ? slab[sel] : 0;
-      const bool has = (unsigned)riv < (unsigned)NLAB;
-      labels[p] = lab;
+      const int lab = scan_store_label(slab, labels, closest, p, sel);
+      const bool has = (unsigned)riv < (unsigned)NLAB;   // a pixel no seed wins has no rival either
       margin[p] = has ? d2 - d1 : 1.0f;
       if (second) second[p] = has ? slab[riv] : -1;
-      if (closest) closest[p] = sel;
       if (rival) rival[p] = has ? riv : -1;
-      if ((unsigned)lab < (unsigned)NLAB) atomicAdd(&hist[lab], 1);
+      scan_count_label(hist, lab);
     }
   }
   __syncthreads();
@@ -2173,35 +2176,45 @@ static int run_hill_climb(const float *X, int batch, int n, float *Z, int m, flo
   return UOC_OK;
 }
 
-template <int ST, int NH, int MET>
-static void launch_assign(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m,
-                          int *labels, int *closest, const MsWorkspace &w, hipStream_t st) {
+// One launch of KERNEL = assign_kernel<ST, NH, MET> or confidence_kernel<ST, NH>: outs... are the kernel's arguments
+// between labels and counts, nout the [batch][n] arrays it writes (for the profiler's byte count).
+template <auto KERNEL, int ST, int NH, class... Outs>
+static void launch_assign(int kc, int nout, const float *X, int batch, int n, const float *Z, const int *seed_labels, int m,
+                          int *labels, int *counts, hipStream_t st, Outs... outs) {
   int nblk = hc_blocks(batch, n) * 2;
   const int maxb = ((n + 15) / 16 + 3) / 4;
   if (nblk > maxb) nblk = maxb;
   const size_t lds = (size_t)NH * ST * 16 * ZP * sizeof(float);
   static DeviceOnce attr_set;
   if (!attr_set.done() && lds > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_kernel<ST, NH, MET>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set.mark();
   }
-  ProfScope prof(KC_ASSIGN, st, 2.0 * batch * m * (double)n * C * NH, 4.0 * batch * ((double)n * C * NH + n));
-  hipLaunchKernelGGL((assign_kernel<ST, NH, MET>), dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m,
-                     labels, closest, w.counts);
+  ProfScope prof(kc, st, 2.0 * batch * m * (double)n * C * NH, 4.0 * batch * ((double)n * C * NH + (double)nout * n));
+  hipLaunchKernelGGL(KERNEL, dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m, labels, outs..., counts);
 }
 
-static int run_assign(const float *X, int batch, int n, const float *Z, const int *seed_labels,
-                      const int *num_unique, int m, int *labels, int *closest, const MsWorkspace &w,
-                      hipStream_t st, int met = MS_COSINE) {
-  UOC_HIP_CHECK(hipMemsetAsync(w.counts, 0, (size_t)batch * NLAB * sizeof(int), st));
-  dispatch_shape(met, w.nh, m, [&](auto ST, auto NH, auto MET) {
-    launch_assign<ST, NH, MET>(X, batch, n, Z, seed_labels, m, labels, closest, w, st);
+// margin != null: confidence_kernel (cosine metric only), else assign_kernel and second = rival = null.
+// The swap runs on the labels and (the same rule: -1 is neither 0 nor the largest label) on `second`.
+static int run_assign(const float *X, int nh, int batch, int n, const float *Z, const int *seed_labels,
+                      const int *num_unique, int m, int *labels, float *margin, int *second, int *closest, int *rival,
+                      int *counts, hipStream_t st, int met = MS_COSINE) {
+  UOC_REQUIRE(!margin || met == MS_COSINE, "the assignment margin is built for the cosine metric only (metric = %d)", met);
+  UOC_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)batch * NLAB * sizeof(int), st));
+  dispatch_shape(met, nh, m, [&](auto ST, auto NH, auto MET) {
+    if (!margin)
+      launch_assign<&assign_kernel<ST, NH, MET>, ST, NH>(KC_ASSIGN, 1, X, batch, n, Z, seed_labels, m, labels, counts, st,
+                                                         closest);
+    else if constexpr (MET == MS_COSINE)
+      launch_assign<&confidence_kernel<ST, NH>, ST, NH>(KC_MS_CONFIDENCE, 2 + (second ? 1 : 0) + (closest ? 1 : 0) + (rival ? 1 : 0),
+                                                        X, batch, n, Z, seed_labels, m, labels, counts, st, margin, second,
+                                                        closest, rival);
   });
   int rb = (n + 255) / 256;
   if (rb > 512) rb = 512;
-  ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n);
-  hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, labels, n, w.counts, num_unique);
+  ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n * (second ? 2 : 1));
+  hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, labels, n, counts, num_unique);
+  if (second) hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, second, n, counts, num_unique);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -2236,45 +2249,6 @@ static int run_seed_cc(const float *Z, int batch, int m, float eps, int *seed_la
 
 // ---- label confidence (uoc_ms_confidence) ----
 static size_t confidence_ws_bytes(int batch) { return align_up((size_t)batch * NLAB * sizeof(int), 256); }
-
-template <int ST, int NH>
-static void launch_confidence(const float *X, int batch, int n, const float *Z, const int *seed_labels, int m, int *labels,
-                              float *margin, int *second, int *closest, int *rival, int *counts, hipStream_t st) {
-  int nblk = hc_blocks(batch, n) * 2;     // the grid of launch_assign
-  const int maxb = ((n + 15) / 16 + 3) / 4;
-  if (nblk > maxb) nblk = maxb;
-  const size_t lds = (size_t)NH * ST * 16 * ZP * sizeof(float);
-  static DeviceOnce attr_set;
-  if (!attr_set.done() && lds > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&confidence_kernel<ST, NH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set.mark();
-  }
-  const int outs = 2 + (second ? 1 : 0) + (closest ? 1 : 0) + (rival ? 1 : 0);
-  ProfScope prof(KC_MS_CONFIDENCE, st, 2.0 * batch * m * (double)n * C * NH, 4.0 * batch * ((double)n * C * NH + (double)outs * n));
-  hipLaunchKernelGGL((confidence_kernel<ST, NH>), dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m,
-                     labels, margin, second, closest, rival, counts);
-}
-
-static int run_confidence(const float *X, int nh, int batch, int n, const float *Z, const int *seed_labels,
-                          const int *num_unique, int m, int *labels, float *margin, int *second, int *closest, int *rival,
-                          int *counts, hipStream_t st) {
-  UOC_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)batch * NLAB * sizeof(int), st));
-  dispatch<1, 2>(nh, [&](auto NH) {
-    dispatch<1, 2, 3, 4, 5, 6, 7, 8>((m + 15) / 16, [&](auto ST) {
-      launch_confidence<decltype(ST)::value, decltype(NH)::value>(X, batch, n, Z, seed_labels, m, labels, margin, second, closest, rival, counts, st);
-    });
-  });
-  int rb = (n + 255) / 256;
-  if (rb > 512) rb = 512;
-  {  // the swap of run_assign, on the labels and (the same rule: -1 is neither 0 nor the largest label) on `second`
-    ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n * (second ? 2 : 1));
-    hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, labels, n, counts, num_unique);
-    if (second) hipLaunchKernelGGL(relabel_swap_kernel, dim3(rb, batch), dim3(256), 0, st, second, n, counts, num_unique);
-  }
-  UOC_LAUNCH_CHECK();
-  return UOC_OK;
-}
 
 }  // namespace uoc
 
@@ -2392,8 +2366,8 @@ int uoc_ms_assign_ex(const float *d_X, int batch, int n, const float *d_Z, const
   UOC_REQUIRE_METRIC(metric);
   if (int rc = check_common(d_X, batch, n, m, d_ws, ws_bytes)) return rc;
   UOC_REQUIRE(d_Z && d_seed_labels && d_num_unique && d_labels, "null pointer");
-  return run_assign(d_X, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, d_closest, carve(d_ws, batch, n),
-                    (hipStream_t)stream, metric);
+  return run_assign(d_X, 1, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, nullptr, nullptr, d_closest, nullptr,
+                    carve(d_ws, batch, n).counts, (hipStream_t)stream, metric);
 }
 
 int uoc_ms_assign(const float *d_X, int batch, int n, const float *d_Z, const int32_t *d_seed_labels,
@@ -2424,7 +2398,8 @@ int uoc_ms_cluster_wide_ex(const float *d_X, int halves, int batch, int n, int m
   if (int rc = run_select_seeds(d_X, batch, n, m, d_first_index, Z, d_indices, w, st, metric)) return rc;
   if (int rc = run_hill_climb(d_X, batch, n, Z, m, kappa, iters, w, st, metric)) return rc;
   if (int rc = run_seed_cc(Z, batch, m, epsilon, sl, w.num_unique, halves, st, metric)) return rc;
-  return run_assign(d_X, batch, n, Z, sl, w.num_unique, m, d_labels, nullptr, w, st, metric);
+  return run_assign(d_X, halves, batch, n, Z, sl, w.num_unique, m, d_labels, nullptr, nullptr, nullptr, nullptr, w.counts, st,
+                    metric);
 }
 
 int uoc_ms_cluster_ex(const float *d_X, int batch, int n, int m, float kappa, int iters, float epsilon, int metric,
@@ -2494,8 +2469,8 @@ int uoc_ms_confidence(const float *d_X, int halves, int batch, int n, const floa
         UOC_REQUIRE(!a || !b || a + row <= b || b + row <= a, "uoc_ms_confidence: %s overlaps %s", out[i].name, out[j].name);
       }
   }
-  return run_confidence(d_X, halves, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, d_margin, d_second, d_closest,
-                        d_rival, (int *)d_ws, (hipStream_t)stream);
+  return run_assign(d_X, halves, batch, n, d_Z, d_seed_labels, d_num_unique, m, d_labels, d_margin, d_second, d_closest,
+                    d_rival, (int *)d_ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

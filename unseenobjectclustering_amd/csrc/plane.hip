@@ -13,10 +13,10 @@
 //   hyp_kernel          per hypothesis: three hashed candidates -> n', c0 = tau*L - n'.p0, 2*tau*L   (int64)
 //   score_kernel        per tile of 1024 candidates: 4 candidates per lane in registers against every hypothesis (read
 //                       through the scalar cache), inliers counted by ballot, one integer atomic per (block, hypothesis)
-//   select_kernel       argmax over the key ((score + 1) << 10) | (1023 - h)
+//   pselect_kernel      argmax over the key ((score + 1) << 10) | (1023 - h)
 //   plane_sum_kernel    fp64 sums of the winner's inliers per chunk
 //   plane_mom_kernel    centroid (chunk order), centred second moments per chunk
-//   plane_fit_kernel    covariance, cyclic Jacobi, normal / d / u / v, the uoc_plane record
+//   pfit_kernel         covariance, cyclic Jacobi, normal / d / u / v, the uoc_plane record
 //   obj_sum_kernel      per id: valid count, min / max height (ordered 64-bit keys), sums of the in-plane coordinates;
 //                       the height map
 //   obj_mean_kernel     foot points (chunk order)
@@ -25,11 +25,12 @@
 //   obj_extent_kernel   min / max along the major and minor axis
 //   obj_box_kernel      half extents and centre of the upright box
 //
-// uoc_support_planes repeats hyp / score / select on what the earlier planes left: pselect_kernel (the
-// argmax with the stop rule and both bands of the winner), recount_kernel / rescatter_kernel (the survivors, re-compacted
-// in raster order between two 8-byte lists), then index_kernel (the first plane whose removal band holds a pixel claims
-// it), psum_kernel / pmom_kernel / pfit_kernel (refinement per (frame, plane) over the index map, in the order of the
-// plane_* kernels), pextent_kernel, pinfo_kernel and the six object kernels with (frame, plane) as their batch.
+// uoc_support_planes is the same pipeline with (frame, plane) as the batch; uoc_support_plane is its
+// K = 1 with no stop rule and no index map.  It repeats hyp / score / pselect on what the earlier planes left (pselect's
+// stop rule and the removal band of the winner), recount_kernel / rescatter_kernel (the survivors, re-compacted in
+// raster order between two 8-byte lists), then index_kernel (the first plane whose removal band holds a pixel claims
+// it), plane_sum_kernel / plane_mom_kernel / pfit_kernel (the same refinement, its pixels taken from the index map
+// instead of the winner's band), pextent_kernel, pinfo_kernel and the six object kernels.
 //
 // Determinism: steps A and B are integer arithmetic and integer atomic adds, which commute.  Every floating-point sum
 // has a fixed order: a lane adds its own pixels in program order, a wave sums its lanes with a fixed DPP tree, a block
@@ -64,9 +65,10 @@ struct Hyp {
   long long c0;             // tau*L - n.p0
   unsigned long long thr2;  // 2*tau*L
 };
-struct Win {  // the frame's winner
+struct PWin {  // winner of (frame, round)
   int found, hyp, score, M;
-  Hyp h;
+  Hyp h;   // inlier band:  |n'.(q - p0)| <= tau * L
+  Hyp hr;  // removal band: |n'.(q - p0)| <= rem * L
 };
 
 __device__ __forceinline__ bool inlier(const Hyp &h, int qx, int qy, int qz) {
@@ -102,54 +104,6 @@ __device__ __forceinline__ Pt load_pt(const int *__restrict__ L, const float *__
     }
   }
   return q;
-}
-
-// Workspace layout (uoc_plane_workspace_bytes).  The zeroed part comes first.
-struct Ws {
-  unsigned *score;            // [B][num_hyp]            zeroed
-  int *ocnt;                  // [B][NL]                 zeroed
-  unsigned long long *okey;   // [B][NL][NKEY]           zeroed
-  int *wcnt;                  // [B][nch][WAVES]  candidates per wave, then rank bases
-  int *M;                     // [B]
-  int2 *cand;                 // [B][n]   x | y << 16, z
-  Hyp *hyp;                   // [B][num_hyp]
-  Win *win;                   // [B]
-  double *psum;               // [B][nch][3]
-  double *pmom;               // [B][nch][6]
-  double *frame;              // [B][NFR]
-  double *osum;               // [B][nch][NL][2]
-  double *omom;               // [B][nch][NL][3]
-  double *ofoot;              // [B][NL][2]
-  double *oaxis;              // [B][NL][2]
-  size_t zero_bytes, total;
-};
-Ws carve(void *base, int B, size_t n, int nch, int num_hyp) {
-  Ws w;
-  char *p = (char *)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char *r = p ? p + off : nullptr;
-    off = align_up(off + bytes, 256);
-    return r;
-  };
-  w.score = (unsigned *)take((size_t)B * num_hyp * 4);
-  w.ocnt = (int *)take((size_t)B * NL * 4);
-  w.okey = (unsigned long long *)take((size_t)B * NL * NKEY * 8);
-  w.zero_bytes = off;
-  w.wcnt = (int *)take((size_t)B * nch * WAVES * 4);
-  w.M = (int *)take((size_t)B * 4);
-  w.cand = (int2 *)take((size_t)B * n * 8);
-  w.hyp = (Hyp *)take((size_t)B * num_hyp * sizeof(Hyp));
-  w.win = (Win *)take((size_t)B * sizeof(Win));
-  w.psum = (double *)take((size_t)B * nch * 3 * 8);
-  w.pmom = (double *)take((size_t)B * nch * 6 * 8);
-  w.frame = (double *)take((size_t)B * NFR * 8);
-  w.osum = (double *)take((size_t)B * nch * NL * 2 * 8);
-  w.omom = (double *)take((size_t)B * nch * NL * 3 * 8);
-  w.ofoot = (double *)take((size_t)B * NL * 2 * 8);
-  w.oaxis = (double *)take((size_t)B * NL * 2 * 8);
-  w.total = off;
-  return w;
 }
 
 // ---- A. candidates ---------------------------------------------------------------------------------------------
@@ -310,9 +264,10 @@ __global__ __launch_bounds__(256) void score_kernel(const int2 *__restrict__ can
   }
 }
 
-__global__ __launch_bounds__(256) void select_kernel(int num_hyp, const Hyp *__restrict__ hyp,
-                                                     const unsigned *__restrict__ score, const int *__restrict__ Mv,
-                                                     Win *__restrict__ win) {
+// The winner of round r, with the stop rule (not found below min_inliers) and its removal band.
+__global__ __launch_bounds__(256) void pselect_kernel(int num_hyp, int K, int r, int tau_mm, int rem_mm, int min_inliers,
+                                                      const Hyp *__restrict__ hyp, const unsigned *__restrict__ score,
+                                                      const int *__restrict__ Mv, PWin *__restrict__ win) {
   __shared__ unsigned long long best[256];
   const int tid = threadIdx.x, b = blockIdx.x;
   unsigned long long k = 0ull;
@@ -328,13 +283,20 @@ __global__ __launch_bounds__(256) void select_kernel(int num_hyp, const Hyp *__r
   }
   if (tid == 0) {
     const unsigned long long top = best[0];
-    Win o;
+    const Hyp none{0, 0, 0, 0, -1ll, 0ull};
+    PWin o;
     o.M = Mv[b];
-    o.found = (top >> 10) != 0ull;
+    o.found = (top >> 10) != 0ull && (long long)((top >> 10) - 1ull) >= (long long)min_inliers;
     o.hyp = o.found ? 1023 - (int)(top & 1023ull) : 0;
     o.score = o.found ? (int)((top >> 10) - 1ull) : 0;
-    o.h = o.found ? hyp[(size_t)b * num_hyp + o.hyp] : Hyp{0, 0, 0, 0, -1ll, 0ull};
-    win[b] = o;
+    o.h = o.found ? hyp[(size_t)b * num_hyp + o.hyp] : none;
+    o.hr = o.h;
+    if (o.found) {
+      const long long L = (long long)(o.h.thr2 / (2ull * (unsigned long long)tau_mm));  // thr2 = 2 * tau * L exactly
+      o.hr.c0 = o.h.c0 + (long long)(rem_mm - tau_mm) * L;                               // rem * L - n'.p0
+      o.hr.thr2 = 2ull * (unsigned long long)rem_mm * (unsigned long long)L;
+    }
+    win[(size_t)b * K + r] = o;
   }
 }
 
@@ -352,29 +314,46 @@ __device__ __forceinline__ void block_sum_store(double (&acc)[N], double (*ws)[N
   if (tid < N) out[tid] = ((ws[0][tid] + ws[1][tid]) + ws[2][tid]) + ws[3][tid];
 }
 
-__global__ __launch_bounds__(256) void plane_sum_kernel(const int *__restrict__ labels, const float *__restrict__ xyz,
-                                                        int n, int nch, const Win *__restrict__ win,
+// Refinement of plane r of frame b, batch entry by = b * K + r of a (chunk, frame * K) grid.  Which pixels are summed is
+// the template parameter, everything else (per-lane, lane-tree, wave and chunk order) is written once, so plane 0 of
+// uoc_support_planes has the bits of uoc_support_plane.
+//   BY_INDEX false (K = 1, `map` = the labels): a candidate by load_pt that is an inlier of the winner's band;
+//   BY_INDEX true  (`map` = the index map):     index[p] == r.
+// A member has p < n: its coordinates are X[p], X[n + p], X[2 n + p].
+template <bool BY_INDEX>
+__device__ __forceinline__ bool member(const int *map, const float *X, int n, int p, int r, const PWin &wn) {
+  if constexpr (BY_INDEX) {
+    return p < n && map[p] == r;
+  } else {
+    const Pt q = load_pt(map, X, n, p);
+    return q.cand && inlier(wn.h, q.qx, q.qy, q.qz);
+  }
+}
+
+template <bool BY_INDEX>
+__global__ __launch_bounds__(256) void plane_sum_kernel(const int *__restrict__ map, const float *__restrict__ xyz, int n,
+                                                        int nch, int K, const PWin *__restrict__ win,
                                                         double *__restrict__ psum) {
   __shared__ double ws[WAVES][3];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = blockIdx.x, b = blockIdx.y;
-  const Win wn = win[b];
+  const int c = blockIdx.x, by = blockIdx.y, b = by / K, r = by - b * K;
+  const PWin wn = win[by];   // the <true> instantiation uses `found` only
   if (!wn.found) return;
-  const int *L = labels + (size_t)b * n;
+  const int *MP = map + (size_t)b * n;
   const float *X = xyz + (size_t)b * 3 * n;
   const int p0 = c * CHUNK + w * SUB;
   double acc[3] = {0.0, 0.0, 0.0};
   for (int it = 0; it < SUB / 64; ++it) {
     const int base = p0 + it * 64;
     if (base >= n) break;
-    const Pt q = load_pt(L, X, n, base + lane);
-    if (q.cand && inlier(wn.h, q.qx, q.qy, q.qz)) {
-      acc[0] += (double)q.x;
-      acc[1] += (double)q.y;
-      acc[2] += (double)q.z;
+    const int p = base + lane;
+    if (member<BY_INDEX>(MP, X, n, p, r, wn)) {
+      acc[0] += (double)X[p];
+      acc[1] += (double)X[(size_t)n + p];
+      acc[2] += (double)X[2 * (size_t)n + p];
     }
   }
-  block_sum_store<3>(acc, ws, psum + ((size_t)b * nch + c) * 3);
+  block_sum_store<3>(acc, ws, psum + ((size_t)by * nch + c) * 3);
 }
 
 // Sum of column k of a [nch][N] table in chunk order.
@@ -386,28 +365,29 @@ __device__ __forceinline__ double chunk_sum(const double *__restrict__ t, int nc
   return s;
 }
 
-__global__ __launch_bounds__(256) void plane_mom_kernel(const int *__restrict__ labels, const float *__restrict__ xyz,
-                                                        int n, int nch, const Win *__restrict__ win,
+template <bool BY_INDEX>
+__global__ __launch_bounds__(256) void plane_mom_kernel(const int *__restrict__ map, const float *__restrict__ xyz, int n,
+                                                        int nch, int K, const PWin *__restrict__ win,
                                                         const double *__restrict__ psum, double *__restrict__ pmom) {
   __shared__ double ws[WAVES][6];
   __shared__ double cs[3];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = blockIdx.x, b = blockIdx.y;
-  const Win wn = win[b];
+  const int c = blockIdx.x, by = blockIdx.y, b = by / K, r = by - b * K;
+  const PWin wn = win[by];   // the <true> instantiation uses `found` and `score` only
   if (!wn.found) return;
-  if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)b * nch * 3, nch, tid) / wn.score;
+  if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)by * nch * 3, nch, tid) / wn.score;
   __syncthreads();
   const double c0 = cs[0], c1 = cs[1], c2 = cs[2];
-  const int *L = labels + (size_t)b * n;
+  const int *MP = map + (size_t)b * n;
   const float *X = xyz + (size_t)b * 3 * n;
   const int p0 = c * CHUNK + w * SUB;
   double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int it = 0; it < SUB / 64; ++it) {
     const int base = p0 + it * 64;
     if (base >= n) break;
-    const Pt q = load_pt(L, X, n, base + lane);
-    if (q.cand && inlier(wn.h, q.qx, q.qy, q.qz)) {
-      const double dx = (double)q.x - c0, dy = (double)q.y - c1, dz = (double)q.z - c2;
+    const int p = base + lane;
+    if (member<BY_INDEX>(MP, X, n, p, r, wn)) {
+      const double dx = (double)X[p] - c0, dy = (double)X[(size_t)n + p] - c1, dz = (double)X[2 * (size_t)n + p] - c2;
       acc[0] += dx * dx;
       acc[1] += dx * dy;
       acc[2] += dx * dz;
@@ -416,7 +396,7 @@ __global__ __launch_bounds__(256) void plane_mom_kernel(const int *__restrict__ 
       acc[5] += dz * dz;
     }
   }
-  block_sum_store<6>(acc, ws, pmom + ((size_t)b * nch + c) * 6);
+  block_sum_store<6>(acc, ws, pmom + ((size_t)by * nch + c) * 6);
 }
 
 // The uoc_plane record and the fp64 frame F[NFR] of one plane from its centroid cs and centred moments ms (both already
@@ -472,19 +452,19 @@ __device__ __forceinline__ void fit_record(int found, int M, int score, int hyp,
   *out = o;
 }
 
-__global__ __launch_bounds__(64) void plane_fit_kernel(int nch, const Win *__restrict__ win,
-                                                       const double *__restrict__ psum, const double *__restrict__ pmom,
-                                                       uoc_plane *__restrict__ planes, double *__restrict__ frame) {
+__global__ __launch_bounds__(64) void pfit_kernel(int nch, const PWin *__restrict__ win, const double *__restrict__ psum,
+                                                  const double *__restrict__ pmom, uoc_plane *__restrict__ planes,
+                                                  double *__restrict__ frame) {
   __shared__ double cs[3], ms[6];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const Win wn = win[b];
-  if (wn.found) {
-    if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)b * nch * 3, nch, tid) / wn.score;
-    if (tid >= 8 && tid < 14) ms[tid - 8] = chunk_sum<6>(pmom + (size_t)b * nch * 6, nch, tid - 8) / wn.score;
+  const int tid = threadIdx.x, by = blockIdx.x;
+  const int found = win[by].found, score = win[by].score;
+  if (found) {
+    if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)by * nch * 3, nch, tid) / score;
+    if (tid >= 8 && tid < 14) ms[tid - 8] = chunk_sum<6>(pmom + (size_t)by * nch * 6, nch, tid - 8) / score;
   }
   __syncthreads();
   if (tid != 0) return;
-  fit_record(wn.found, wn.M, wn.score, wn.hyp, cs, ms, planes + b, frame + (size_t)b * NFR);
+  fit_record(found, win[by].M, score, win[by].hyp, cs, ms, planes + by, frame + (size_t)by * NFR);
 }
 
 // ---- D. objects against the plane ---------------------------------------------------------------------------------------
@@ -764,52 +744,10 @@ __global__ __launch_bounds__(NL) void obj_box_kernel(const double *__restrict__ 
 constexpr int MAX_PLANES = 8;
 constexpr int FRINGE = 16;  // index map: FRINGE + r marks the removal band of plane r outside its inliers
 
-struct PWin {  // winner of (frame, round)
-  int found, hyp, score, M;
-  Hyp h;   // inlier band:  |n'.(q - p0)| <= tau * L
-  Hyp hr;  // removal band: |n'.(q - p0)| <= rem * L
-};
-
 __device__ __forceinline__ void unpack_q(const int2 q, int &qx, int &qy, int &qz) {
   qx = (short)(q.x & 0xffff);
   qy = q.x >> 16;
   qz = q.y;
-}
-
-// select_kernel with the stop rule: not found below min_inliers; the winner also carries its removal band.
-__global__ __launch_bounds__(256) void pselect_kernel(int num_hyp, int K, int r, int tau_mm, int rem_mm, int min_inliers,
-                                                      const Hyp *__restrict__ hyp, const unsigned *__restrict__ score,
-                                                      const int *__restrict__ Mv, PWin *__restrict__ win) {
-  __shared__ unsigned long long best[256];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  unsigned long long k = 0ull;
-  for (int h = tid; h < num_hyp; h += 256) {
-    const unsigned long long sc1 = hyp[(size_t)b * num_hyp + h].ok ? (unsigned long long)score[(size_t)b * num_hyp + h] + 1ull : 0ull;
-    k = max(k, (sc1 << 10) | (unsigned long long)(1023 - h));
-  }
-  best[tid] = k;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) best[tid] = max(best[tid], best[tid + s]);
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const unsigned long long top = best[0];
-    const Hyp none{0, 0, 0, 0, -1ll, 0ull};
-    PWin o;
-    o.M = Mv[b];
-    o.found = (top >> 10) != 0ull && (long long)((top >> 10) - 1ull) >= (long long)min_inliers;
-    o.hyp = o.found ? 1023 - (int)(top & 1023ull) : 0;
-    o.score = o.found ? (int)((top >> 10) - 1ull) : 0;
-    o.h = o.found ? hyp[(size_t)b * num_hyp + o.hyp] : none;
-    o.hr = o.h;
-    if (o.found) {
-      const long long L = (long long)(o.h.thr2 / (2ull * (unsigned long long)tau_mm));  // thr2 = 2 * tau * L exactly
-      o.hr.c0 = o.h.c0 + (long long)(rem_mm - tau_mm) * L;                               // rem * L - n'.p0
-      o.hr.thr2 = 2ull * (unsigned long long)rem_mm * (unsigned long long)L;
-    }
-    win[(size_t)b * K + r] = o;
-  }
 }
 
 // Re-compaction of the survivors, pass 1: survivors per wave; a wave owns SUB consecutive list entries.
@@ -931,80 +869,6 @@ __global__ __launch_bounds__(256) void index_kernel(const int *__restrict__ labe
   if (tid < K && bcnt[tid]) atomicAdd(&pcnt[(size_t)b * K + tid], bcnt[tid]);
 }
 
-// Refinement sums of plane r = blockIdx.y % K over the pixels the index map gives to r as inliers: the per-lane, lane
-// tree, wave and chunk order of plane_sum_kernel / plane_mom_kernel, so plane 0 has the bits of uoc_support_plane.
-__global__ __launch_bounds__(256) void psum_kernel(const float *__restrict__ xyz, const int *__restrict__ index, int n,
-                                                   int nch, int K, const PWin *__restrict__ win,
-                                                   double *__restrict__ psum) {
-  __shared__ double ws[WAVES][3];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = blockIdx.x, by = blockIdx.y, b = by / K, r = by - b * K;
-  if (!win[by].found) return;
-  const float *X = xyz + (size_t)b * 3 * n;
-  const int *IX = index + (size_t)b * n;
-  const int p0 = c * CHUNK + w * SUB;
-  double acc[3] = {0.0, 0.0, 0.0};
-  for (int it = 0; it < SUB / 64; ++it) {
-    const int base = p0 + it * 64;
-    if (base >= n) break;
-    const int p = base + lane;
-    if (p < n && IX[p] == r) {
-      acc[0] += (double)X[p];
-      acc[1] += (double)X[(size_t)n + p];
-      acc[2] += (double)X[2 * (size_t)n + p];
-    }
-  }
-  block_sum_store<3>(acc, ws, psum + ((size_t)by * nch + c) * 3);
-}
-
-__global__ __launch_bounds__(256) void pmom_kernel(const float *__restrict__ xyz, const int *__restrict__ index, int n,
-                                                   int nch, int K, const PWin *__restrict__ win,
-                                                   const double *__restrict__ psum, double *__restrict__ pmom) {
-  __shared__ double ws[WAVES][6];
-  __shared__ double cs[3];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = blockIdx.x, by = blockIdx.y, b = by / K, r = by - b * K;
-  const int found = win[by].found, score = win[by].score;
-  if (!found) return;
-  if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)by * nch * 3, nch, tid) / score;
-  __syncthreads();
-  const double c0 = cs[0], c1 = cs[1], c2 = cs[2];
-  const float *X = xyz + (size_t)b * 3 * n;
-  const int *IX = index + (size_t)b * n;
-  const int p0 = c * CHUNK + w * SUB;
-  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int it = 0; it < SUB / 64; ++it) {
-    const int base = p0 + it * 64;
-    if (base >= n) break;
-    const int p = base + lane;
-    if (p < n && IX[p] == r) {
-      const double dx = (double)X[p] - c0, dy = (double)X[(size_t)n + p] - c1, dz = (double)X[2 * (size_t)n + p] - c2;
-      acc[0] += dx * dx;
-      acc[1] += dx * dy;
-      acc[2] += dx * dz;
-      acc[3] += dy * dy;
-      acc[4] += dy * dz;
-      acc[5] += dz * dz;
-    }
-  }
-  block_sum_store<6>(acc, ws, pmom + ((size_t)by * nch + c) * 6);
-}
-
-__global__ __launch_bounds__(64) void pfit_kernel(int nch, const PWin *__restrict__ win, const double *__restrict__ psum,
-                                                  const double *__restrict__ pmom, uoc_plane *__restrict__ planes,
-                                                  double *__restrict__ frame) {
-  __shared__ double cs[3], ms[6];
-  const int tid = threadIdx.x, by = blockIdx.x;
-  const int found = win[by].found, score = win[by].score;
-  if (found) {
-    if (tid < 3) cs[tid] = chunk_sum<3>(psum + (size_t)by * nch * 3, nch, tid) / score;
-    if (tid >= 8 && tid < 14) ms[tid - 8] = chunk_sum<6>(pmom + (size_t)by * nch * 6, nch, tid - 8) / score;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  fit_record(found, win[by].M, score, win[by].hyp, cs, ms, planes + by, frame + (size_t)by * NFR);
-}
-
 // In-plane extents of every plane's inliers through the ordered keys: max a, max -a, max b, max -b.
 __global__ __launch_bounds__(256) void pextent_kernel(const float *__restrict__ xyz, const int *__restrict__ index, int n,
                                                       int K, const double *__restrict__ frame,
@@ -1091,19 +955,25 @@ __global__ __launch_bounds__(64) void pinfo_kernel(int K, const PWin *__restrict
   info[by] = o;
 }
 
-// Workspace layout (uoc_planes_workspace_bytes).  The zeroed part comes first.
+// Workspace layout of both entry points (uoc_plane_workspace_bytes is K = 1).  The zeroed part comes first.
 struct PWs {
   unsigned *score;            // [K][B][num_hyp]         zeroed
   int *ocnt;                  // [B*K][NL]               zeroed
   unsigned long long *okey;   // [B*K][NL][NKEY]         zeroed
   int *pcnt;                  // [B*K]                   zeroed
   unsigned long long *pext;   // [B*K][4]                zeroed
-  int *wcnt;                  // [B][nch][WAVES]
-  int *M;                     // [K+1][B]
-  int2 *cand[2];              // [B][n] each: ping-pong
+  int *wcnt;                  // [B][nch][WAVES]  candidates per wave, then rank bases
+  int *M;                     // [K+1][B]; [B] if K = 1
+  int2 *cand[2];              // [B][n] each, x | y << 16, z: ping-pong; the second only if K > 1
   Hyp *hyp;                   // [B][num_hyp]
   PWin *win;                  // [B*K]
-  double *psum, *pmom, *frame, *osum, *omom, *ofoot, *oaxis;  // as Ws, with (frame, plane) as the batch
+  double *psum;               // [B*K][nch][3]
+  double *pmom;               // [B*K][nch][6]
+  double *frame;              // [B*K][NFR]
+  double *osum;               // [B*K][nch][NL][2]
+  double *omom;               // [B*K][nch][NL][3]
+  double *ofoot;              // [B*K][NL][2]
+  double *oaxis;              // [B*K][NL][2]
   size_t zero_bytes, total;
 };
 PWs pcarve(void *base, int B, size_t n, int nch, int num_hyp, int K) {
@@ -1123,9 +993,9 @@ PWs pcarve(void *base, int B, size_t n, int nch, int num_hyp, int K) {
   w.pext = (unsigned long long *)take(BK * 4 * 8);
   w.zero_bytes = off;
   w.wcnt = (int *)take((size_t)B * nch * WAVES * 4);
-  w.M = (int *)take((size_t)(K + 1) * B * 4);
+  w.M = (int *)take((size_t)(K > 1 ? K + 1 : 1) * B * 4);
   w.cand[0] = (int2 *)take((size_t)B * n * 8);
-  w.cand[1] = (int2 *)take((size_t)B * n * 8);
+  w.cand[1] = K > 1 ? (int2 *)take((size_t)B * n * 8) : nullptr;
   w.hyp = (Hyp *)take((size_t)B * num_hyp * sizeof(Hyp));
   w.win = (PWin *)take(BK * sizeof(PWin));
   w.psum = (double *)take(BK * nch * 3 * 8);
@@ -1139,6 +1009,43 @@ PWs pcarve(void *base, int B, size_t n, int nch, int num_hyp, int K) {
   return w;
 }
 
+// ---- host side: what the two entry points share; `who` is the entry point's name in the messages ----------------
+int check_shape(const char *who, int B, int max_B, int H, int W) {
+  UOC_REQUIRE(B > 0 && B <= max_B && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+  UOC_REQUIRE((long long)B * H * W <= INT_MAX, "%s: B*H*W = %lld exceeds int32 indexing", who, (long long)B * H * W);
+  return UOC_OK;
+}
+int check_hyp(const char *who, int num_hyp, int tau_mm) {
+  UOC_REQUIRE(num_hyp >= 1 && num_hyp <= MAX_HYP, "%s: num_hyp = %d outside [1, %d]", who, num_hyp, MAX_HYP);
+  UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "%s: tau_mm = %d outside [1, 1000]", who, tau_mm);
+  return UOC_OK;
+}
+
+// Zero the workspace's head and compact the candidates into w.cand[0], their count into w.M[0..B).
+int launch_candidates(int kc, const int *d_labels, const float *d_xyz, int B, int n, int nch, void *d_ws, const PWs &w,
+                      hipStream_t st) {
+  const dim3 grid(nch, B), blk(256);
+  ProfScope prof(kc, st, 0.0, (double)B * n * (2 * 16.0 + 8.0));
+  UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.zero_bytes, st));
+  hipLaunchKernelGGL(cand_count_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt);
+  hipLaunchKernelGGL(cand_scan_kernel, dim3(B), blk, 0, st, nch * WAVES, w.wcnt, w.M);
+  hipLaunchKernelGGL(cand_scatter_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt, w.cand[0]);
+  return UOC_OK;
+}
+
+// The objects of every frame against each of its K planes; the height map (K = 1 only) may be null.
+void launch_objects(int kc, const int *d_labels, const float *d_xyz, int B, int n, int nch, int K, const PWs &w,
+                    uoc_plane_object *d_objs, float *d_height, hipStream_t st) {
+  const dim3 gridk(nch, B * K), blk(256);
+  ProfScope prof(kc, st, 0.0, (double)B * n * (3 * 16.0 * K + (d_height ? 4.0 : 0.0)));
+  hipLaunchKernelGGL(obj_sum_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, nch, K, w.frame, w.ocnt, w.okey, w.osum, d_height);
+  hipLaunchKernelGGL(obj_mean_kernel, dim3(B * K), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.osum, w.ofoot);
+  hipLaunchKernelGGL(obj_mom_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, nch, K, w.frame, w.ofoot, w.omom);
+  hipLaunchKernelGGL(obj_axis_kernel, dim3(B * K), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.okey, w.ofoot, w.omom, w.oaxis, d_objs);
+  hipLaunchKernelGGL(obj_extent_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, K, w.frame, w.ofoot, w.oaxis, w.okey);
+  hipLaunchKernelGGL(obj_box_kernel, dim3(B * K), dim3(NL), 0, st, w.frame, w.ofoot, w.oaxis, w.okey, d_objs);
+}
+
 }  // namespace
 }  // namespace uoc
 
@@ -1149,55 +1056,40 @@ extern "C" {
 size_t uoc_plane_workspace_bytes(int B, int H, int W, int num_hyp) {
   if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)B * H * W > INT_MAX || num_hyp < 1 || num_hyp > MAX_HYP) return 0;
   const long long n = (long long)H * W;
-  return carve(nullptr, B, (size_t)n, (int)((n + CHUNK - 1) / CHUNK), num_hyp).total;
+  return pcarve(nullptr, B, (size_t)n, (int)((n + CHUNK - 1) / CHUNK), num_hyp, 1).total;
 }
 
 int uoc_support_plane(const int32_t *d_labels, const float *d_xyz, int B, int H, int W, int num_hyp, int tau_mm,
                       uint32_t seed, uoc_plane *d_planes, uoc_plane_object *d_objs, float *d_height, void *d_ws,
                       size_t ws_bytes, void *stream) {
   UOC_REQUIRE(d_labels && d_xyz && d_planes && d_objs && d_ws, "uoc_support_plane: null labels / xyz / planes / objects / workspace");
-  UOC_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0, "uoc_support_plane: bad shape B=%d H=%d W=%d", B, H, W);
-  UOC_REQUIRE((long long)B * H * W <= INT_MAX, "uoc_support_plane: B*H*W = %lld exceeds int32 indexing", (long long)B * H * W);
-  UOC_REQUIRE(num_hyp >= 1 && num_hyp <= MAX_HYP, "uoc_support_plane: num_hyp = %d outside [1, %d]", num_hyp, MAX_HYP);
-  UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_support_plane: tau_mm = %d outside [1, 1000]", tau_mm);
+  if (int rc = check_shape("uoc_support_plane", B, 65535, H, W)) return rc;
+  if (int rc = check_hyp("uoc_support_plane", num_hyp, tau_mm)) return rc;
   const int n = H * W;
   const int nch = (int)(((long long)n + CHUNK - 1) / CHUNK);
-  const Ws w = carve(d_ws, B, (size_t)n, nch, num_hyp);
+  const PWs w = pcarve(d_ws, B, (size_t)n, nch, num_hyp, 1);
   UOC_REQUIRE(ws_bytes >= w.total, "uoc_support_plane: workspace %zu < %zu bytes", ws_bytes, w.total);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(nch, B), blk(256);
   const double px = (double)B * n;
-  {
-    ProfScope prof(KC_PLANE_CAND, st, 0.0, px * (2 * 16.0 + 8.0));
-    UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.zero_bytes, st));
-    hipLaunchKernelGGL(cand_count_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt);
-    hipLaunchKernelGGL(cand_scan_kernel, dim3(B), blk, 0, st, nch * WAVES, w.wcnt, w.M);
-    hipLaunchKernelGGL(cand_scatter_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt, w.cand);
-  }
+  if (int rc = launch_candidates(KC_PLANE_CAND, d_labels, d_xyz, B, n, nch, d_ws, w, st)) return rc;
   {
     ProfScope prof(KC_PLANE_HYP, st, 0.0, (double)B * num_hyp * (24.0 + sizeof(Hyp)));
-    hipLaunchKernelGGL(hyp_kernel, dim3((num_hyp + 255) / 256, B), blk, 0, st, w.cand, w.M, n, num_hyp, tau_mm, seed, w.hyp);
+    hipLaunchKernelGGL(hyp_kernel, dim3((num_hyp + 255) / 256, B), blk, 0, st, w.cand[0], w.M, n, num_hyp, tau_mm, seed, w.hyp);
   }
   {
     ProfScope prof(KC_PLANE_SCORE, st, 0.0, px * 8.0);
-    hipLaunchKernelGGL(score_kernel, dim3((n + TILE - 1) / TILE, B), blk, 0, st, w.cand, w.M, n, num_hyp, w.hyp, w.score);
-    hipLaunchKernelGGL(select_kernel, dim3(B), blk, 0, st, num_hyp, w.hyp, w.score, w.M, w.win);
+    hipLaunchKernelGGL(score_kernel, dim3((n + TILE - 1) / TILE, B), blk, 0, st, w.cand[0], w.M, n, num_hyp, w.hyp, w.score);
+    // one round, no stop rule, removal band = inlier band
+    hipLaunchKernelGGL(pselect_kernel, dim3(B), blk, 0, st, num_hyp, 1, 0, tau_mm, tau_mm, 0, w.hyp, w.score, w.M, w.win);
   }
   {
     ProfScope prof(KC_PLANE_REFINE, st, 0.0, px * 2 * 16.0);
-    hipLaunchKernelGGL(plane_sum_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.win, w.psum);
-    hipLaunchKernelGGL(plane_mom_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.win, w.psum, w.pmom);
-    hipLaunchKernelGGL(plane_fit_kernel, dim3(B), dim3(64), 0, st, nch, w.win, w.psum, w.pmom, d_planes, w.frame);
+    hipLaunchKernelGGL(plane_sum_kernel<false>, grid, blk, 0, st, d_labels, d_xyz, n, nch, 1, w.win, w.psum);
+    hipLaunchKernelGGL(plane_mom_kernel<false>, grid, blk, 0, st, d_labels, d_xyz, n, nch, 1, w.win, w.psum, w.pmom);
+    hipLaunchKernelGGL(pfit_kernel, dim3(B), dim3(64), 0, st, nch, w.win, w.psum, w.pmom, d_planes, w.frame);
   }
-  {
-    ProfScope prof(KC_PLANE_OBJECTS, st, 0.0, px * (3 * 16.0 + (d_height ? 4.0 : 0.0)));
-    hipLaunchKernelGGL(obj_sum_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, 1, w.frame, w.ocnt, w.okey, w.osum, d_height);
-    hipLaunchKernelGGL(obj_mean_kernel, dim3(B), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.osum, w.ofoot);
-    hipLaunchKernelGGL(obj_mom_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, 1, w.frame, w.ofoot, w.omom);
-    hipLaunchKernelGGL(obj_axis_kernel, dim3(B), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.okey, w.ofoot, w.omom, w.oaxis, d_objs);
-    hipLaunchKernelGGL(obj_extent_kernel, grid, blk, 0, st, d_labels, d_xyz, n, 1, w.frame, w.ofoot, w.oaxis, w.okey);
-    hipLaunchKernelGGL(obj_box_kernel, dim3(B), dim3(NL), 0, st, w.frame, w.ofoot, w.oaxis, w.okey, d_objs);
-  }
+  launch_objects(KC_PLANE_OBJECTS, d_labels, d_xyz, B, n, nch, 1, w, d_objs, d_height, st);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -1216,12 +1108,10 @@ int uoc_support_planes(const int32_t *d_labels, const float *d_xyz, int B, int H
                        void *stream) {
   UOC_REQUIRE(d_labels && d_xyz && d_count && d_planes && d_info && d_index && d_ws,
               "uoc_support_planes: null labels / xyz / count / planes / info / index / workspace");
-  UOC_REQUIRE(B > 0 && H > 0 && W > 0, "uoc_support_planes: bad shape B=%d H=%d W=%d", B, H, W);
-  UOC_REQUIRE((long long)B * H * W <= INT_MAX, "uoc_support_planes: B*H*W = %lld exceeds int32 indexing", (long long)B * H * W);
+  if (int rc = check_shape("uoc_support_planes", B, INT_MAX, H, W)) return rc;
   UOC_REQUIRE(max_planes >= 1 && max_planes <= MAX_PLANES, "uoc_support_planes: max_planes = %d outside [1, %d]", max_planes, MAX_PLANES);
   UOC_REQUIRE((long long)B * max_planes <= 65535, "uoc_support_planes: B * max_planes = %lld above 65535", (long long)B * max_planes);
-  UOC_REQUIRE(num_hyp >= 1 && num_hyp <= MAX_HYP, "uoc_support_planes: num_hyp = %d outside [1, %d]", num_hyp, MAX_HYP);
-  UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_support_planes: tau_mm = %d outside [1, 1000]", tau_mm);
+  if (int rc = check_hyp("uoc_support_planes", num_hyp, tau_mm)) return rc;
   UOC_REQUIRE(rem_mm >= tau_mm && rem_mm <= 1000, "uoc_support_planes: rem_mm = %d outside [tau_mm = %d, 1000]", rem_mm, tau_mm);
   UOC_REQUIRE(min_inliers >= 3, "uoc_support_planes: min_inliers = %d below 3", min_inliers);
   const int K = max_planes, n = H * W;
@@ -1231,13 +1121,7 @@ int uoc_support_planes(const int32_t *d_labels, const float *d_xyz, int B, int H
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(nch, B), gridk(nch, B * K), blk(256);
   const double px = (double)B * n;
-  {
-    ProfScope prof(KC_PLANES_CAND, st, 0.0, px * (2 * 16.0 + 8.0));
-    UOC_HIP_CHECK(hipMemsetAsync(d_ws, 0, w.zero_bytes, st));
-    hipLaunchKernelGGL(cand_count_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt);
-    hipLaunchKernelGGL(cand_scan_kernel, dim3(B), blk, 0, st, nch * WAVES, w.wcnt, w.M);
-    hipLaunchKernelGGL(cand_scatter_kernel, grid, blk, 0, st, d_labels, d_xyz, n, nch, w.wcnt, w.cand[0]);
-  }
+  if (int rc = launch_candidates(KC_PLANES_CAND, d_labels, d_xyz, B, n, nch, d_ws, w, st)) return rc;
   {
     ProfScope prof(KC_PLANES_ROUNDS, st, 0.0, px * 8.0 * K);
     for (int r = 0; r < K; ++r) {
@@ -1259,21 +1143,13 @@ int uoc_support_planes(const int32_t *d_labels, const float *d_xyz, int B, int H
   }
   {
     ProfScope prof(KC_PLANES_REFINE, st, 0.0, px * 16.0 * (2 * K + 1));
-    hipLaunchKernelGGL(psum_kernel, gridk, blk, 0, st, d_xyz, d_index, n, nch, K, w.win, w.psum);
-    hipLaunchKernelGGL(pmom_kernel, gridk, blk, 0, st, d_xyz, d_index, n, nch, K, w.win, w.psum, w.pmom);
+    hipLaunchKernelGGL(plane_sum_kernel<true>, gridk, blk, 0, st, d_index, d_xyz, n, nch, K, w.win, w.psum);
+    hipLaunchKernelGGL(plane_mom_kernel<true>, gridk, blk, 0, st, d_index, d_xyz, n, nch, K, w.win, w.psum, w.pmom);
     hipLaunchKernelGGL(pfit_kernel, dim3(B * K), dim3(64), 0, st, nch, w.win, w.psum, w.pmom, d_planes, w.frame);
     hipLaunchKernelGGL(pextent_kernel, grid, blk, 0, st, d_xyz, d_index, n, K, w.frame, w.pext);
     hipLaunchKernelGGL(pinfo_kernel, dim3(B), dim3(64), 0, st, K, w.win, w.frame, w.pcnt, w.pext, d_info, d_count);
   }
-  if (d_objs) {
-    ProfScope prof(KC_PLANES_OBJECTS, st, 0.0, px * 3 * 16.0 * K);
-    hipLaunchKernelGGL(obj_sum_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, nch, K, w.frame, w.ocnt, w.okey, w.osum, (float *)nullptr);
-    hipLaunchKernelGGL(obj_mean_kernel, dim3(B * K), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.osum, w.ofoot);
-    hipLaunchKernelGGL(obj_mom_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, nch, K, w.frame, w.ofoot, w.omom);
-    hipLaunchKernelGGL(obj_axis_kernel, dim3(B * K), dim3(NL), 0, st, nch, w.frame, w.ocnt, w.okey, w.ofoot, w.omom, w.oaxis, d_objs);
-    hipLaunchKernelGGL(obj_extent_kernel, gridk, blk, 0, st, d_labels, d_xyz, n, K, w.frame, w.ofoot, w.oaxis, w.okey);
-    hipLaunchKernelGGL(obj_box_kernel, dim3(B * K), dim3(NL), 0, st, w.frame, w.ofoot, w.oaxis, w.okey, d_objs);
-  }
+  if (d_objs) launch_objects(KC_PLANES_OBJECTS, d_labels, d_xyz, B, n, nch, K, w, d_objs, nullptr, st);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
