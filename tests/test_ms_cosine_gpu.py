@@ -14,6 +14,7 @@ import torch
 from tests import ms_cosine_cases as CS
 from tests import ms_cosine_reference as R
 from tests.golden.cases import EPSILON, KAPPA
+from tests.ms_stage_calls import assign_raw, both_sampling_kernels, components_raw, hill_climb_raw, select_raw, to_dev
 from unseenobjectclustering_amd import _native
 from unseenobjectclustering_amd.utils import mean_shift as MS
 
@@ -21,94 +22,7 @@ pytestmark = pytest.mark.gpu
 assert KAPPA == CS.KAPPA
 
 
-def to_dev(a, device):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
-# ---- the stage entry points ------------------------------------------------------------------------------------------
-def hill_climb_raw(X, Z0, iters, n=None):
-    """uoc_ms_hill_climb on device tensors X [B, >= n, 64] (n rows are read), Z0 [B, m, 64] -> the new seeds."""
-    L = _native.lib()
-    batch, m = X.shape[0], Z0.shape[1]
-    n = X.shape[1] if n is None else n
-    assert batch == 1 or n == X.shape[1]
-    ws = MS._workspace(X.device, L.uoc_ms_workspace_bytes(batch, n, m))
-    Z = Z0.clone()
-    with torch.cuda.device(X.device):
-        rc = L.uoc_ms_hill_climb(_native.ptr(X), batch, n, _native.ptr(Z), m, KAPPA, iters, _native.ptr(ws), ws.numel(),
-                                 _native.stream_ptr(X.device))
-    _native.check(rc, "uoc_ms_hill_climb")
-    torch.cuda.synchronize(X.device)
-    return Z
-
-
-def select_raw(device, X, m, first=None, init=None, num_init=0):
-    """uoc_ms_select_seeds (no init) / uoc_ms_select_seeds_from on X [B, n, 64] -> (indices [B, m], seeds [B, m, 64]) numpy."""
-    L = _native.lib()
-    Xd = to_dev(X, device)
-    B, n = X.shape[0], X.shape[1]
-    seeds = torch.full((B, m, 64), 9.0, device=device) if init is None else to_dev(init, device)
-    idx = torch.full((B, m), -7, dtype=torch.int32, device=device)
-    firstd = None if first is None else torch.tensor(first, dtype=torch.int32, device=device)
-    ws = MS._workspace(device, L.uoc_ms_workspace_bytes(B, n, m))
-    with torch.cuda.device(device):
-        if init is None:
-            rc = L.uoc_ms_select_seeds(_native.ptr(Xd), B, n, m, _native.ptr(firstd), _native.ptr(seeds), _native.ptr(idx),
-                                       _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
-        else:
-            rc = L.uoc_ms_select_seeds_from(_native.ptr(Xd), B, n, m, num_init, _native.ptr(firstd), _native.ptr(seeds),
-                                            _native.ptr(idx), _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_select_seeds")
-        _native.check(L.uoc_ms_check(_native.stream_ptr(device)), "uoc_ms_check")
-    return idx.cpu().numpy(), seeds.cpu().numpy()
-
-
-def both_sampling_kernels(fn):
-    """fn() with the on-chip persistent kernel, then with the one-launch-per-step kernel; the setting is restored."""
-    L = _native.lib()
-    try:
-        for on in (1, 0):
-            L.uoc_ms_set_persistent_fps(on)
-            fn("on-chip" if on else "streaming")
-    finally:
-        L.uoc_ms_set_persistent_fps(1)
-
-
-def components_raw(device, Z, eps):
-    """uoc_ms_seed_components on Z [B, m, 64] -> (labels [B, m], num_unique [B]) numpy."""
-    L = _native.lib()
-    Zd = to_dev(Z, device)
-    B, m = Z.shape[0], Z.shape[1]
-    out = torch.full((B, m), -7, dtype=torch.int32, device=device)
-    nu = torch.full((B,), -7, dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_seed_components(_native.ptr(Zd), B, m, float(eps), _native.ptr(out), _native.ptr(nu), _native.stream_ptr(device))
-    _native.check(rc, "uoc_ms_seed_components")
-    return out.cpu().numpy(), nu.cpu().numpy()
-
-
-def assign_raw(device, X, Z, sl, nu):
-    """uoc_ms_assign and uoc_ms_confidence on X [B, n, 64], Z [B, m, 64], seed labels [B, m], num_unique [B]
-    -> ((labels, closest) of the assignment, (labels, closest) of the confidence call), numpy [B, n]."""
-    L = _native.lib()
-    Xd, Zd = to_dev(X, device), to_dev(Z, device)
-    sld, nud = to_dev(np.asarray(sl, np.int32), device), to_dev(np.asarray(nu, np.int32), device)
-    B, n, m = X.shape[0], X.shape[1], Z.shape[1]
-    la, ca, lc, cc = (torch.full((B, n), -7, dtype=torch.int32, device=device) for _ in range(4))
-    margin = torch.empty((B, n), device=device)
-    ws = MS._workspace(device, L.uoc_ms_workspace_bytes(B, n, m))
-    nws = L.uoc_ms_confidence_workspace_bytes(B, n, m, 1)
-    cws = torch.empty(nws, dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_assign(_native.ptr(Xd), B, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, _native.ptr(la),
-                             _native.ptr(ca), _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_assign")
-        rc = L.uoc_ms_confidence(_native.ptr(Xd), 1, B, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, 0, _native.ptr(lc),
-                                 _native.ptr(margin), None, _native.ptr(cc), None, _native.ptr(cws), nws, _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_confidence")
-    return (la.cpu().numpy(), ca.cpu().numpy()), (lc.cpu().numpy(), cc.cpu().numpy())
-
-
+# ---- the stage entry points (tests/ms_stage_calls.py; the metric defaults to cosine) ---------------------------------------
 # ---- 3a. hill climbing against float64 ---------------------------------------------------------------------------------
 def climb_rows(what, got, fields, seeds, iters, check=None):
     """Per checked field: (name, kernel deviation from float64, the oracle's, the tile order's, the tolerance)."""
