@@ -53,8 +53,9 @@ def boundary_overlap(predicted_mask, gt_mask, bound_th=0.003):
     return np.sum(np.logical_and(fg_boundary, gt_dil)), np.sum(np.logical_and(gt_boundary, fg_dil))
 
 
-def pair_tables(prediction, gt):
-    """The integer tables the HIP kernels produce (uoc_eval_pair_stats), by brute force over label pairs."""
+def pair_tables(prediction, gt, bound_th=0.003):
+    """The integer tables the HIP kernels produce (uoc_eval_pair_stats), by brute force over label pairs; bound_th as in
+    boundary_overlap (a fraction of the diagonal below 1, else pixels)."""
     prediction, gt = np.asarray(prediction).astype(np.int64), np.asarray(gt).astype(np.int64)
     cont = np.zeros((128, 128), np.int64)
     np.add.at(cont, (gt.reshape(-1), prediction.reshape(-1)), 1)
@@ -69,5 +70,5 @@ def pair_tables(prediction, gt):
     for i in lg:
         bnd_gt[i] = seg2bmap(gt == i).sum()
         for j in lp:
-            prec_tp[i, j], rec_tp[i, j] = boundary_overlap(prediction == j, gt == i)
+            prec_tp[i, j], rec_tp[i, j] = boundary_overlap(prediction == j, gt == i, bound_th)
     return dict(cont=cont, prec_tp=prec_tp, rec_tp=rec_tp, bnd_pred=bnd_pred, bnd_gt=bnd_gt)

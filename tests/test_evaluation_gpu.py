@@ -8,6 +8,8 @@ import pytest
 import torch
 
 from oracle import evaluation_oracle as EO
+from tests import evaluation_cases as EC
+from tests import evaluation_reference as ER
 from tests.golden.cases import EVAL_CASES, eval_pair
 from unseenobjectclustering_amd import synth
 from unseenobjectclustering_amd.fcn import test_dataset as TD
@@ -24,6 +26,17 @@ def test_tables_match_oracle(device, name):
     want = EO.pair_tables(pred, gt)
     for k in ("cont", "bnd_pred", "bnd_gt", "prec_tp", "rec_tp"):
         assert np.array_equal(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("name", list(EC.CASES))
+def test_engineered_cases_match_reference(device, name):
+    """tests/evaluation_cases.py (what each case contains: tests/test_evaluation_cases_host.py): labels from 64 up, four
+    labels in one 2x2 neighbourhood, radii 0..32, maps of one row / column / pixel, one table cell hit by every pixel."""
+    pred, gt, bound_th = EC.CASES[name]()
+    want = ER.pair_tables(pred, gt, ER.radius_of(pred.shape, bound_th))
+    got = EV.pair_stats(torch.from_numpy(pred).to(device), torch.from_numpy(gt).to(device), bound_th=bound_th)
+    for k in ("cont", "bnd_pred", "bnd_gt", "prec_tp", "rec_tp"):
+        assert got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), k
 
 
 @pytest.mark.parametrize("name", list(EVAL_CASES))

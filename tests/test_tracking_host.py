@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import tracking_cases as TC
+from tests.tracking_cases import line
 from tests.tracking_reference import ReferenceTracker, iou_threshold, object_ids
 from unseenobjectclustering_amd import _native, tracking
 
@@ -97,32 +99,30 @@ def test_occlusion_up_to_max_age_keeps_the_uid_and_one_more_frame_loses_it(max_a
     assert tr.events["retire"] == 1 and tr.events["reuse"] == 1 and tr.events["birth"] == 1
 
 
-def line(n, *spans):
-    img = np.zeros((1, n), dtype=np.int32)
-    for a, b, v in spans:
-        img[0, a:b] = v
-    return img
+def begin(c):
+    """A fresh reference tracker with the case's parameters, and the case's frames (tests/tracking_cases.py)."""
+    return ReferenceTracker(min_iou=c["min_iou"], max_age=c["max_age"]), c["frames"]
 
 
 def test_exact_iou_ties_go_to_larger_intersection_then_lower_track_then_lower_id():
     # larger intersection: track 1 has 6 pixels; id 5 (2 px, all inside: 2/6) and id 9 (10 px, 4 inside: 4/12) tie at 1/3
-    tr = ReferenceTracker(min_iou=0.3)
-    tr.step(line(40, (10, 16, 1)))
-    out = tr.step(line(40, (10, 12, 5), (12, 22, 9)))
+    tr, frames = begin(TC.tie_larger_inter())
+    tr.step(frames[0])
+    out = tr.step(frames[1])
     assert tr.lut[9] == 1 and tr.lut[5] == 2
     assert tr.table[1].tolist() == [1, 0, 2, 10, 0] and tr.table[2].tolist() == [2, 0, 1, 2, 1]
     assert np.array_equal(out, line(40, (10, 12, 2), (12, 22, 1)))
     # lower track: tracks 1 and 2 (4 px each) against one id covering the inner halves of both (2/6 each, equal inter)
-    tr = ReferenceTracker(min_iou=0.3)
-    tr.step(line(40, (10, 14, 3), (14, 18, 8)))
+    tr, frames = begin(TC.tie_lower_track())
+    tr.step(frames[0])
     assert live(tr) == {1: 1, 2: 2}
-    out = tr.step(line(40, (12, 16, 6)))
+    out = tr.step(frames[1])
     assert tr.lut[6] == 1 and tr.table[1].tolist() == [1, 0, 2, 4, 0] and tr.table[2].tolist() == [2, 1, 1, 4, 0]
     assert np.array_equal(tr.mem, line(40, (12, 16, 1), (16, 18, 2)))      # track 2 keeps what was not covered
     # lower id: one track (8 px) against ids 4 and 7, each 2 px inside plus 2 outside (2/10 each)
-    tr = ReferenceTracker(min_iou=0.2)
-    tr.step(line(40, (10, 18, 1)))
-    out = tr.step(line(40, (8, 12, 7), (16, 20, 4)))
+    tr, frames = begin(TC.tie_lower_id())
+    tr.step(frames[0])
+    out = tr.step(frames[1])
     assert tr.lut[4] == 1 and tr.lut[7] == 2
     assert np.array_equal(out, line(40, (8, 12, 2), (16, 20, 1)))
     assert np.array_equal(tr.mem, out)                                      # a matched track's stale pixels vanish
@@ -131,23 +131,25 @@ def test_exact_iou_ties_go_to_larger_intersection_then_lower_track_then_lower_id
 def test_threshold_is_inclusive_and_exact():
     q = iou_threshold(0.3)
     assert q == 19661
-    n = 70000
     # the id covers 65536 pixels, the track's pixels all lie inside: IoU = area_track / 65536
-    for area, matched in ((q, True), (q - 1, False)):
-        tr = ReferenceTracker(min_iou=0.3)
-        tr.step(line(n, (0, area, 1)))
-        tr.step(line(n, (0, 65536, 1)))
+    for area, matched, c in ((q, True, TC.threshold_equal_large()), (q - 1, False, TC.threshold_equal_large_miss())):
+        tr, frames = begin(c)
+        assert tr.q == q and frames.shape == (2, 1, 70000) and (frames[0] == 1).sum() == area and (frames[1] == 1).sum() == 65536
+        tr.step(frames[0])
+        tr.step(frames[1])
         assert (tr.table[1, 0] == 1 and tr.table[1, 2] == 2) == matched
         assert (tr.table[2, 0] == 2) == (not matched)
     # one half exactly, and just under it
     for inter, matched in ((2, True),):
-        tr = ReferenceTracker(min_iou=0.5)
-        tr.step(line(16, (0, 3, 1)))
-        tr.step(line(16, (1, 4, 1)))                                           # inter 2, union 4
+        tr, frames = begin(TC.threshold_half_line())
+        assert tr.q == 32768
+        tr.step(frames[0])
+        tr.step(frames[1])                                                     # inter 2, union 4
         assert (tr.meta()["next_uid"] == 2) == matched
-    tr = ReferenceTracker(min_iou=0.5)
-    tr.step(line(300, (0, 100, 1)))
-    tr.step(line(300, (34, 134, 1)))                                           # inter 66, union 134
+    tr, frames = begin(TC.threshold_below_half())
+    assert tr.q == 32768
+    tr.step(frames[0])
+    tr.step(frames[1])                                                         # inter 66, union 134
     assert tr.meta()["next_uid"] == 3 and live(tr) == {1: 1, 2: 2} and tr.table[1, 1] == 1
 
 
@@ -161,14 +163,11 @@ def test_values_outside_1_to_127_are_background():
 
 
 def test_a_128th_object_is_dropped():
+    tr, frames = begin(TC.overflow_128th())                                    # raw id 127 shows up somewhere else
+
     def frame(moved):
-        img = np.zeros((4, 128), dtype=np.int32)
-        img[0, 1:128] = np.arange(1, 128)
-        if moved:
-            img[0, 127] = 0
-            img[2, 5] = 127                                                    # raw id 127 shows up somewhere else
-        return img
-    tr = ReferenceTracker(max_age=2)
+        return frames[1 if moved else 0]
+    assert tr.max_age == 2 and np.array_equal(frames[2], frames[1]) and np.array_equal(frames[3], frames[1])
     out = tr.step(frame(False))
     assert np.array_equal(out, frame(False)) and len(live(tr)) == 127 and tr.dropped == 0
     out = tr.step(frame(True))

@@ -36,6 +36,21 @@ class ReferenceTracker:
         self.used = np.zeros(NUM, dtype=bool)
         self.events = dict(match=0, birth=0, retire=0, recover=0, reuse=0)
 
+    # The decision rules, one method each, so that tests/tracking_cases.py can break one at a time (its mutants).
+    def passes(self, inter, union):
+        """The candidate test: inclusive, exact."""
+        return inter * 65536 >= self.q * union
+
+    def prefers(self, a, b):
+        """Candidate a = (inter, union, t, c) goes before b: larger IoU, larger inter, lower t, lower c."""
+        (inter, union, t, c), (bi, bu, bt, bc) = a, b
+        lhs, rhs = inter * bu, bi * union               # Python ints: exact
+        return lhs > rhs or (lhs == rhs and (inter > bi or (inter == bi and (t, c) < (bt, bc))))
+
+    def free_slots(self, retired):
+        """The free slots in the order births take them; `retired` = the slots retired in this very step."""
+        return [s for s in range(1, NUM) if self.table[s, 0] == 0]
+
     def step(self, labels):
         cur = object_ids(labels)
         if self.mem is None or self.mem.shape != cur.shape:
@@ -54,7 +69,7 @@ class ReferenceTracker:
                 continue
             inter = int(cont[t, c])
             union = int(area_mem[t]) + int(area_cur[c]) - inter
-            if inter * 65536 >= self.q * union:
+            if self.passes(inter, union):
                 cands.append((inter, union, t, c))
         # 3. greedy matching on exact rationals
         match_t, match_c = {}, {}
@@ -64,12 +79,7 @@ class ReferenceTracker:
                 inter, union, t, c = cand
                 if t in match_t or c in match_c:
                     continue
-                if best is None:
-                    best = cand
-                    continue
-                bi, bu, bt, bc = best
-                lhs, rhs = inter * bu, bi * union           # Python ints: exact
-                if lhs > rhs or (lhs == rhs and (inter > bi or (inter == bi and (t, c) < (bt, bc)))):
+                if best is None or self.prefers(cand, best):
                     best = cand
             if best is None:
                 break
@@ -78,6 +88,7 @@ class ReferenceTracker:
         # 4. ageing
         lut = np.zeros(NUM, dtype=np.int64)
         keep = np.zeros(NUM, dtype=bool)
+        retired = set()
         for t in range(1, NUM):
             if not live_before[t]:
                 continue
@@ -94,6 +105,7 @@ class ReferenceTracker:
                 table[t, 1] += 1
                 if table[t, 1] > self.max_age:
                     table[t] = 0
+                    retired.add(t)
                     self.events["retire"] += 1
                 else:
                     keep[t] = True
@@ -101,7 +113,7 @@ class ReferenceTracker:
         for c in range(1, NUM):
             if area_cur[c] == 0 or c in match_c:
                 continue
-            free = [s for s in range(1, NUM) if table[s, 0] == 0]
+            free = self.free_slots(retired)
             if not free:
                 self.dropped += 1
                 continue
