@@ -344,7 +344,7 @@ typedef struct uoc_object {
   float cov[6];           /* population covariance (1/n) sum (p-c)(p-c)^T: xx, xy, xz, yy, yz, zz               */
   float aabb_min[3];
   float aabb_max[3];
-  float eig[3];           /* eigenvalues of cov, descending                                                      */
+  float eig[3];           /* eigenvalues of cov, descending, never negative (clamped at 0)                       */
   float axes[9];          /* row-major 3x3, column k = unit eigenvector e_k; e0, e1 have their largest-magnitude
                              component positive (ties: lowest index), e2 = e0 x e1                                 */
   float obb_center[3];    /* c + sum_k e_k (min d_k + max d_k) / 2,  d_k = (p - c) . e_k over the valid points     */
@@ -471,7 +471,7 @@ typedef struct uoc_plane {
   float normal[3];     /* refined unit normal                                                                    */
   float d;             /* refined offset: normal.p + d = 0                                                       */
   float centroid[3];   /* centroid c of the inliers                                                              */
-  float eig[3];        /* eigenvalues of the inliers' covariance, descending                                     */
+  float eig[3];        /* eigenvalues of the inliers' covariance, descending, never negative (clamped at 0)      */
   float rms;           /* sqrt(eig[2]): rms distance of the inliers from the plane                               */
   float u[3];          /* in-plane axes                                                                          */
   float v[3];

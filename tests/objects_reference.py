@@ -24,18 +24,19 @@ def eig_frame(cov):
     """(eigenvalues descending, axes [3,3] with column k = e_k) under the sign rule and e2 = e0 x e1."""
     w, v = np.linalg.eigh(cov)
     order = np.argsort(-w, kind="stable")
-    w, v = w[order], v[:, order]
+    w, v = np.maximum(w[order], 0.0), v[:, order]      # eigenvalues of a covariance: never negative (include/uoc_hip.h)
     e0, e1 = sign_rule(v[:, 0]), sign_rule(v[:, 1])
     return w, np.stack([e0, e1, np.cross(e0, e1)], axis=1)
 
 
 def object_record(pts):
-    """Float statistics of one object's valid points [n,3] (float64 in, float64 out)."""
+    """Float statistics of one object's valid points [n,3] (float64 in, float64 out); `points` keeps the input for the
+    gap-independent checker (tests/stats_cases.py)."""
     n = len(pts)
     z3 = np.zeros(3)
     if n == 0:
         return dict(centroid=z3, cov=np.zeros((3, 3)), aabb_min=z3, aabb_max=z3, eig=z3, axes=np.zeros((3, 3)),
-                    obb_center=z3, obb_half=z3)
+                    obb_center=z3, obb_half=z3, points=np.zeros((0, 3)))
     p = pts.astype(np.float64)
     c = p.mean(axis=0)
     d = p - c
@@ -44,7 +45,7 @@ def object_record(pts):
     proj = d @ ax
     lo, hi = proj.min(axis=0), proj.max(axis=0)
     return dict(centroid=c, cov=cov, aabb_min=p.min(axis=0), aabb_max=p.max(axis=0), eig=w, axes=ax,
-                obb_center=c + ax @ ((lo + hi) / 2), obb_half=(hi - lo) / 2)
+                obb_center=c + ax @ ((lo + hi) / 2), obb_half=(hi - lo) / 2, points=p)
 
 
 def extract(labels, xyz, attrs=None, max_points_per_object=None):

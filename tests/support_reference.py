@@ -84,10 +84,13 @@ def sign_rule(e):
 
 
 def refine(pts):
-    """pts [n,3] float64 -> dict normal, d, centroid, eig (descending), u, v."""
+    """pts [n,3] float64 -> dict normal, d, centroid, eig (descending, never negative), u, v; `points` and `cov` keep the
+    input and its fp64 covariance for the gap-independent checker (tests/stats_cases.py)."""
     c = pts.mean(axis=0)
     dd = pts - c
-    w, vec = np.linalg.eigh(dd.T @ dd / len(pts))
+    cov = dd.T @ dd / len(pts)
+    w, vec = np.linalg.eigh(cov)
+    w = np.maximum(w, 0.0)
     normal = vec[:, 0]
     d = -float(normal @ c)
     if d < 0:
@@ -101,11 +104,11 @@ def refine(pts):
         if np.linalg.norm(u) >= 1e-6:
             break
     u = u / np.linalg.norm(u)
-    return dict(normal=normal, d=d, centroid=c, eig=w[::-1].copy(), u=u, v=np.cross(normal, u))
+    return dict(normal=normal, d=d, centroid=c, eig=w[::-1].copy(), u=u, v=np.cross(normal, u), points=pts, cov=cov)
 
 
 def object_record(pts, pl):
-    """Valid points [n,3] float64 of one id against the refined plane."""
+    """Valid points [n,3] float64 of one id against the refined plane (`points` keeps them for the checker)."""
     t = pts @ pl["normal"] + pl["d"]
     ab = np.stack([(pts - pl["centroid"]) @ pl["u"], (pts - pl["centroid"]) @ pl["v"]], axis=1)
     foot = ab.mean(axis=0)
@@ -124,13 +127,13 @@ def object_record(pts, pl):
     m_ab = foot + mid[0] * e + mid[1] * ep
     center = pl["centroid"] + m_ab[0] * pl["u"] + m_ab[1] * pl["v"] + mid[2] * pl["normal"]
     return dict(count=len(pts), height_min=t.min(), height_max=t.max(), foot=foot, cov2=np.array([cov[0, 0], cov[0, 1], cov[1, 1]]),
-                axis=e, half=(hi - lo) / 2, center=center, lam0=float(w[1]), gap=gap)
+                axis=e, half=(hi - lo) / 2, center=center, lam0=float(w[1]), gap=gap, points=pts)
 
 
 def fit(labels, xyz, num_hyp, tau_mm, seed, height_map=False):
     """One frame: labels [H,W] ints, xyz [3,H,W] float32.  Returns dict(plane=..., objects={id: record}, height=[H,W]
     float64 with NaN or None, scores=int64 [num_hyp]); plane has found, candidates, inliers, hyp and, when found, the
-    float fields as float64."""
+    float fields as float64; xyz = the input as [3, H*W] float32."""
     lab = np.asarray(labels).astype(np.int64)
     H, W = lab.shape
     X = np.asarray(xyz, np.float32).reshape(3, -1)
@@ -153,7 +156,7 @@ def fit(labels, xyz, num_hyp, tau_mm, seed, height_map=False):
             sel = np.nonzero((flat == l) & valid)[0]
             if len(sel):
                 objects[l] = object_record(X[:, sel].T.astype(np.float64), plane)
-    return dict(plane=plane, objects=objects, height=None if height is None else height.reshape(H, W), scores=sc)
+    return dict(plane=plane, objects=objects, height=None if height is None else height.reshape(H, W), scores=sc, xyz=X)
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,10 @@
 
 The rounds are exact integers: count, found, candidates, inliers, hyp, round_candidates, removed, the object counts and
 the whole index map are compared with np.array_equal.  Refinement and objects are fp64 sums stored in fp32: every plane
-slot goes through tests/test_support_gpu.py's check_frame (its tolerances, under its eigen-gap condition); cos0 and
+slot goes through tests/test_support_gpu.py's check_frame (its tolerances, under its eigen-gap condition, and, without
+exemption, the gap-independent checker of tests/stats_cases.py on every found plane and every object with a point, and
+the comparison of the step C and D sums with the reference within half an ulp plus derived terms; the sign rule alone is
+judged only where the float32 record decides it, see tests/test_support_gpu.py); cos0 and
 offset0 within 2e-6 and extent within 1e-5 where the planes involved meet the gap condition.  Round 0 is compared bit for
 bit with support.fit_plane.
 

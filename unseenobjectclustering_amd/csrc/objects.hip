@@ -370,7 +370,7 @@ __global__ __launch_bounds__(NUM_IDS) void moments_kernel(int B, int H, int W, i
       o.axes[i * 3 + 0] = (float)e0[i];
       o.axes[i * 3 + 1] = (float)e1[i];
       o.axes[i * 3 + 2] = (float)e2[i];
-      o.eig[i] = (float)lam[i];
+      o.eig[i] = (float)fmax(lam[i], 0.0);  // eigenvalues of a covariance: a rank-deficient one can leave -1e-20
       o.centroid[i] = (float)C[i];
       o.aabb_max[i] = fdecode(S[ST_MAX + i]);
       o.aabb_min[i] = fdecode(~S[ST_MIN + i]);

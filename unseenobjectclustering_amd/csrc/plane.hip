@@ -440,7 +440,7 @@ __device__ __forceinline__ void fit_record(int found, int M, int score, int hyp,
       F[FR_V + k] = vv[k];
       o.normal[k] = (float)nn[k];
       o.centroid[k] = (float)cs[k];
-      o.eig[k] = (float)lam[k];
+      o.eig[k] = (float)fmax(lam[k], 0.0);  // as rms below: a rank-deficient covariance can leave -1e-20
       o.u[k] = (float)u[k];
       o.v[k] = (float)vv[k];
     }
