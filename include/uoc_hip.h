@@ -394,6 +394,10 @@ typedef struct uoc_track {
   int32_t area;   /* pixels at the last match                                                           */
   int32_t born;   /* step index of the birth                                                            */
 } uoc_track;
+#define UOC_TRACK_SLOTS 128            /* slot 0 is never a track */
+#define UOC_TRACK_HEADER_WORDS 1024    /* int32 words of a stream's state before its contingency scratch */
+#define UOC_TRACK_META_WORD 640        /* words 640, 641, 642 = uids handed out, step, dropped */
+#define UOC_TRACK_CONT_WORDS (128 * 128)
 
 size_t uoc_track_state_bytes(int B, int H, int W);
 size_t uoc_track_workspace_bytes(int B);
@@ -488,6 +492,8 @@ typedef struct uoc_plane_object {
   float half[3];       /* half extents (max - min) / 2 of r.e, r.e' and t, r = (a, b) - foot, e' = (-e[1], e[0])  */
   float center[3];     /* upright box centre: c + (foot + m0 e + m1 e') in (u, v) + m2 normal, m = (max + min) / 2 */
 } uoc_plane_object;
+#define UOC_PLANE_MAX_HYP 1024      /* num_hyp in 1..1024 */
+#define UOC_PLANE_MAX_TAU_MM 1000   /* tau_mm (and rem_mm) in 1..1000 */
 
 /* 0 for a bad shape or num_hyp outside 1..1024. */
 size_t uoc_plane_workspace_bytes(int B, int H, int W, int num_hyp);
@@ -534,6 +540,8 @@ typedef struct uoc_plane_info {
   float offset0;             /* normal_0 . centroid_r + d_0: signed distance of plane r's centroid from plane 0  */
   float extent[4];           /* min a, max a, min b, max b of I_r, (a, b) = ((p - c_r).u_r, (p - c_r).v_r), fp64 */
 } uoc_plane_info;
+#define UOC_PLANES_MAX 8            /* max_planes in 1..8 */
+#define UOC_PLANES_FRINGE 16        /* d_index: 16 + r marks the removal band of plane r outside its inliers */
 
 /* 0 for a bad shape, num_hyp outside 1..1024, max_planes outside 1..8 or B * max_planes above 65535. */
 size_t uoc_planes_workspace_bytes(int B, int H, int W, int num_hyp, int max_planes);
@@ -574,6 +582,7 @@ int uoc_support_planes(const int32_t *d_labels, const float *d_xyz, int B, int H
 #define UOC_REL_BORDER 0
 #define UOC_REL_TOUCH 1
 #define UOC_REL_FRONT 2
+#define UOC_REL_MAX_GAP_MM 65535   /* gap_mm in 1..65535 */
 
 typedef struct uoc_relation_object {   /* one per (frame, id); all zero for id 0 and for an absent id */
   int32_t pixels;     /* pixels with the id                                                                      */
@@ -633,6 +642,11 @@ int uoc_relations(const int32_t *d_labels, const float *d_xyz, int B, int H, int
 #define UOC_PLACE_MAX_QUERIES 16
 #define UOC_PLACE_WIDEST 0
 #define UOC_PLACE_NEAREST 1
+#define UOC_PLACE_MAX_GRID 512      /* G: a multiple of 8 in 8..512 (every table-grid call) */
+#define UOC_PLACE_MAX_MM 1000       /* cell_mm, tau_mm in 1..1000, h_obs_mm in 0..1000 */
+#define UOC_PLACE_MAX_MIN_PTS 65535
+#define UOC_PLACE_MAX_ANCHOR 4096   /* a query's anchor cell lies in -4096..4095 */
+#define UOC_PLACE_SCALE 16384       /* S of the integer frame */
 
 /* 0 for a bad shape (B outside 1..65535, H*W not below 2^31) or a bad G. */
 size_t uoc_placement_workspace_bytes(int B, int H, int W, int G);
@@ -689,6 +703,12 @@ int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *
 #define UOC_GRASP_WIDE (-2)
 #define UOC_GRASP_PINCHED (-3)
 #define UOC_GRASP_BLOCKED (-4)
+#define UOC_GRASP_SCALE 16384       /* S of the direction table and of the anchor */
+#define UOC_GRASP_MAX_OFFSETS 8     /* M in 0..8 */
+#define UOC_GRASP_MAX_OPEN 64       /* Wmax in 1..64 cells */
+#define UOC_GRASP_MAX_GAP 4         /* gap in 0..4 cells */
+#define UOC_GRASP_MAX_FINGER 8      /* F in 1..8 cells */
+#define UOC_GRASP_MAX_PAD 4         /* Hp in 0..4 cells */
 
 /* 0 for B outside 1..65535, a bad G, A outside 1..32 or M outside 0..8. */
 size_t uoc_grasp_workspace_bytes(int B, int G, int A, int M);
@@ -912,6 +932,7 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
  * bad ranges.  One memset and two launches.
  * ---------------------------------------------------------------------------------------- */
 #define UOC_CONF_MAX_N (1 << 30)
+#define UOC_CONF_ONE 65536          /* the fixed-point unit of uoc_conf_objects' q */
 
 /* 0 for a bad shape: batch outside 1..65535, n outside 1..2^30, m outside 1..128, halves not 1 or 2. */
 size_t uoc_ms_confidence_workspace_bytes(int batch, int n, int m, int halves);
@@ -996,6 +1017,17 @@ long uoc_lzf_decompress(const uint8_t *in, size_t in_len, uint8_t *out, size_t o
 int uoc_prof_enable(int on);
 int uoc_prof_reset(void);
 int uoc_prof_report(char *buf, size_t cap);
+
+#ifdef __cplusplus
+/* The record sizes a binding's struct mirrors are held to. */
+static_assert(sizeof(uoc_roi_table) == 2564, "uoc_roi_table");
+static_assert(sizeof(uoc_object) == 164, "uoc_object");
+static_assert(sizeof(uoc_track) == 20, "uoc_track");
+static_assert(sizeof(uoc_plane) == 84, "uoc_plane");
+static_assert(sizeof(uoc_plane_object) == 64, "uoc_plane_object");
+static_assert(sizeof(uoc_plane_info) == 32, "uoc_plane_info");
+static_assert(sizeof(uoc_relation_object) == 44, "uoc_relation_object");
+#endif
 
 #ifdef __cplusplus
 }

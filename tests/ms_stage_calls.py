@@ -24,10 +24,7 @@ def hill_climb_raw(X, Z0, iters, n=None, metric=COSINE):
     assert batch == 1 or n == X.shape[1]
     ws = MS._workspace(X.device, L.uoc_ms_workspace_bytes(batch, n, m))
     Z = Z0.clone()
-    with torch.cuda.device(X.device):
-        rc = L.uoc_ms_hill_climb_ex(_native.ptr(X), batch, n, _native.ptr(Z), m, KAPPA, iters, metric, _native.ptr(ws),
-                                    ws.numel(), _native.stream_ptr(X.device))
-    _native.check(rc, "uoc_ms_hill_climb_ex")
+    _native.call("uoc_ms_hill_climb_ex", X.device, X, batch, n, Z, m, KAPPA, iters, metric, ws, ws.numel())
     torch.cuda.synchronize(X.device)
     return Z
 
@@ -41,12 +38,8 @@ def select_raw(device, X, m, first=None, init=None, num_init=0, metric=COSINE):
     idx = torch.full((B, m), -7, dtype=torch.int32, device=device)
     firstd = None if first is None else torch.tensor(first, dtype=torch.int32, device=device)
     ws = MS._workspace(device, L.uoc_ms_workspace_bytes(B, n, m))
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_select_seeds_ex(_native.ptr(Xd), B, n, m, 0 if init is None else num_init, _native.ptr(firstd),
-                                      _native.ptr(seeds), _native.ptr(idx), metric, _native.ptr(ws), ws.numel(),
-                                      _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_select_seeds_ex")
-        _native.check(L.uoc_ms_check(_native.stream_ptr(device)), "uoc_ms_check")
+    _native.call("uoc_ms_select_seeds_ex", device, Xd, B, n, m, 0 if init is None else num_init, firstd, seeds, idx, metric, ws, ws.numel())
+    _native.call("uoc_ms_check", device)
     return idx.cpu().numpy(), seeds.cpu().numpy()
 
 
@@ -63,15 +56,11 @@ def both_sampling_kernels(fn):
 
 def components_raw(device, Z, eps, metric=COSINE):
     """uoc_ms_seed_components_ex on Z [B, m, 64] -> (labels [B, m], num_unique [B]) numpy."""
-    L = _native.lib()
     Zd = to_dev(Z, device)
     B, m = Z.shape[0], Z.shape[1]
     out = torch.full((B, m), -7, dtype=torch.int32, device=device)
     nu = torch.full((B,), -7, dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_seed_components_ex(_native.ptr(Zd), B, m, float(eps), metric, _native.ptr(out), _native.ptr(nu),
-                                         _native.stream_ptr(device))
-    _native.check(rc, "uoc_ms_seed_components_ex")
+    _native.call("uoc_ms_seed_components_ex", device, Zd, B, m, float(eps), metric, out, nu)
     return out.cpu().numpy(), nu.cpu().numpy()
 
 
@@ -85,16 +74,11 @@ def assign_raw(device, X, Z, sl, nu, metric=COSINE):
     B, n, m = X.shape[0], X.shape[1], Z.shape[1]
     la, ca, lc, cc = (torch.full((B, n), -7, dtype=torch.int32, device=device) for _ in range(4))
     ws = MS._workspace(device, L.uoc_ms_workspace_bytes(B, n, m))
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_assign_ex(_native.ptr(Xd), B, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, metric,
-                                _native.ptr(la), _native.ptr(ca), _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_assign_ex")
-        if metric != COSINE:
-            return (la.cpu().numpy(), ca.cpu().numpy()), None
-        margin = torch.empty((B, n), device=device)
-        nws = L.uoc_ms_confidence_workspace_bytes(B, n, m, 1)
-        cws = torch.empty(nws, dtype=torch.uint8, device=device)
-        rc = L.uoc_ms_confidence(_native.ptr(Xd), 1, B, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, 0, _native.ptr(lc),
-                                 _native.ptr(margin), None, _native.ptr(cc), None, _native.ptr(cws), nws, _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_confidence")
+    _native.call("uoc_ms_assign_ex", device, Xd, B, n, Zd, sld, nud, m, metric, la, ca, ws, ws.numel())
+    if metric != COSINE:
+        return (la.cpu().numpy(), ca.cpu().numpy()), None
+    margin = torch.empty((B, n), device=device)
+    nws = L.uoc_ms_confidence_workspace_bytes(B, n, m, 1)
+    cws = torch.empty(nws, dtype=torch.uint8, device=device)
+    _native.call("uoc_ms_confidence", device, Xd, 1, B, n, Zd, sld, nud, m, 0, lc, margin, None, cc, None, cws, nws)
     return (la.cpu().numpy(), ca.cpu().numpy()), (lc.cpu().numpy(), cc.cpu().numpy())

@@ -6,7 +6,6 @@
     (embeddings are unit-norm, so absolute == relative to the vector scale),
 (c) the CPU oracle on a fresh seeded input.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -54,10 +53,7 @@ def test_conv_kernel_vs_torch_cpu(device, case):
     rd = res.permute(0, 2, 3, 1).contiguous().to(device) if res is not None else None
     Ho, Wo = ref.shape[2], ref.shape[3]
     out = torch.empty((B, Ho, Wo, Cout), device=device)
-    L = _native.lib()
-    rc = L.uoc_conv2d_nhwc(_native.ptr(xd), _native.ptr(wd), _native.ptr(bd), _native.ptr(rd), _native.ptr(out),
-                           1, B, H, W, Cin, Cout, K, stride, dil, pad, int(relu), _native.stream_ptr(device))
-    _native.check(rc, "uoc_conv2d_nhwc")
+    _native.call("uoc_conv2d_nhwc", device, xd, wd, bd, rd, out, 1, B, H, W, Cin, Cout, K, stride, dil, pad, int(relu))
     got = out.cpu().permute(0, 3, 1, 2)
     err = (got - ref).abs().max().item()
     assert err < 2e-4 * max(1.0, ref.abs().max().item()), err

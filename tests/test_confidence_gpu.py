@@ -55,10 +55,7 @@ def raw_assign(device, X, Z, sl, nu):
     n, m = X.shape[0], Z.shape[0]
     labels, closest = (torch.empty((1, n), dtype=torch.int32, device=device) for _ in range(2))
     ws = MS._workspace(device, L.uoc_ms_workspace_bytes(1, n, m))
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_assign(_native.ptr(Xd), 1, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, _native.ptr(labels),
-                             _native.ptr(closest), _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
-    _native.check(rc, "uoc_ms_assign")
+    _native.call("uoc_ms_assign", device, Xd, 1, n, Zd, sld, nud, m, labels, closest, ws, ws.numel())
     return labels[0].cpu().numpy(), closest[0].cpu().numpy()
 
 
@@ -214,11 +211,8 @@ def test_null_optional_outputs(device):
         labels = torch.full((1, n), -77, dtype=torch.int32, device=device)
         margin = torch.full((1, n), -77.0, device=device)
         opt = {k: torch.full((1, n), -77, dtype=torch.int32, device=device) if k in keep else None for k in ("second", "closest", "rival")}
-        with torch.cuda.device(device):
-            rc = L.uoc_ms_confidence(_native.ptr(Xd), 1, 1, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, 0,
-                                     _native.ptr(labels), _native.ptr(margin), _native.ptr(opt["second"]), _native.ptr(opt["closest"]),
-                                     _native.ptr(opt["rival"]), _native.ptr(ws), nws, _native.stream_ptr(device))
-        _native.check(rc, "uoc_ms_confidence")
+        _native.call("uoc_ms_confidence", device, Xd, 1, 1, n, Zd, sld, nud, m, 0, labels, margin, opt["second"], opt["closest"],
+                     opt["rival"], ws, nws)
         assert torch.equal(labels, full.labels) and torch.equal(margin, full.margin), keep
         for k in keep:
             assert torch.equal(opt[k], getattr(full, k)), k
@@ -274,11 +268,7 @@ def match_with_plan(labels_crop, mask, depth, table, K, S, H, W, device):
     refined = torch.empty((H * W,), dtype=torch.int32, device=device)
     plan = torch.empty((K + K * 128,), dtype=torch.int32, device=device)
     ws, status = TD._ws(device), TD._status_word(device)
-    with torch.cuda.device(device):
-        rc = _native.lib().uoc_roi_match(_native.ptr(labels_crop), _native.ptr(mask), _native.ptr(depth), _native.ptr(table), K, S,
-                                         H, W, _native.ptr(refined), None, _native.ptr(plan), _native.ptr(status), _native.ptr(ws),
-                                         ws.numel(), _native.stream_ptr(device))
-    _native.check(rc, "uoc_roi_match")
+    _native.call("uoc_roi_match", device, labels_crop, mask, depth, table, K, S, H, W, refined, None, plan, status, ws, ws.numel())
     assert not TD._take_order_flag(status)
     return refined, plan
 

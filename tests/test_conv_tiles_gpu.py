@@ -295,9 +295,7 @@ def _stem(device, x, w, b, res, relu):
     wh = w.contiguous().float()
     bh = b.contiguous().float() if b is not None else None
     out = torch.full((G, B, H1, W1, 64), float("nan"), device=device)
-    rc = _native.lib().uoc_net_stem(_native.ptr(xd), _native.ptr(wh), _native.ptr(bh), _native.ptr(res), G, B, H, W, int(relu),
-                                    _native.ptr(out), _native.stream_ptr(device))
-    _native.check(rc, "uoc_net_stem")
+    _native.call("uoc_net_stem", device, xd, wh, bh, res, G, B, H, W, int(relu), out)
     return out
 
 
@@ -360,8 +358,7 @@ def test_maxpool_equals_torch(device, hw, negative):
     assert want.shape == (3, 64, Ho, Wo)
     xd = x.permute(0, 2, 3, 1).contiguous().to(device)
     out = torch.full((3, Ho, Wo, 64), float("nan"), device=device)
-    rc = _native.lib().uoc_maxpool3x3s2_nhwc(_native.ptr(xd), _native.ptr(out), 3, H, W, 64, _native.stream_ptr(device))
-    _native.check(rc, "uoc_maxpool3x3s2_nhwc")
+    _native.call("uoc_maxpool3x3s2_nhwc", device, xd, out, 3, H, W, 64)
     assert torch.equal(out.cpu().permute(0, 3, 1, 2), want)
 
 
@@ -376,8 +373,7 @@ def _head(device, fa, fb, H, W, cat):
     fad = fa.permute(0, 2, 3, 1).contiguous().to(device)
     fbd = fb.permute(0, 2, 3, 1).contiguous().to(device) if fb is not None else None
     out = torch.full((B, 2 if cat else 1, H * W, 64), float("nan"), device=device)
-    rc = _native.lib().uoc_head(_native.ptr(fad), _native.ptr(fbd), _native.ptr(out), B, h, w, H, W, int(cat), _native.stream_ptr(device))
-    _native.check(rc, "uoc_head")
+    _native.call("uoc_head", device, fad, fbd, out, B, h, w, H, W, int(cat))
     return out.cpu().permute(0, 1, 3, 2).reshape(B, -1, H, W)
 
 

@@ -79,14 +79,11 @@ def test_filter_raw_abi_leaves_foreign_ids_alone(device, thr):
     filtered = G.filter_labels_depth(clean.float(), depth, thr)
     want = filtered.to(torch.int32)
     want[invalid] = raw[invalid]
-    L, ws = _native.lib(), TD._ws(device)
+    ws = TD._ws(device)
     B, H, W = raw.shape
     depth_d = depth.to(device).contiguous()
     lab = raw.to(device).contiguous()
-    with torch.cuda.device(device):
-        rc = L.uoc_filter_labels_depth(_native.ptr(lab), _z_plane(depth_d, H, W), 3 * H * W, B, H, W, float(thr),
-                                       _native.ptr(ws), ws.numel(), _native.stream_ptr(device))
-    _native.check(rc, "uoc_filter_labels_depth")
+    _native.call("uoc_filter_labels_depth", device, lab, _z_plane(depth_d, H, W), 3 * H * W, B, H, W, float(thr), ws, ws.numel())
     assert torch.equal(lab.cpu(), want)
     # the fused form: filter + ROI table in one call
     lab = raw[0].to(device).contiguous()
@@ -300,17 +297,14 @@ def test_roi_match_stats_alone(device, name):
     labels, mask, depth = _stats_inputs()[name]
     K, S = labels.shape[0], labels.shape[-1]
     want_keep, want_meanz, _ = C.oracle_keep_meanz(labels, mask, depth)
-    L, ws = _native.lib(), TD._ws(device)
+    ws = TD._ws(device)
     lab_d = labels.to(torch.int32).reshape(K, -1).to(device)
     mask_d, depth_d = mask.to(device).contiguous(), depth.to(device).contiguous()
     for with_depth in (True, False):
         keep = torch.full((K, 128), -7, dtype=torch.int32, device=device)
         meanz = torch.full((K,), 123.0, device=device)
-        with torch.cuda.device(device):
-            rc = L.uoc_roi_match_stats(_native.ptr(lab_d), _native.ptr(mask_d), _native.ptr(depth_d if with_depth else None), K, S,
-                                       _native.ptr(keep), _native.ptr(meanz if with_depth else None), _native.ptr(ws),
-                                       ws.numel(), _native.stream_ptr(device))
-        _native.check(rc, "uoc_roi_match_stats")
+        _native.call("uoc_roi_match_stats", device, lab_d, mask_d, depth_d if with_depth else None, K, S, keep,
+                     meanz if with_depth else None, ws, ws.numel())
         assert torch.equal(keep.cpu(), want_keep)
         got = meanz.cpu()
         if not with_depth:
@@ -327,9 +321,7 @@ def test_roi_match_stats_alone(device, name):
 def _to_u8(lab_d, n, preset, device):
     out = torch.full((n + 8,), 0xAA, dtype=torch.uint8, device=device)
     top = torch.tensor([preset], dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        rc = _native.lib().uoc_labels_to_u8(_native.ptr(lab_d), n, _native.ptr(out), _native.ptr(top), _native.stream_ptr(device))
-    _native.check(rc, "uoc_labels_to_u8")
+    _native.call("uoc_labels_to_u8", device, lab_d, n, out, top)
     return out.cpu().numpy(), int(top.item())
 
 

@@ -166,8 +166,7 @@ def _hill_climb_raw(X, Z0, iters=10):
     batch, n, _ = X.shape
     ws = MS._workspace(X.device, L.uoc_ms_workspace_bytes(batch, n, Z0.shape[1]))
     Z = Z0.clone()
-    _native.check(L.uoc_ms_hill_climb(_native.ptr(X), batch, n, _native.ptr(Z), Z0.shape[1], KAPPA, iters, _native.ptr(ws),
-                                      ws.numel(), _native.stream_ptr(X.device)), "uoc_ms_hill_climb")
+    _native.call("uoc_ms_hill_climb", X.device, X, batch, n, Z, Z0.shape[1], KAPPA, iters, ws, ws.numel())
     torch.cuda.synchronize()
     return Z
 

@@ -279,11 +279,7 @@ def confidence_all(device, X, Z, sl, nu, halves):
     margin = torch.full((1, n), -7.0, device=device)
     nws = L.uoc_ms_confidence_workspace_bytes(1, n, m, halves)
     cws = torch.empty(nws, dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        rc = L.uoc_ms_confidence(_native.ptr(Xd), halves, 1, n, _native.ptr(Zd), _native.ptr(sld), _native.ptr(nud), m, 0,
-                                 _native.ptr(labels), _native.ptr(margin), _native.ptr(second), _native.ptr(closest),
-                                 _native.ptr(rival), _native.ptr(cws), nws, _native.stream_ptr(device))
-    _native.check(rc, "uoc_ms_confidence")
+    _native.call("uoc_ms_confidence", device, Xd, halves, 1, n, Zd, sld, nud, m, 0, labels, margin, second, closest, rival, cws, nws)
     return [t[0].cpu().numpy() for t in (labels, margin, second, closest, rival)]
 
 

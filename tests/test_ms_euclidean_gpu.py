@@ -215,10 +215,7 @@ def test_cosine_metric_equals_the_unchanged_entry_points(device):
     Z = torch.empty((B, 100, 64), dtype=torch.float32, device=device)
     sl = torch.empty((B, 100), dtype=torch.int32, device=device)
     ws = torch.empty(L.uoc_ms_workspace_bytes(B, n, 100), dtype=torch.uint8, device=device)
-    rc = L.uoc_ms_cluster(_native.ptr(X), B, n, 100, KAPPA, 10, EPSILON, _native.ptr(first), _native.ptr(labels),
-                          _native.ptr(indices), _native.ptr(Z), _native.ptr(sl), _native.ptr(ws), ws.numel(),
-                          _native.stream_ptr(device))
-    _native.check(rc, "uoc_ms_cluster")
+    _native.call("uoc_ms_cluster", device, X, B, n, 100, KAPPA, 10, EPSILON, first, labels, indices, Z, sl, ws, ws.numel())
     for a, b in zip(got, (labels, indices, Z, sl)):
         assert torch.equal(a, b)
     assert cfg.TRAIN.EMBEDDING_METRIC == "cosine"

@@ -18,6 +18,109 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(uoc_[a-z0-9_]+)\s*\(", src)))
 
 
+def header_text():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def header_prototypes():
+    """[(name, return type, [argument types])] of every function the header declares, in its order, as C type strings
+    without the argument names."""
+    out = []
+    for ret, name, args in re.findall(r"^([A-Za-z_][\w \*]*?)\b(uoc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text(), flags=re.M):
+        args = [] if args.strip() == "void" else [re.match(r"(.*?)\w+$", a.strip()).group(1).strip() for a in args.split(",")]
+        out.append((name, ret.strip(), args))
+    return out
+
+
+def header_constants():
+    """{name: value} of the header's #define and enum constants with an integer value."""
+    src, out = header_text(), {}
+    pairs = re.findall(r"^#define\s+(UOC_\w+)\s+(.+?)\s*$", src, flags=re.M)
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", src):
+        pairs += [tuple(x.strip() for x in item.split("=")) for item in body.split(",") if "=" in item]
+    for name, value in pairs:
+        if re.fullmatch(r"[-\d\s()<*+]+", value):
+            out[name] = eval(value)
+    return out
+
+
+# C scalar -> the ctypes of the same size and signedness; a pointer of any kind matches any ctypes pointer type
+SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "long": ctypes.c_long,
+           "uint32_t": ctypes.c_uint32, "unsigned long long": ctypes.c_ulonglong}
+
+
+def matches(c_type, ct):
+    if "*" in c_type:
+        return ct in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ct, type) and issubclass(ct, ctypes._Pointer))
+    return SCALARS[re.sub(r"\bconst\b", "", c_type).strip()] is ct
+
+
+def abi_mismatches(table):
+    protos = header_prototypes()
+    bad = [f"{name}: not in the table" for name, _, _ in protos if name not in table]
+    for name, ret, args in protos:
+        if name not in table:
+            continue
+        restype, argtypes = table[name]
+        if not matches(ret, restype):
+            bad.append(f"{name}: returns {ret}, the table says {restype}")
+        if len(args) != len(argtypes):
+            bad.append(f"{name}: {len(args)} arguments, the table has {len(argtypes)}")
+        bad += [f"{name}: argument {i} is {a}, the table says {t}" for i, (a, t) in enumerate(zip(args, argtypes)) if not matches(a, t)]
+    return bad
+
+
+def test_abi_table_matches_every_prototype():
+    protos = header_prototypes()
+    assert len(protos) >= 87 and sorted(p[0] for p in protos) == declared_symbols()     # the parser misses no declaration
+    assert list(_native.ABI) == [p[0] for p in protos]              # the table is in header order, nothing extra
+    assert all(restype is not None and isinstance(argtypes, list) for restype, argtypes in _native.ABI.values())
+    assert abi_mismatches(_native.ABI) == []
+    lib = _native.lib()                                             # and the loaded library carries exactly the table
+    for name, (restype, argtypes) in _native.ABI.items():
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == argtypes, name
+
+
+def test_abi_check_catches_a_wrong_entry():
+    """The comparison itself: a c_int for a size_t, a missing argument and a wrong return type are each reported."""
+    I, Z, P = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
+    ret, args = _native.ABI["uoc_grasp"]
+    for name, entry in (("uoc_grasp", (ret, [I if t is Z else t for t in args])), ("uoc_grasp", (ret, args[:-1])),
+                        ("uoc_grasp_workspace_bytes", (I, [I] * 4)), ("uoc_ms_check", (I, [I])),
+                        ("uoc_support_plane", (ret, [I if t is ctypes.c_uint32 else t for t in _native.ABI["uoc_support_plane"][1]]))):
+        bad = abi_mismatches({**_native.ABI, name: entry})
+        assert len(bad) == 1 and bad[0].startswith(name + ":"), bad
+
+
+# module constants of _native that are no mirror of a header constant
+NOT_MIRRORED = {"ROI_TABLE_BYTES", "OBJECT_BYTES", "GRAPHS_ALIVE"}
+
+
+def test_mirrored_constants_equal_the_header():
+    """Every upper-case integer of _native is the header's UOC_<name>, value for value."""
+    consts = header_constants()
+    mirrored = {k: v for k, v in vars(_native).items() if k.isupper() and type(v) is int and k not in NOT_MIRRORED}
+    assert len(mirrored) >= 50
+    for name, value in mirrored.items():
+        assert "UOC_" + name in consts, f"_native.{name} has no UOC_{name} in include/uoc_hip.h"
+        assert consts["UOC_" + name] == value, f"_native.{name} = {value}, the header says {consts['UOC_' + name]}"
+    assert _native.METRICS == {"cosine": consts["UOC_METRIC_COSINE"], "euclidean": consts["UOC_METRIC_EUCLIDEAN"]}
+    assert _native.CC_MODES == {"all": consts["UOC_CC_ALL"], "largest": consts["UOC_CC_LARGEST"]}
+
+
+def test_struct_mirrors_have_the_header_sizes():
+    """ctypes.sizeof of every struct mirror against the sizeof the header's static_assert states."""
+    sizes = {n: int(v) for n, v in re.findall(r"static_assert\(sizeof\((uoc_\w+)\) == (\d+)", header_text())}
+    mirrors = {"uoc_roi_table": _native.RoiTable, "uoc_object": _native.UocObject, "uoc_track": _native.UocTrack,
+               "uoc_plane": _native.UocPlane, "uoc_plane_object": _native.UocPlaneObject, "uoc_plane_info": _native.UocPlaneInfo,
+               "uoc_relation_object": _native.UocRelationObject}
+    assert set(sizes) == set(mirrors)
+    for name, cls in mirrors.items():
+        assert ctypes.sizeof(cls) == sizes[name], name
+    assert all(issubclass(v, ctypes.Structure) and v in mirrors.values() for v in vars(_native).values()
+               if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure)
+
+
 def test_library_builds_and_loads():
     path = build_native()
     assert os.path.exists(path)

@@ -12,7 +12,6 @@ stored centroid and axes, with every point inside it; each bound is derived ther
 roundings.  One judgement is left open: the sign rule is checked only where the stored float32 vector decides it; a tie of
 mixed signs within 2^-22 of the largest component is decided by fp64 bits the record does not hold, and the exact
 45-degree cases cover it.  The exact cases are in tests/test_stats_cases_gpu.py."""
-import ctypes
 import json
 import os
 import subprocess
@@ -180,9 +179,7 @@ def test_capacity_is_respected(device):
     tot = torch.zeros(1, dtype=torch.int32, device=device)
     nws = lib.uoc_objects_workspace_bytes(B, H, W)
     ws = torch.empty(nws, dtype=torch.uint8, device=device)
-    rc = lib.uoc_objects(_native.ptr(dl), _native.ptr(dx), None, 0, B, H, W, 0, _native.ptr(rec), _native.ptr(pts), None,
-                         _native.ptr(pix), ctypes.c_long(cap), _native.ptr(tot), _native.ptr(ws), nws, _native.stream_ptr(device))
-    _native.check(rc, "uoc_objects")
+    _native.call("uoc_objects", device, dl, dx, None, 0, B, H, W, 0, rec, pts, None, pix, cap, tot, ws, nws)
     assert int(tot.cpu()[0]) == len(want) > cap
     p = pts.cpu().reshape(-1, 3)
     assert torch.equal(p[:cap], torch.from_numpy(want[:cap])) and bool((p[cap:] == -7.0).all())

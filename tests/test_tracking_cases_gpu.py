@@ -90,11 +90,7 @@ def raw_run(device, c, label_offset=0, outputs=True):
     steps = []
     for t in range(T):
         lab.copy_(torch.from_numpy(frames[t].reshape(-1)).to(device))
-        with torch.cuda.device(device):
-            rc = lib.uoc_track_step(_native.ptr(lab), 1, H, W, iou_threshold(c["min_iou"]), c["max_age"], _native.ptr(state),
-                                    _native.ptr(out), _native.ptr(lut), _native.ptr(tracks), _native.ptr(ws), ws.numel(),
-                                    _native.stream_ptr(device))
-        _native.check(rc, "uoc_track_step")
+        _native.call("uoc_track_step", device, lab, 1, H, W, iou_threshold(c["min_iou"]), c["max_age"], state, out, lut, tracks, ws, ws.numel())
         steps.append((out.cpu().numpy().reshape(H, W), state.view(torch.int32).cpu().numpy(),
                       lut.cpu().numpy() if outputs else None, tracks.cpu().numpy() if outputs else None))
     assert not buf[:label_offset].any() and not buf[label_offset + n:].any()

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p, POINTER
+from ctypes import c_char_p, c_float, c_int, c_int32, c_long, c_size_t, c_uint32, c_ulonglong, c_void_p, POINTER
 
 from .build import LIB_PATH
 
@@ -15,162 +15,105 @@ class NativeError(RuntimeError):
     pass
 
 
+# The C ABI of include/uoc_hip.h, in its order: name -> (restype, argtypes).  tests/test_native_abi.py parses the header and
+# holds every entry to its prototype.  Every pointer is a c_void_p: a tensor's data_ptr(), None or a ctypes array passes.
+P, I, F, Z, L, U = c_void_p, c_int, c_float, c_size_t, c_long, c_uint32
+ABI = {
+    "uoc_version": (I, []),
+    "uoc_is_dev_build": (I, []),
+    "uoc_config_fingerprint": (c_ulonglong, []),
+    "uoc_shutdown": (I, []),
+    "uoc_last_error": (c_char_p, []),
+    "uoc_reload_env": (I, []),
+    "uoc_ms_set_persistent_fps": (I, [I]),
+    "uoc_ms_set_stream_ordering": (I, [I]),
+    "uoc_ms_fps_fallbacks": (I, []),
+    "uoc_ms_check": (I, [P]),
+    "uoc_ms_workspace_bytes": (Z, [I, I, I]),
+    "uoc_ms_select_seeds": (I, [P, I, I, I, P, P, P, P, Z, P]),
+    "uoc_ms_select_seeds_from": (I, [P, I, I, I, I, P, P, P, P, Z, P]),
+    "uoc_ms_hill_climb": (I, [P, I, I, P, I, F, I, P, Z, P]),
+    "uoc_ms_seed_components": (I, [P, I, I, F, P, P, P]),
+    "uoc_ms_assign": (I, [P, I, I, P, P, P, I, P, P, P, Z, P]),
+    "uoc_ms_cluster": (I, [P, I, I, I, F, I, F, P, P, P, P, P, P, Z, P]),
+    "uoc_ms_workspace_bytes_wide": (Z, [I, I, I, I]),
+    "uoc_ms_cluster_wide": (I, [P, I, I, I, I, F, I, F, P, P, P, P, P, P, Z, P]),
+    "uoc_ms_select_seeds_ex": (I, [P, I, I, I, I, P, P, P, I, P, Z, P]),
+    "uoc_ms_hill_climb_ex": (I, [P, I, I, P, I, F, I, I, P, Z, P]),
+    "uoc_ms_seed_components_ex": (I, [P, I, I, F, I, P, P, P]),
+    "uoc_ms_assign_ex": (I, [P, I, I, P, P, P, I, I, P, P, P, Z, P]),
+    "uoc_ms_cluster_ex": (I, [P, I, I, I, F, I, F, I, P, P, P, P, P, P, Z, P]),
+    "uoc_ms_cluster_wide_ex": (I, [P, I, I, I, I, F, I, F, I, P, P, P, P, P, P, Z, P]),
+    "uoc_net_create": (I, [POINTER(P)]),
+    "uoc_net_create_mode": (I, [POINTER(P), I]),
+    "uoc_net_embed_dim": (I, [P]),
+    "uoc_net_destroy": (I, [P]),
+    "uoc_net_load_param": (I, [P, c_char_p, P, Z]),
+    "uoc_net_finalize": (I, [P]),
+    "uoc_net_workspace_bytes": (Z, [P, I, I, I]),
+    "uoc_net_set_split_precision": (I, [P, I]),
+    "uoc_net_forward": (I, [P, P, P, I, I, I, P, P, Z, P]),
+    "uoc_conv2d_nhwc": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "uoc_conv2d_nhwc_algo": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "uoc_conv2d_tile_list": (I, [I, P, I]),
+    "uoc_conv2d_nhwc_tile": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I]),
+    "uoc_conv2d_tile_choice": (I, [I, I, I, I, I, I, I, I, I, I, P, P, P]),
+    "uoc_net_stem": (I, [P, P, P, P, I, I, I, I, I, P, P]),
+    "uoc_maxpool3x3s2_nhwc": (I, [P, P, I, I, I, I, P]),
+    "uoc_head": (I, [P, P, P, I, I, I, I, I, I, P]),
+    "uoc_roi_workspace_bytes": (Z, []),
+    "uoc_prep_rgbd": (I, [P, P, I, I, F, F, F, F, F, F, F, P, P, P]),
+    "uoc_filter_labels_depth": (I, [P, P, L, I, I, I, F, P, Z, P]),
+    "uoc_roi_build": (I, [P, P, I, I, F, F, P, P, Z, P]),
+    "uoc_roi_crop": (I, [P, P, P, I, I, P, I, I, P, P, P, P]),
+    "uoc_roi_match_stats": (I, [P, P, P, I, I, P, P, P, Z, P]),
+    "uoc_roi_paste": (I, [P, P, P, P, I, I, I, I, P, P]),
+    "uoc_roi_match": (I, [P, P, P, P, I, I, I, I, P, P, P, P, P, Z, P]),
+    "uoc_labels_to_u8": (I, [P, L, P, P, P]),
+    "uoc_eval_workspace_bytes": (Z, [I, I]),
+    "uoc_eval_pair_stats": (I, [P, P, I, I, I, P, P, Z, P]),
+    "uoc_objects_workspace_bytes": (Z, [I, I, I]),
+    "uoc_objects": (I, [P, P, P, I, I, I, I, I, P, P, P, P, L, P, P, Z, P]),
+    "uoc_track_state_bytes": (Z, [I, I, I]),
+    "uoc_track_workspace_bytes": (Z, [I]),
+    "uoc_track_reset": (I, [P, I, I, I, I, P]),
+    "uoc_track_step": (I, [P, I, I, I, I, I, P, P, P, P, P, Z, P]),
+    "uoc_cc_workspace_bytes": (Z, [I, I, I]),
+    "uoc_cc_split": (I, [P, I, I, I, I, I, I, P, P, P, P, Z, P]),
+    "uoc_plane_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_support_plane": (I, [P, P, I, I, I, I, I, U, P, P, P, P, Z, P]),
+    "uoc_planes_workspace_bytes": (Z, [I, I, I, I, I]),
+    "uoc_support_planes": (I, [P, P, I, I, I, I, I, I, I, I, U, P, P, P, P, P, P, Z, P]),
+    "uoc_relations_workspace_bytes": (Z, [I, I, I]),
+    "uoc_relations": (I, [P, P, I, I, I, I, I, I, P, P, P, Z, P]),
+    "uoc_placement_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_placement": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P, I, P, P, P, P, P, P, P, Z, P]),
+    "uoc_grasp_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_grasp": (I, [P, P, I, I, P, I, I, I, I, I, I, I, P, P, P, Z, P]),
+    "uoc_elevation_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_elevation": (I, [P, P, P, I, I, I, I, I, I, I, I, P, I, P, P, P, P, P, P, P, P, P, Z, P]),
+    "uoc_footprint_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_footprint": (I, [P, P, P, P, I, I, P, I, P, I, I, P, P, P, P, Z, P]),
+    "uoc_routes_workspace_bytes": (Z, [I, I, I]),
+    "uoc_routes": (I, [P, P, P, I, I, P, I, I, I, P, P, P, P, Z, P]),
+    "uoc_ms_confidence_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_ms_confidence": (I, [P, I, I, I, P, P, P, I, I, P, P, P, P, P, P, Z, P]),
+    "uoc_conf_paste": (I, [P, P, P, P, I, I, I, I, P, P]),
+    "uoc_conf_objects": (I, [P, P, I, I, I, I, P, P]),
+    "uoc_normals_workspace_bytes": (Z, [I, I, I]),
+    "uoc_normals": (I, [P, P, P, I, I, I, I, I, I, I, P, I, I, I, P, P, P, P, Z, P]),
+    "uoc_lzf_decompress": (L, [P, Z, P, Z]),
+    "uoc_prof_enable": (I, [I]),
+    "uoc_prof_reset": (I, []),
+    "uoc_prof_report": (I, [c_char_p, Z]),
+}
+EXPORTED_SYMBOLS = tuple(ABI)
+
+
 def _declare(lib):
-    P = c_void_p
-    lib.uoc_version.restype = c_int
-    lib.uoc_is_dev_build.argtypes = []
-    lib.uoc_is_dev_build.restype = c_int
-    lib.uoc_config_fingerprint.argtypes = []
-    lib.uoc_config_fingerprint.restype = ctypes.c_ulonglong
-    lib.uoc_shutdown.restype = c_int
-    lib.uoc_reload_env.argtypes = []
-    lib.uoc_reload_env.restype = c_int
-    lib.uoc_shutdown.argtypes = []
-    lib.uoc_last_error.restype = c_char_p
-    lib.uoc_ms_set_persistent_fps.argtypes = [c_int]
-    lib.uoc_ms_set_persistent_fps.restype = c_int
-    lib.uoc_ms_set_stream_ordering.argtypes = [c_int]
-    lib.uoc_ms_set_stream_ordering.restype = c_int
-    lib.uoc_ms_fps_fallbacks.argtypes = []
-    lib.uoc_ms_fps_fallbacks.restype = c_int
-    lib.uoc_ms_workspace_bytes.restype = c_size_t
-    lib.uoc_ms_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_ms_select_seeds.argtypes = [P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
-    lib.uoc_ms_select_seeds_from.argtypes = [P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
-    lib.uoc_ms_hill_climb.argtypes = [P, c_int, c_int, P, c_int, c_float, c_int, P, c_size_t, P]
-    lib.uoc_ms_seed_components.argtypes = [P, c_int, c_int, c_float, P, P, P]
-    lib.uoc_ms_assign.argtypes = [P, c_int, c_int, P, P, P, c_int, P, P, P, c_size_t, P]
-    lib.uoc_ms_cluster.argtypes = [P, c_int, c_int, c_int, c_float, c_int, c_float, P, P, P, P, P, P, c_size_t, P]
-    lib.uoc_ms_check.argtypes = [P]
-    lib.uoc_ms_check.restype = c_int
-    lib.uoc_ms_workspace_bytes_wide.restype = c_size_t
-    lib.uoc_ms_workspace_bytes_wide.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_ms_cluster_wide.argtypes = [P, c_int, c_int, c_int, c_int, c_float, c_int, c_float, P, P, P, P, P, P, c_size_t, P]
-    lib.uoc_ms_cluster_wide.restype = c_int
-    # the same calls with the embedding metric (METRIC_COSINE / METRIC_EUCLIDEAN) as an argument
-    lib.uoc_ms_select_seeds_ex.argtypes = [P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, c_size_t, P]
-    lib.uoc_ms_hill_climb_ex.argtypes = [P, c_int, c_int, P, c_int, c_float, c_int, c_int, P, c_size_t, P]
-    lib.uoc_ms_seed_components_ex.argtypes = [P, c_int, c_int, c_float, c_int, P, P, P]
-    lib.uoc_ms_assign_ex.argtypes = [P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, c_size_t, P]
-    lib.uoc_ms_cluster_ex.argtypes = [P, c_int, c_int, c_int, c_float, c_int, c_float, c_int, P, P, P, P, P, P, c_size_t, P]
-    lib.uoc_ms_cluster_wide_ex.argtypes = [P, c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_int, P, P, P, P, P, P,
-                                           c_size_t, P]
-    for name in METRIC_SYMBOLS:
-        getattr(lib, name).restype = c_int
-    lib.uoc_net_embed_dim.argtypes = [P]
-    lib.uoc_net_embed_dim.restype = c_int
-    lib.uoc_net_create.argtypes = [POINTER(P)]
-    lib.uoc_net_create_mode.argtypes = [POINTER(P), c_int]
-    lib.uoc_net_destroy.argtypes = [P]
-    lib.uoc_net_load_param.argtypes = [P, c_char_p, P, c_size_t]
-    lib.uoc_net_finalize.argtypes = [P]
-    lib.uoc_net_workspace_bytes.restype = c_size_t
-    lib.uoc_net_workspace_bytes.argtypes = [P, c_int, c_int, c_int]
-    lib.uoc_net_forward.argtypes = [P, P, P, c_int, c_int, c_int, P, P, c_size_t, P]
-    lib.uoc_net_set_split_precision.argtypes = [P, c_int]
-    lib.uoc_net_set_split_precision.restype = c_int
-    lib.uoc_conv2d_nhwc.argtypes = [P, P, P, P, P] + [c_int] * 11 + [P]
-    lib.uoc_conv2d_nhwc_algo.argtypes = [P, P, P, P, P] + [c_int] * 12 + [P]
-    lib.uoc_conv2d_nhwc_algo.restype = c_int
-    # test entries: one tile instantiation at a time; stem, pooling and head on their own
-    lib.uoc_conv2d_tile_list.argtypes = [c_int, P, c_int]
-    lib.uoc_conv2d_nhwc_tile.argtypes = [P, P, P, P, P] + [c_int] * 12 + [P, c_int, c_int]
-    lib.uoc_conv2d_tile_choice.argtypes = [c_int] * 10 + [P, P, P]
-    lib.uoc_net_stem.argtypes = [P, P, P, P] + [c_int] * 5 + [P, P]
-    lib.uoc_maxpool3x3s2_nhwc.argtypes = [P, P] + [c_int] * 4 + [P]
-    lib.uoc_head.argtypes = [P, P, P] + [c_int] * 6 + [P]
-    for name in TILE_SYMBOLS:
-        getattr(lib, name).restype = c_int
-    for name in ("uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_forward",
-                 "uoc_conv2d_nhwc"):
-        getattr(lib, name).restype = c_int
-    lib.uoc_eval_workspace_bytes.restype = c_size_t
-    lib.uoc_eval_workspace_bytes.argtypes = [c_int, c_int]
-    lib.uoc_eval_pair_stats.argtypes = [P, P, c_int, c_int, c_int, P, P, c_size_t, P]
-    lib.uoc_eval_pair_stats.restype = c_int
-    lib.uoc_roi_workspace_bytes.restype = c_size_t
-    lib.uoc_roi_workspace_bytes.argtypes = []
-    lib.uoc_prep_rgbd.argtypes = [P, P, c_int, c_int] + [c_float] * 7 + [P, P, P]
-    lib.uoc_prep_rgbd.restype = c_int
-    lib.uoc_filter_labels_depth.argtypes = [P, P, ctypes.c_long, c_int, c_int, c_int, c_float, P, c_size_t, P]
-    lib.uoc_roi_build.argtypes = [P, P, c_int, c_int, c_float, c_float, P, P, c_size_t, P]
-    lib.uoc_roi_crop.argtypes = [P, P, P, c_int, c_int, P, c_int, c_int, P, P, P, P]
-    lib.uoc_roi_match_stats.argtypes = [P, P, P, c_int, c_int, P, P, P, c_size_t, P]
-    lib.uoc_roi_paste.argtypes = [P, P, P, P, c_int, c_int, c_int, c_int, P, P]
-    lib.uoc_labels_to_u8.argtypes = [P, ctypes.c_long, P, P, P]
-    lib.uoc_roi_match.argtypes = [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]
-    for name in ("uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats", "uoc_roi_paste", "uoc_labels_to_u8", "uoc_roi_match"):
-        getattr(lib, name).restype = c_int
-    lib.uoc_objects_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_objects_workspace_bytes.restype = c_size_t
-    lib.uoc_objects.argtypes = [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, ctypes.c_long, P, P, c_size_t, P]
-    lib.uoc_objects.restype = c_int
-    lib.uoc_track_state_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_track_state_bytes.restype = c_size_t
-    lib.uoc_track_workspace_bytes.argtypes = [c_int]
-    lib.uoc_track_workspace_bytes.restype = c_size_t
-    lib.uoc_track_reset.argtypes = [P, c_int, c_int, c_int, c_int, P]
-    lib.uoc_track_reset.restype = c_int
-    lib.uoc_track_step.argtypes = [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]
-    lib.uoc_track_step.restype = c_int
-    lib.uoc_cc_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_cc_workspace_bytes.restype = c_size_t
-    lib.uoc_cc_split.argtypes = [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
-    lib.uoc_cc_split.restype = c_int
-    lib.uoc_plane_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_plane_workspace_bytes.restype = c_size_t
-    lib.uoc_support_plane.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32, P, P, P, P, c_size_t, P]
-    lib.uoc_support_plane.restype = c_int
-    lib.uoc_planes_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    lib.uoc_planes_workspace_bytes.restype = c_size_t
-    lib.uoc_support_planes.argtypes = [P, P] + [c_int] * 8 + [ctypes.c_uint32, P, P, P, P, P, P, c_size_t, P]
-    lib.uoc_support_planes.restype = c_int
-    lib.uoc_relations_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_relations_workspace_bytes.restype = c_size_t
-    lib.uoc_relations.argtypes = [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]
-    lib.uoc_relations.restype = c_int
-    lib.uoc_placement_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_placement_workspace_bytes.restype = c_size_t
-    lib.uoc_placement.argtypes = [P, P, P] + [c_int] * 9 + [P, c_int, P, P, P, P, P, P, P, c_size_t, P]
-    lib.uoc_placement.restype = c_int
-    lib.uoc_grasp_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_grasp_workspace_bytes.restype = c_size_t
-    lib.uoc_grasp.argtypes = [P, P, c_int, c_int, P] + [c_int] * 7 + [P, P, P, c_size_t, P]
-    lib.uoc_grasp.restype = c_int
-    lib.uoc_elevation_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_elevation_workspace_bytes.restype = c_size_t
-    lib.uoc_elevation.argtypes = [P, P, P] + [c_int] * 8 + [P, c_int] + [P] * 9 + [c_size_t, P]
-    lib.uoc_elevation.restype = c_int
-    lib.uoc_footprint_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_footprint_workspace_bytes.restype = c_size_t
-    lib.uoc_footprint.argtypes = [P, P, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, c_size_t, P]
-    lib.uoc_footprint.restype = c_int
-    lib.uoc_routes_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_routes_workspace_bytes.restype = c_size_t
-    lib.uoc_routes.argtypes = [P, P, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
-    lib.uoc_routes.restype = c_int
-    lib.uoc_ms_confidence_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.uoc_ms_confidence_workspace_bytes.restype = c_size_t
-    lib.uoc_ms_confidence.argtypes = [P, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P, P, c_size_t, P]
-    lib.uoc_ms_confidence.restype = c_int
-    lib.uoc_conf_paste.argtypes = [P, P, P, P, c_int, c_int, c_int, c_int, P, P]
-    lib.uoc_conf_paste.restype = c_int
-    lib.uoc_conf_objects.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P]
-    lib.uoc_conf_objects.restype = c_int
-    lib.uoc_normals_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.uoc_normals_workspace_bytes.restype = c_size_t
-    lib.uoc_normals.argtypes = [P, P, P] + [c_int] * 7 + [P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
-    lib.uoc_normals.restype = c_int
-    lib.uoc_lzf_decompress.argtypes = [P, c_size_t, P, c_size_t]
-    lib.uoc_lzf_decompress.restype = ctypes.c_long
-    lib.uoc_prof_enable.argtypes = [c_int]
-    lib.uoc_prof_reset.argtypes = []
-    lib.uoc_prof_report.argtypes = [ctypes.c_char_p, c_size_t]
-    for name in ("uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report"):
-        getattr(lib, name).restype = c_int
-    for name in ("uoc_ms_select_seeds", "uoc_ms_select_seeds_from", "uoc_ms_hill_climb", "uoc_ms_seed_components", "uoc_ms_assign",
-                 "uoc_ms_cluster"):
-        getattr(lib, name).restype = c_int
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 # include/uoc_hip.h: UOC_METRIC_COSINE / UOC_METRIC_EUCLIDEAN, the metric argument of the *_ex clustering calls
@@ -190,28 +133,6 @@ def metric_code(metric) -> int:
     if metric not in METRICS:
         raise NotImplementedError(f"metric={metric!r}: only 'cosine' and 'euclidean' are implemented on gfx950")
     return METRICS[metric]
-
-
-# every symbol include/uoc_hip.h declares (tests check the .so exports them all)
-EXPORTED_SYMBOLS = (
-    "uoc_version", "uoc_is_dev_build", "uoc_config_fingerprint", "uoc_shutdown", "uoc_last_error", "uoc_reload_env", "uoc_ms_set_persistent_fps", "uoc_ms_set_stream_ordering", "uoc_ms_fps_fallbacks", "uoc_ms_check", "uoc_ms_workspace_bytes", "uoc_ms_select_seeds", "uoc_ms_select_seeds_from", "uoc_ms_hill_climb",
-    "uoc_ms_seed_components", "uoc_ms_assign", "uoc_ms_cluster", "uoc_ms_workspace_bytes_wide", "uoc_ms_cluster_wide",
-) + METRIC_SYMBOLS + (
-    "uoc_net_embed_dim",
-    "uoc_net_create", "uoc_net_create_mode", "uoc_net_destroy", "uoc_net_load_param", "uoc_net_finalize", "uoc_net_workspace_bytes",
-    "uoc_net_forward", "uoc_net_set_split_precision", "uoc_conv2d_nhwc", "uoc_conv2d_nhwc_algo",
-) + TILE_SYMBOLS + (
-    "uoc_roi_workspace_bytes", "uoc_prep_rgbd", "uoc_filter_labels_depth", "uoc_roi_build", "uoc_roi_crop", "uoc_roi_match_stats",
-    "uoc_roi_paste", "uoc_roi_match", "uoc_labels_to_u8", "uoc_eval_workspace_bytes", "uoc_eval_pair_stats", "uoc_objects_workspace_bytes", "uoc_objects",
-    "uoc_track_state_bytes", "uoc_track_workspace_bytes", "uoc_track_reset", "uoc_track_step",
-    "uoc_cc_workspace_bytes", "uoc_cc_split", "uoc_plane_workspace_bytes", "uoc_support_plane",
-    "uoc_planes_workspace_bytes", "uoc_support_planes",
-    "uoc_relations_workspace_bytes", "uoc_relations", "uoc_placement_workspace_bytes", "uoc_placement",
-    "uoc_grasp_workspace_bytes", "uoc_grasp", "uoc_elevation_workspace_bytes", "uoc_elevation",
-    "uoc_footprint_workspace_bytes", "uoc_footprint", "uoc_routes_workspace_bytes", "uoc_routes",
-    "uoc_ms_confidence_workspace_bytes", "uoc_ms_confidence", "uoc_conf_paste", "uoc_conf_objects",
-    "uoc_normals_workspace_bytes", "uoc_normals", "uoc_lzf_decompress", "uoc_prof_enable", "uoc_prof_reset", "uoc_prof_report",
-)
 
 
 class RoiTable(ctypes.Structure):
@@ -396,6 +317,19 @@ def frame_inputs(who, labels, xyz):
     return as_labels(labels), xyz.to(torch.float32).contiguous()
 
 
+def grid_inputs(who, state, owner):
+    """The input check of every stage that takes the two table grids of placement.free_space: both on the GPU, [G,G]
+    batched to B = 1, square grids of equal shape on one device; else `who`'s NativeError.  Returns (state, owner) int32
+    and contiguous; a tensor that already is comes back itself."""
+    for t, what in ((state, "state"), (owner, "owner")):
+        if not on_gpu(t):
+            raise NativeError(f"{who}: {what} must be a tensor on the GPU (there is no CPU fallback)")
+    state, owner = (t[None] if t.dim() == 2 else t for t in (state, owner))
+    if state.dim() != 3 or state.shape[1] != state.shape[2] or tuple(owner.shape) != tuple(state.shape) or owner.device != state.device:
+        raise NativeError(f"{who}: state {tuple(state.shape)} and owner {tuple(owner.shape)} are not two [B,G,G] grids on one device")
+    return as_labels(state), as_labels(owner)
+
+
 def ptr(t):
     """Device (or host) pointer of a torch tensor as c_void_p; None -> NULL."""
     if t is None:
@@ -408,11 +342,45 @@ def stream_ptr(device=None):
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def call(name, device, *args, stream=True):
+    """lib().<name>(*args, current stream of `device`) under torch.cuda.device(device); a non-zero status raises NativeError
+    with uoc_last_error.  A tensor passes as its data_ptr(), None as NULL, ctypes arrays and numbers as they are.
+    stream=False: the entry point has no stream argument; device None: it does no device work either."""
+    import torch
+    fn = getattr(lib(), name)
+    args = [a.data_ptr() if hasattr(a, "data_ptr") else a for a in args]
+    if device is None:
+        rc = fn(*args)
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*args, torch.cuda.current_stream(device).cuda_stream) if stream else fn(*args)
+    check(rc, name)
+
+
+def workspace(name, device, *shape, who, hint):
+    """The scratch tensor (uint8, from torch's stream-ordered cache: no allocation in steady state) of the size the
+    *_workspace_bytes function `name` gives for `shape`; a size of 0 is `who`'s NativeError "bad shape <hint>"."""
+    import torch
+    nbytes = getattr(lib(), name)(*shape)
+    if nbytes == 0:
+        raise NativeError(f"{who}: bad shape {hint}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def host_words(rows, width):
+    """A host table of int32 records (queries, directions) as the ctypes array the h_* arguments take: len(rows) * width
+    words, at least `width` so that an empty table still has an address."""
+    flat = [int(x) for row in rows for x in row]
+    return (c_int32 * max(len(flat), width))(*flat)
+
+
 def stream_key(device):
     """(device type, index, current HIP stream handle): the key of every per-stream scratch cache, so that frames in
-    flight on different streams never share a workspace."""
+    flight on different streams never share a workspace.  A device without an index is the current one: torch.device("cuda")
+    and torch.device("cuda", current_device()) give the same key."""
     import torch
-    return (device.type, device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    index = torch.cuda.current_device() if device.index is None else device.index
+    return (device.type, index, int(torch.cuda.current_stream(device).cuda_stream))
 
 
 _retired = []
@@ -427,6 +395,27 @@ def retire(t):
         _retired.append(t)
 
 
+class PerStream:
+    """One scratch object per stream_key: get(device, need) returns the current stream's, made by make(device, need) when
+    there is none yet or, with a `size` rule, when size(object) < need; the one it replaces is retired."""
+
+    def __init__(self, make, size=None):
+        self.make, self.size, self.items = make, size, {}
+
+    def get(self, device, need=0):
+        key = stream_key(device)
+        obj = self.items.get(key)
+        if obj is None or (self.size is not None and self.size(obj) < need):
+            retire(obj)
+            obj = self.items[key] = self.make(device, need)
+        return obj
+
+    def of_device(self, device):
+        """The objects of every stream of `device`."""
+        where = stream_key(device)[:2]
+        return [obj for key, obj in self.items.items() if key[:2] == where]
+
+
 def prof_enable(on: bool):
     lib().uoc_prof_reset()
     lib().uoc_prof_enable(1 if on else 0)
@@ -436,5 +425,5 @@ def prof_report():
     """Per-kernel-class totals recorded since prof_enable(True): list of dicts."""
     import json
     buf = ctypes.create_string_buffer(1 << 19)
-    check(lib().uoc_prof_report(buf, len(buf)), "uoc_prof_report")
+    call("uoc_prof_report", None, buf, len(buf))
     return json.loads(buf.value.decode())

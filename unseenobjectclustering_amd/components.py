@@ -39,19 +39,12 @@ def split_components(labels, connectivity=8, min_area=1, mode="all"):
     lab3 = lab[None] if lab.dim() == 2 else lab
     B, H, W = (int(v) for v in lab3.shape)
     dev = lab.device
-    lib = _native.lib()
-    nbytes = lib.uoc_cc_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        raise _native.NativeError(f"split_components: bad shape B={B} H={H} W={W} (H*W must be below 2^31)")
+    ws = _native.workspace("uoc_cc_workspace_bytes", dev, B, H, W, who="split_components", hint=f"B={B} H={H} W={W} (H*W must be below 2^31)")
     out = torch.empty_like(lab3)
     table = torch.empty((B, NUM_IDS, _NF), dtype=torch.int32, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    with torch.cuda.device(dev):
-        rc = lib.uoc_cc_split(_native.ptr(lab3), B, H, W, int(connectivity), int(min_area), _native.CC_MODES[mode],
-                              _native.ptr(out), _native.ptr(table), _native.ptr(counts), _native.ptr(ws), ws.numel(),
-                              _native.stream_ptr(dev))
-    _native.check(rc, "uoc_cc_split")
+    _native.call("uoc_cc_split", dev, lab3, B, H, W, int(connectivity), int(min_area), _native.CC_MODES[mode], out, table, counts,
+                 ws, ws.numel())
     return out.view(lab.shape), table, counts
 
 

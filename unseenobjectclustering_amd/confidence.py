@@ -87,11 +87,8 @@ def assign_confidence(X, Z, seed_labels, num_unique=None) -> AssignConfidence:
     margin = torch.empty((B, n), dtype=torch.float32, device=dev)
     nws = L.uoc_ms_confidence_workspace_bytes(B, n, m, halves)
     ws = torch.empty(max(int(nws), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.uoc_ms_confidence(_native.ptr(X), halves, B, n, _native.ptr(Z), _native.ptr(sl), _native.ptr(nu), m,
-                                 _native.METRIC_COSINE, _native.ptr(labels), _native.ptr(margin), _native.ptr(second),
-                                 _native.ptr(closest), _native.ptr(rival), _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_confidence")
+    _native.call("uoc_ms_confidence", dev, X, halves, B, n, Z, sl, nu, m, _native.METRIC_COSINE, labels, margin, second, closest,
+                 rival, ws, nws)
     return AssignConfidence(labels=labels, margin=margin, second=second, closest=closest, rival=rival)
 
 
@@ -111,10 +108,7 @@ def object_stats(labels, conf, weak_q: int):
     B, H, W = labels.shape
     dev = labels.device
     stats = torch.empty((B, NUM_IDS, 4), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().uoc_conf_objects(_native.ptr(labels), _native.ptr(conf), B, H, W, int(weak_q), _native.ptr(stats),
-                                            _native.stream_ptr(dev))
-    _native.check(rc, "uoc_conf_objects")
+    _native.call("uoc_conf_objects", dev, labels, conf, B, H, W, int(weak_q), stats)
     return stats
 
 
@@ -145,10 +139,7 @@ def paste_values(values_crop, labels_crop, table, plan, K, H, W, out):
     caller) along the paint plan [K + K*128] int32 of uoc_roi_match.  No synchronisation."""
     S = int(round(values_crop.shape[-1] ** 0.5)) if values_crop.dim() == 2 else int(values_crop.shape[-1])
     dev = out.device
-    with torch.cuda.device(dev):
-        rc = _native.lib().uoc_conf_paste(_native.ptr(values_crop), _native.ptr(labels_crop), _native.ptr(table), _native.ptr(plan),
-                                          int(K), S, int(H), int(W), _native.ptr(out), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_conf_paste")
+    _native.call("uoc_conf_paste", dev, values_crop, labels_crop, table, plan, int(K), S, int(H), int(W), out)
     return out
 
 
@@ -183,7 +174,6 @@ def segment_confidence(sample, network, network_crop, return_device=False, weak=
                                   "cosine metric only, and the frame is not re-segmented with another metric"
                                   % (cfg.TRAIN.EMBEDDING_METRIC,))
     dev = TD._device()
-    L = _native.lib()
     image, depth = TD._upload([sample], dev)
     N, _, H, W = image.shape
     thr = TD.DEPTH_FILTER if depth is not None else None
@@ -198,9 +188,7 @@ def segment_confidence(sample, network, network_crop, return_device=False, weak=
     table = TD._build_rois(labels[0], zptr(0), H, W, dev, thr if thr is not None else 0.0)       # filters item 0 in place
     if N > 1 and thr is not None:
         ws = TD._ws(dev)
-        with torch.cuda.device(dev):
-            _native.check(L.uoc_filter_labels_depth(_native.ptr(labels[1:]), zptr(1), 3 * H * W, N - 1, H, W, float(thr),
-                                                    _native.ptr(ws), ws.numel(), _native.stream_ptr(dev)), "uoc_filter_labels_depth")
+        _native.call("uoc_filter_labels_depth", dev, labels[1:], zptr(1), 3 * H * W, N - 1, H, W, float(thr), ws, ws.numel())
     refined = margin = stage2 = None
     K = 0
     if network_crop is not None:
@@ -216,11 +204,7 @@ def segment_confidence(sample, network, network_crop, return_device=False, weak=
         plan = torch.empty((K + K * NUM_IDS,), dtype=torch.int32, device=dev)
         refined = torch.empty((H * W,), dtype=torch.int32, device=dev)
         status, ws = TD._status_word(dev), TD._ws(dev)
-        with torch.cuda.device(dev):
-            rc = L.uoc_roi_match(_native.ptr(labels_crop), _native.ptr(mask), _native.ptr(dep), _native.ptr(table), K, S, H, W,
-                                 _native.ptr(refined), None, _native.ptr(plan), _native.ptr(status), _native.ptr(ws), ws.numel(),
-                                 _native.stream_ptr(dev))
-        _native.check(rc, "uoc_roi_match")
+        _native.call("uoc_roi_match", dev, labels_crop, mask, dep, table, K, S, H, W, refined, None, plan, status, ws, ws.numel())
         margin = final_margin(refined, labels[0], res1.margin[0], res2.margin, labels_crop, table, plan, K, H, W).view(H, W)
         stage2 = dict(margin_crop=res2.margin, labels_crop=labels_crop, table=table, plan=plan, labels1=labels[0])
     TD._check_clustering(dev)                         # synchronises

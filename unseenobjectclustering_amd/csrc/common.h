@@ -50,6 +50,21 @@ struct EnvInt {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Carves a caller-owned workspace into arrays that start on 256-byte boundaries, in the order they are taken.  With a null
+// base it only measures: every take() is null and total() is the size the same sequence of takes needs.
+struct Carver {
+  char *base;
+  size_t off = 0;
+  explicit Carver(void *b) : base((char *)b) {}
+  template <typename T>
+  T *take(size_t count) {
+    T *p = base ? (T *)(base + off) : nullptr;
+    off += align_up(count * sizeof(T), 256);
+    return p;
+  }
+  size_t total() const { return off; }
+};
+
 // True while `st` is being captured into a hipGraph (fcn/graph_replay.py): nothing that synchronises, times or launches
 // cooperatively may run then.
 static inline bool stream_is_capturing(hipStream_t st) {
@@ -73,6 +88,15 @@ struct DeviceOnce {
   bool done() const { return (bits.load(std::memory_order_acquire) >> current_device()) & 1ull; }
   void mark() { bits.fetch_or(1ull << current_device(), std::memory_order_release); }
 };
+// Dynamic LDS above 48 KB has to be allowed per kernel and per device before the launch.  `bytes` is the most the kernel is
+// ever launched with, the same at every call that shares `once`; at or below 48 KB there is nothing to allow.  A refusal
+// goes through the error channel: the launch that would follow could only fail.
+static inline int opt_in_dynamic_lds(const void *kernel, size_t bytes, DeviceOnce &once) {
+  if (bytes <= 48 * 1024 || once.done()) return UOC_OK;
+  UOC_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  once.mark();
+  return UOC_OK;
+}
 // Compute-unit count of the current device (cached per device).
 static inline int device_num_cu() {
   static std::atomic<int> cached[kMaxDevices];

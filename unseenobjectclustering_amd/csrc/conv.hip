@@ -352,11 +352,8 @@ static int launch_glds(const ConvParams &p, hipStream_t st, int kc) {
   const int mtiles = (M + BM - 1) / BM, ntiles = p.Cout / BN;
   const size_t lds = (size_t)3 * (BM + BN) * BK * sizeof(float);
   static DeviceOnce attr_set;
-  if (!attr_set.done()) {
-    UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_glds_kernel<BM, BN, WAVES_M, WAVES_N, STEM, VARIANT>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set.mark();
-  }
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&conv_glds_kernel<BM, BN, WAVES_M, WAVES_N, STEM, VARIANT>), lds, attr_set))
+    return rc;
   const int total = mtiles * ntiles * p.G;
   hipLaunchKernelGGL((conv_glds_kernel<BM, BN, WAVES_M, WAVES_N, STEM, VARIANT>), dim3(((total + 7) / 8) * 8),
                      dim3(WAVES_M * WAVES_N * 64), lds, st, p, ntiles, mtiles);

@@ -282,21 +282,15 @@ struct Ws {
 };
 Ws carve(void *base, int B, int G) {
   Ws w;
-  char *p = (char *)base;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    char *q = p ? p + at : nullptr;
-    at += align_up(bytes, 256);
-    return q;
-  };
-  w.top = (int *)take((size_t)B * G * G * sizeof(int));
-  w.acc.cells = (int *)take((size_t)B * NUM_IDS * sizeof(int));
-  w.acc.level = (int *)take((size_t)B * NUM_IDS * sizeof(int));
-  w.acc.emax = (int *)take((size_t)B * NUM_IDS * sizeof(int));
-  w.acc.key = (unsigned long long *)take((size_t)B * NUM_IDS * sizeof(unsigned long long));
-  w.acc.sum = (unsigned long long *)take((size_t)B * NUM_IDS * sizeof(unsigned long long));
-  w.acc.qkey = (unsigned long long *)take((size_t)B * MAX_Q * sizeof(unsigned long long));
-  w.total = at;
+  Carver cv(base);
+  w.top = cv.take<int>((size_t)B * G * G);
+  w.acc.cells = cv.take<int>((size_t)B * NUM_IDS);
+  w.acc.level = cv.take<int>((size_t)B * NUM_IDS);
+  w.acc.emax = cv.take<int>((size_t)B * NUM_IDS);
+  w.acc.key = cv.take<unsigned long long>((size_t)B * NUM_IDS);
+  w.acc.sum = cv.take<unsigned long long>((size_t)B * NUM_IDS);
+  w.acc.qkey = cv.take<unsigned long long>((size_t)B * MAX_Q);
+  w.total = cv.total();
   return w;
 }
 

@@ -224,20 +224,14 @@ struct Ws {
 };
 Ws carve(void *base, int B, int G, int A, int F) {
   Ws w;
-  char *p = (char *)base;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    char *q = p ? p + at : nullptr;
-    at += align_up(bytes, 256);
-    return q;
-  };
-  w.spans = (signed char *)take((size_t)F * A * MAX_ROWS * 2);
-  w.runs = (unsigned short *)take((size_t)B * F * G * G * sizeof(unsigned short));
-  w.acc_at = at;
-  w.acc.key = (unsigned long long *)take((size_t)B * F * sizeof(unsigned long long));
-  w.acc.cells = (int *)take((size_t)B * F * sizeof(int));
-  w.acc_bytes = at - w.acc_at;
-  w.total = at;
+  Carver cv(base);
+  w.spans = cv.take<signed char>((size_t)F * A * MAX_ROWS * 2);
+  w.runs = cv.take<unsigned short>((size_t)B * F * G * G);
+  w.acc_at = cv.total();
+  w.acc.key = cv.take<unsigned long long>((size_t)B * F);
+  w.acc.cells = cv.take<int>((size_t)B * F);
+  w.acc_bytes = cv.total() - w.acc_at;
+  w.total = cv.total();
   return w;
 }
 

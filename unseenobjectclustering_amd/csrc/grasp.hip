@@ -26,7 +26,8 @@ namespace uoc {
 namespace {
 
 constexpr int SHIFT = 14;  // S = 1 << SHIFT
-constexpr int MAX_A = UOC_GRASP_MAX_DIRS, MAX_M = 8, MAX_W = 64, MAX_GAP = 4, MAX_F = 8, MAX_HP = 4;
+constexpr int MAX_A = UOC_GRASP_MAX_DIRS, MAX_M = UOC_GRASP_MAX_OFFSETS, MAX_W = UOC_GRASP_MAX_OPEN, MAX_GAP = UOC_GRASP_MAX_GAP,
+              MAX_F = UOC_GRASP_MAX_FINGER, MAX_HP = UOC_GRASP_MAX_PAD;
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int CHUNK = 8 * THREADS;     // cells per block of the moments pass
 constexpr int MOM = 4;                 // words per (frame, id) in the workspace: n, sum i, sum j, 0

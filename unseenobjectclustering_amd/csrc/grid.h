@@ -12,9 +12,9 @@
 namespace uoc {
 
 constexpr int SCALE = 16384;     // S: a unit vector's component in the frame, a direction's in the tables
-constexpr int MAX_G = 512;       // cells per side
+constexpr int MAX_G = UOC_PLACE_MAX_GRID;       // cells per side
 constexpr int IDX_MASK = 0x3FFFF;
-constexpr int MAX_ANCHOR = 4096;
+constexpr int MAX_ANCHOR = UOC_PLACE_MAX_ANCHOR;
 constexpr int PIX_WAVES = 4;             // the pixel sweep: waves per block,
 constexpr int PIX_SUB = 1024;            // pixels per wave,
 constexpr int PIX_CHUNK = PIX_WAVES * PIX_SUB;   // pixels per block

@@ -1839,24 +1839,19 @@ static int hc_blocks(int batch, int n) {
 
 static MsWorkspace carve(void *base, int batch, int n, int nh = 1) {
   MsWorkspace w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void *p = base ? (void *)((char *)base + off) : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
+  Carver cv(base);
   w.hc_nblk = hc_virtual_blocks(n);
-  w.dmin = (float *)take((size_t)batch * n * sizeof(float));
-  w.part[0] = (ArgMax *)take((size_t)batch * FPS_MAX_BLOCKS * sizeof(ArgMax));
-  w.part[1] = (ArgMax *)take((size_t)batch * FPS_MAX_BLOCKS * sizeof(ArgMax));
+  w.dmin = cv.take<float>((size_t)batch * n);
+  w.part[0] = cv.take<ArgMax>((size_t)batch * FPS_MAX_BLOCKS);
+  w.part[1] = cv.take<ArgMax>((size_t)batch * FPS_MAX_BLOCKS);
   // [batch][nblk][nh][rows][64] partial sums, then (euclidean metric) [batch][nblk][rows] weight sums
-  w.hc_partial = (float *)take((size_t)batch * w.hc_nblk * (nh * NLAB * C + NLAB) * sizeof(float));
-  w.counts = (int *)take((size_t)batch * NLAB * sizeof(int));
-  w.num_unique = (int *)take((size_t)batch * sizeof(int));
-  w.seed_labels = (int *)take((size_t)batch * NLAB * sizeof(int));
-  w.Z = (float *)take((size_t)batch * nh * NLAB * C * sizeof(float));
+  w.hc_partial = cv.take<float>((size_t)batch * w.hc_nblk * (nh * NLAB * C + NLAB));
+  w.counts = cv.take<int>((size_t)batch * NLAB);
+  w.num_unique = cv.take<int>((size_t)batch);
+  w.seed_labels = cv.take<int>((size_t)batch * NLAB);
+  w.Z = cv.take<float>((size_t)batch * nh * NLAB * C);
   w.nh = nh;
-  w.total = off;
+  w.total = cv.total();
   return w;
 }
 
@@ -1978,11 +1973,7 @@ static int run_select_seeds(const float *X, int batch, int n, int m, const int32
     // dynamic LDS at all and can share a CU with another stream's convolution blocks (two frames in flight)
     const size_t lds = (nslots > FPP_RS) ? (size_t)FPP_LS * (C / 4) * FPP_THREADS * sizeof(float4) : 0;
     static DeviceOnce attr_set[2];
-    if (!attr_set[met].done()) {
-      UOC_HIP_CHECK(hipFuncSetAttribute(fpp, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)FPP_LS * (C / 4) * FPP_THREADS * sizeof(float4))));
-      attr_set[met].mark();
-    }
+    if (int rc = opt_in_dynamic_lds(fpp, (size_t)FPP_LS * (C / 4) * FPP_THREADS * sizeof(float4), attr_set[met])) return rc;
     const float *Xc = X + (size_t)done * n * C;
     const int32_t *fc = first + done;
     float *sc = seeds + (size_t)done * m * C;
@@ -2113,7 +2104,7 @@ static HcPlan hc_make_plan(int batch, int nvb, bool splittable) {
 }
 
 template <int ST, int NH, int MET>
-static void launch_hc(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
+static int launch_hc(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
                       const MsWorkspace &w, hipStream_t st) {
   const int nvb = w.hc_nblk;
   const int last = m - 16 * (ST - 1);                  // seeds in the last tile
@@ -2125,26 +2116,17 @@ static void launch_hc(const float *X, int batch, int n, float *Z, int m, float k
     plan = hc_make_plan(batch, nvb, ST == 7 && quad);
     phys = plan.grid;
     lds = (size_t)4 * ST * 4 * 64 * sizeof(f32x4) + (MET == MS_EUCLIDEAN ? (size_t)4 * ST * 16 * sizeof(float) : 0);
-    static DeviceOnce attr_set;
-    if (!attr_set.done() && lds > 64 * 1024) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, false, MET>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if constexpr (ST >= 2)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, true, MET>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set.mark();
-    }
+    static DeviceOnce attr_set, attr_set_quad;
+    if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, false, MET>), lds, attr_set)) return rc;
+    if constexpr (ST >= 2)
+      if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&hc_iter_flat_kernel<ST, true, MET>), lds, attr_set_quad)) return rc;
   } else {                   // 128-d fields: the LDS-fragment kernel
     phys = hc_physical_blocks(batch, nvb, 2);
     const size_t zbytes = (size_t)NH * ST * 16 * ZP * sizeof(float);
     const size_t rbytes = (size_t)2 * ST * 4 * 64 * sizeof(f32x4);
     lds = zbytes > rbytes ? zbytes : rbytes;
     static DeviceOnce attr_set;
-    if (!attr_set.done() && lds > 64 * 1024) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hc_iter_kernel<ST, NH, MET>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set.mark();
-    }
+    if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&hc_iter_kernel<ST, NH, MET>), lds, attr_set)) return rc;
   }
   for (int it = 0; it < iters; ++it) {
     {
@@ -2165,13 +2147,16 @@ static void launch_hc(const float *X, int batch, int n, float *Z, int m, float k
     hipLaunchKernelGGL((hc_finalize_kernel<NH, MET>), dim3(m, batch), dim3(256), 0, st, w.hc_partial, w.hc_nblk, ST * 16,
                        m, Z);
   }
+  return UOC_OK;
 }
 
 static int run_hill_climb(const float *X, int batch, int n, float *Z, int m, float kappa, int iters,
                           const MsWorkspace &w, hipStream_t st, int met = MS_COSINE) {
+  int rc = UOC_OK;
   dispatch_shape(met, w.nh, m, [&](auto ST, auto NH, auto MET) {
-    launch_hc<ST, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st);
+    rc = launch_hc<ST, NH, MET>(X, batch, n, Z, m, kappa, iters, w, st);
   });
+  if (rc) return rc;
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -2179,19 +2164,17 @@ static int run_hill_climb(const float *X, int batch, int n, float *Z, int m, flo
 // One launch of KERNEL = assign_kernel<ST, NH, MET> or confidence_kernel<ST, NH>: outs... are the kernel's arguments
 // between labels and counts, nout the [batch][n] arrays it writes (for the profiler's byte count).
 template <auto KERNEL, int ST, int NH, class... Outs>
-static void launch_assign(int kc, int nout, const float *X, int batch, int n, const float *Z, const int *seed_labels, int m,
+static int launch_assign(int kc, int nout, const float *X, int batch, int n, const float *Z, const int *seed_labels, int m,
                           int *labels, int *counts, hipStream_t st, Outs... outs) {
   int nblk = hc_blocks(batch, n) * 2;
   const int maxb = ((n + 15) / 16 + 3) / 4;
   if (nblk > maxb) nblk = maxb;
   const size_t lds = (size_t)NH * ST * 16 * ZP * sizeof(float);
   static DeviceOnce attr_set;
-  if (!attr_set.done() && lds > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set.mark();
-  }
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(KERNEL), lds, attr_set)) return rc;
   ProfScope prof(kc, st, 2.0 * batch * m * (double)n * C * NH, 4.0 * batch * ((double)n * C * NH + (double)nout * n));
   hipLaunchKernelGGL(KERNEL, dim3(nblk, batch), dim3(HC_THREADS), lds, st, X, n, Z, seed_labels, m, labels, outs..., counts);
+  return UOC_OK;
 }
 
 // margin != null: confidence_kernel (cosine metric only), else assign_kernel and second = rival = null.
@@ -2201,15 +2184,17 @@ static int run_assign(const float *X, int nh, int batch, int n, const float *Z, 
                       int *counts, hipStream_t st, int met = MS_COSINE) {
   UOC_REQUIRE(!margin || met == MS_COSINE, "the assignment margin is built for the cosine metric only (metric = %d)", met);
   UOC_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)batch * NLAB * sizeof(int), st));
+  int rc = UOC_OK;
   dispatch_shape(met, nh, m, [&](auto ST, auto NH, auto MET) {
     if (!margin)
-      launch_assign<&assign_kernel<ST, NH, MET>, ST, NH>(KC_ASSIGN, 1, X, batch, n, Z, seed_labels, m, labels, counts, st,
+      rc = launch_assign<&assign_kernel<ST, NH, MET>, ST, NH>(KC_ASSIGN, 1, X, batch, n, Z, seed_labels, m, labels, counts, st,
                                                          closest);
     else if constexpr (MET == MS_COSINE)
-      launch_assign<&confidence_kernel<ST, NH>, ST, NH>(KC_MS_CONFIDENCE, 2 + (second ? 1 : 0) + (closest ? 1 : 0) + (rival ? 1 : 0),
+      rc = launch_assign<&confidence_kernel<ST, NH>, ST, NH>(KC_MS_CONFIDENCE, 2 + (second ? 1 : 0) + (closest ? 1 : 0) + (rival ? 1 : 0),
                                                         X, batch, n, Z, seed_labels, m, labels, counts, st, margin, second,
                                                         closest, rival);
   });
+  if (rc) return rc;
   int rb = (n + 255) / 256;
   if (rb > 512) rb = 512;
   ProfScope prof(KC_RELABEL, st, 0.0, 8.0 * batch * n * (second ? 2 : 1));
@@ -2223,14 +2208,8 @@ template <int NH, int MET>
 static int launch_seed_cc(const float *Z, int batch, int m, float eps, int *seed_labels, int *num_unique,
                           hipStream_t st) {
   const size_t lds = (size_t)NLAB * (NH * C + 1) * sizeof(float);
-  if constexpr (NH == 2) {   // more than 64 KB
-    static DeviceOnce attr_set;
-    if (!attr_set.done()) {
-      UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&seed_cc_kernel<NH, MET>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_set.mark();
-    }
-  }
+  static DeviceOnce attr_set;   // NH == 2: more than 64 KB
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&seed_cc_kernel<NH, MET>), lds, attr_set)) return rc;
   hipLaunchKernelGGL((seed_cc_kernel<NH, MET>), dim3(batch), dim3(64), lds, st, Z, m, eps, seed_labels, num_unique);
   return UOC_OK;
 }

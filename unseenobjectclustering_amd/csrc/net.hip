@@ -220,20 +220,15 @@ static NetWs carve_net(void *base, int mode, int wino_f, int B, int H, int W) {
   const int G = (mode == UOC_NET_RGBD_ADD || mode == UOC_NET_RGBD_CAT) ? 2 : 1;
   const int n_in = (G == 2 || mode == UOC_NET_RGBD_EARLY) ? 2 : 1;
   NetWs w;
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    float *p = base ? (float *)((char *)base + off) : nullptr;
-    off += align_up(floats * sizeof(float), 256);
-    return p;
-  };
-  w.in4 = take((size_t)n_in * B * H * W * 4);
-  w.stem = take((size_t)G * B * d.H1 * d.W1 * 64);
-  w.stem_part = mode == UOC_NET_RGBD_EARLY ? take((size_t)B * d.H1 * d.W1 * 64) : nullptr;
+  Carver cv(base);
+  w.in4 = cv.take<float>((size_t)n_in * B * H * W * 4);
+  w.stem = cv.take<float>((size_t)G * B * d.H1 * d.W1 * 64);
+  w.stem_part = mode == UOC_NET_RGBD_EARLY ? cv.take<float>((size_t)B * d.H1 * d.W1 * 64) : nullptr;
   size_t act = (size_t)G * B * d.H2 * d.W2 * 64;
   const size_t a3 = (size_t)G * B * d.H3 * d.W3 * 512;
   if (a3 > act) act = a3;
-  for (int i = 0; i < 4; ++i) w.buf[i] = take(act);
-  w.fc = take((size_t)G * B * d.H3 * d.W3 * 64);
+  for (int i = 0; i < 4; ++i) w.buf[i] = cv.take<float>(act);
+  w.fc = cv.take<float>((size_t)G * B * d.H3 * d.W3 * 64);
   // Winograd scratch: worst case over the layers that may use it (1/8 resolution, dilation 2 with 256 channels or
   // dilation 4 with 512 channels; also sized for 1/4 resolution x 64)
   size_t wv = 0;
@@ -244,8 +239,8 @@ static NetWs carve_net(void *base, int mode, int wino_f, int B, int H, int W) {
       if (v > wv) wv = v;
     }
   }
-  w.wino = take(wv);
-  w.total = off;
+  w.wino = cv.take<float>(wv);
+  w.total = cv.total();
   return w;
 }
 

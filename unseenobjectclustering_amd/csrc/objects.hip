@@ -34,7 +34,7 @@ constexpr int WAVES = 4;            // waves per block
 constexpr int SUB = 1024;           // pixels per wave: a wave owns a contiguous sub-chunk (16 iterations of 64 pixels)
 constexpr int CHUNK = WAVES * SUB;  // pixels per block
 constexpr int NST = 12;             // integer statistics per (frame, label), see ST_*
-constexpr int MAX_ATTR = 8;
+constexpr int MAX_ATTR = UOC_OBJECTS_MAX_ATTR;
 
 // Integer statistics: all "max" accumulators (or a count) so that zero is the neutral value of a zeroed buffer.
 enum { ST_PIX = 0, ST_X1 = 1, ST_WX = 2, ST_Y1 = 3, ST_HY = 4, ST_MAX = 5, ST_MIN = 8 };
@@ -82,24 +82,18 @@ struct Ws {
 };
 Ws carve(void *base, int B, int nch) {
   Ws w;
-  char *p = (char *)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char *r = p ? p + off : nullptr;
-    off = align_up(off + bytes, 256);
-    return r;
-  };
-  w.st = (unsigned *)take((size_t)B * NUM_IDS * NST * 4);
-  w.ext = (unsigned long long *)take((size_t)B * NUM_IDS * 6 * 8);
-  w.zero_bytes = off;
-  w.wcnt = (int *)take((size_t)B * nch * WAVES * NUM_IDS * 4);
-  w.psum = (double *)take((size_t)B * nch * NUM_IDS * 3 * 8);
-  w.pmom = (double *)take((size_t)B * nch * NUM_IDS * 6 * 8);
-  w.cent = (double *)take((size_t)B * NUM_IDS * 3 * 8);
-  w.axes = (double *)take((size_t)B * NUM_IDS * 9 * 8);
-  w.info = (int *)take((size_t)B * NUM_IDS * 4 * 4);
-  w.ftotal = (int *)take((size_t)B * 4);
-  w.total = off;
+  Carver cv(base);
+  w.st = cv.take<unsigned>((size_t)B * NUM_IDS * NST);
+  w.ext = cv.take<unsigned long long>((size_t)B * NUM_IDS * 6);
+  w.zero_bytes = cv.total();
+  w.wcnt = cv.take<int>((size_t)B * nch * WAVES * NUM_IDS);
+  w.psum = cv.take<double>((size_t)B * nch * NUM_IDS * 3);
+  w.pmom = cv.take<double>((size_t)B * nch * NUM_IDS * 6);
+  w.cent = cv.take<double>((size_t)B * NUM_IDS * 3);
+  w.axes = cv.take<double>((size_t)B * NUM_IDS * 9);
+  w.info = cv.take<int>((size_t)B * NUM_IDS * 4);
+  w.ftotal = cv.take<int>((size_t)B);
+  w.total = cv.total();
   return w;
 }
 

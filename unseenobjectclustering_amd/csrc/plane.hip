@@ -53,7 +53,7 @@ constexpr int SUB = 1024;           // pixels per wave: a wave owns a contiguous
 constexpr int CHUNK = WAVES * SUB;  // pixels per block
 constexpr int TC = 4;               // candidates per lane of the scoring kernel
 constexpr int TILE = 256 * TC;      // candidates per block of the scoring kernel
-constexpr int MAX_HYP = 1024;
+constexpr int MAX_HYP = UOC_PLANE_MAX_HYP;
 constexpr int NFR = 16;             // doubles of a frame's refined plane: normal, d, centroid, u, v, found
 enum { FR_N = 0, FR_D = 3, FR_C = 4, FR_U = 7, FR_V = 10, FR_FOUND = 13 };
 enum { K_TMAX = 0, K_TMIN = 1, K_E0 = 2, NKEY = 6 };  // max key(t), max key(-t), then max / min along e and e'
@@ -741,7 +741,7 @@ __global__ __launch_bounds__(NL) void obj_box_kernel(const double *__restrict__ 
 // Sequential extraction: rounds of hyp / score / select on a candidate list that shrinks by the winner's removal band.
 // M_r and the stop flag live on the device: a stopped frame has M = 0 from then on, so hyp_kernel writes degenerate
 // hypotheses, score_kernel's blocks exit at once and the round's winner is "not found".
-constexpr int MAX_PLANES = 8;
+constexpr int MAX_PLANES = UOC_PLANES_MAX;
 constexpr int FRINGE = 16;  // index map: FRINGE + r marks the removal band of plane r outside its inliers
 
 __device__ __forceinline__ void unpack_q(const int2 q, int &qx, int &qy, int &qz) {
@@ -978,34 +978,28 @@ struct PWs {
 };
 PWs pcarve(void *base, int B, size_t n, int nch, int num_hyp, int K) {
   PWs w;
-  char *p = (char *)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char *r = p ? p + off : nullptr;
-    off = align_up(off + bytes, 256);
-    return r;
-  };
+  Carver cv(base);
   const size_t BK = (size_t)B * K;
-  w.score = (unsigned *)take(BK * num_hyp * 4);
-  w.ocnt = (int *)take(BK * NL * 4);
-  w.okey = (unsigned long long *)take(BK * NL * NKEY * 8);
-  w.pcnt = (int *)take(BK * 4);
-  w.pext = (unsigned long long *)take(BK * 4 * 8);
-  w.zero_bytes = off;
-  w.wcnt = (int *)take((size_t)B * nch * WAVES * 4);
-  w.M = (int *)take((size_t)(K > 1 ? K + 1 : 1) * B * 4);
-  w.cand[0] = (int2 *)take((size_t)B * n * 8);
-  w.cand[1] = K > 1 ? (int2 *)take((size_t)B * n * 8) : nullptr;
-  w.hyp = (Hyp *)take((size_t)B * num_hyp * sizeof(Hyp));
-  w.win = (PWin *)take(BK * sizeof(PWin));
-  w.psum = (double *)take(BK * nch * 3 * 8);
-  w.pmom = (double *)take(BK * nch * 6 * 8);
-  w.frame = (double *)take(BK * NFR * 8);
-  w.osum = (double *)take(BK * nch * NL * 2 * 8);
-  w.omom = (double *)take(BK * nch * NL * 3 * 8);
-  w.ofoot = (double *)take(BK * NL * 2 * 8);
-  w.oaxis = (double *)take(BK * NL * 2 * 8);
-  w.total = off;
+  w.score = cv.take<unsigned>(BK * num_hyp);
+  w.ocnt = cv.take<int>(BK * NL);
+  w.okey = cv.take<unsigned long long>(BK * NL * NKEY);
+  w.pcnt = cv.take<int>(BK);
+  w.pext = cv.take<unsigned long long>(BK * 4);
+  w.zero_bytes = cv.total();
+  w.wcnt = cv.take<int>((size_t)B * nch * WAVES);
+  w.M = cv.take<int>((size_t)(K > 1 ? K + 1 : 1) * B);
+  w.cand[0] = cv.take<int2>((size_t)B * n);
+  w.cand[1] = K > 1 ? cv.take<int2>((size_t)B * n) : nullptr;
+  w.hyp = cv.take<Hyp>((size_t)B * num_hyp);
+  w.win = cv.take<PWin>(BK);
+  w.psum = cv.take<double>(BK * nch * 3);
+  w.pmom = cv.take<double>(BK * nch * 6);
+  w.frame = cv.take<double>(BK * NFR);
+  w.osum = cv.take<double>(BK * nch * NL * 2);
+  w.omom = cv.take<double>(BK * nch * NL * 3);
+  w.ofoot = cv.take<double>(BK * NL * 2);
+  w.oaxis = cv.take<double>(BK * NL * 2);
+  w.total = cv.total();
   return w;
 }
 

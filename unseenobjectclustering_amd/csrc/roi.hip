@@ -418,20 +418,15 @@ struct RoiWs {
 };
 static RoiWs carve_roi(void *base) {
   RoiWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void *p = base ? (void *)((char *)base + off) : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
-  w.stats = (int *)take(NL * NSTAT * sizeof(int));
-  w.lut = (int *)take(NL * sizeof(int));
-  w.cnt = (int *)take((size_t)NL * NL * sizeof(int));
-  w.ov = (int *)take((size_t)NL * NL * sizeof(int));     // directly behind cnt (the statistics' single fill relies on it)
-  w.keep = (int *)take((size_t)NL * NL * sizeof(int));
-  w.meanz = (float *)take(NL * sizeof(float));
-  w.plan = (int *)take((size_t)(NL + NL * NL) * sizeof(int));
-  w.total = off;
+  Carver cv(base);
+  w.stats = cv.take<int>(NL * NSTAT);
+  w.lut = cv.take<int>(NL);
+  w.cnt = cv.take<int>((size_t)NL * NL);
+  w.ov = cv.take<int>((size_t)NL * NL);     // directly behind cnt (the statistics' single fill relies on it)
+  w.keep = cv.take<int>((size_t)NL * NL);
+  w.meanz = cv.take<float>(NL);
+  w.plan = cv.take<int>((size_t)(NL + NL * NL));
+  w.total = cv.total();
   return w;
 }
 

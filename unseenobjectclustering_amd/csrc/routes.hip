@@ -347,19 +347,13 @@ struct Ws {
 };
 Ws carve(void *base, int B, int G, int Q) {
   Ws w;
-  char *p = (char *)base;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    char *q = p ? p + at : nullptr;
-    at += align_up(bytes, 256);
-    return q;
-  };
+  Carver cv(base);
   w.sweeps_bytes = (size_t)B * Q * sizeof(int);
-  w.sweeps = (int *)take(w.sweeps_bytes);
-  w.runs = (unsigned short *)take((size_t)B * Q * G * G * sizeof(unsigned short));
-  w.pass = (unsigned char *)take((size_t)B * Q * G * G);
-  w.field = (unsigned *)take(field_mode(G) == FIELD_LDS32 ? 0 : (size_t)B * Q * (G + 2) * pitch32(G) * sizeof(unsigned));
-  w.total = at;
+  w.sweeps = cv.take<int>((size_t)B * Q);
+  w.runs = cv.take<unsigned short>((size_t)B * Q * G * G);
+  w.pass = cv.take<unsigned char>((size_t)B * Q * G * G);
+  w.field = cv.take<unsigned>(field_mode(G) == FIELD_LDS32 ? 0 : (size_t)B * Q * (G + 2) * pitch32(G));
+  w.total = cv.total();
   return w;
 }
 
@@ -421,11 +415,7 @@ int uoc_routes(const int32_t *d_state, const int32_t *d_owner, const int64_t *d_
   const int cells = G * G, mode = field_mode(G);
   const size_t lds = mode == FIELD_LDS32 ? (size_t)(G + 2) * pitch32(G) * 4 : mode == FIELD_LDS16 ? (size_t)(G + 2) * pitch16(G) * 2 : 0;
   static DeviceOnce attr_set;
-  if (!attr_set.done()) {
-    UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      LDS_FIELD_BYTES));
-    attr_set.mark();
-  }
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&solve_kernel), LDS_FIELD_BYTES, attr_set)) return rc;
   hipStream_t st = (hipStream_t)stream;
   {
     ProfScope prof(KC_ROUTES_TABLES, st, 0.0, (double)B * cells * (8.0 + 5.0 * NM));

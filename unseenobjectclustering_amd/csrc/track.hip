@@ -368,11 +368,7 @@ int uoc_track_step(const int32_t *d_labels, int B, int H, int W, int q, int max_
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)CONT_WORDS * 4 + (size_t)CONT_WORDS * 2;
   static DeviceOnce attr_set;
-  if (!attr_set.done()) {
-    UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&match_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set.mark();
-  }
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&match_kernel), lds, attr_set)) return rc;
   const bool vec = n % 4 == 0 && (((uintptr_t)d_labels | (uintptr_t)d_out) & 15) == 0;
   int blocks = (n + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK;
   if (blocks > MAX_BLOCKS) blocks = MAX_BLOCKS;

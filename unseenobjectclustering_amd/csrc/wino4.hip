@@ -403,11 +403,7 @@ static int launch_wino4_gemm_t(const float *V, const float *U, float *Mo, int NT
   static_assert((size_t)NSTAGE * (BM + BN) * W4BK * sizeof(float) <= 160 * 1024, "LDS ring too large");
   UOC_REQUIRE(!PAIR || (Cin / W4BK) % 2 == 0, "winograd F(4x4): the pair loop needs an even number of 32-channel chunks");
   static DeviceOnce attr_set;
-  if (!attr_set.done()) {
-    UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&wino4_gemm_kernel<BM, BN, PAIR, NW>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set.mark();
-  }
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&wino4_gemm_kernel<BM, BN, PAIR, NW>), lds, attr_set)) return rc;
   hipLaunchKernelGGL((wino4_gemm_kernel<BM, BN, PAIR, NW>), dim3(nblocks), dim3(NW * 64), lds, st, V, U, Mo, NT, Cin, Cout, planes,
                      mtiles, nt_shift);
   UOC_LAUNCH_CHECK();

@@ -413,11 +413,7 @@ static int launch_gemm3_t(const unsigned short *V3, const unsigned short *U3, fl
   UOC_REQUIRE((1 << nt_shift) == ntiles, "winograd F(4x4) bf16x3: Cout / %d = %d is not a power of two", BN, ntiles);
   const size_t lds = (size_t)3 * 3 * (BM + BN) * 64;
   static DeviceOnce attr_set;
-  if (!attr_set.done()) {
-    UOC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&wino4_gemm3_kernel<BM, BN>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set.mark();
-  }
+  if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&wino4_gemm3_kernel<BM, BN>), lds, attr_set)) return rc;
   hipLaunchKernelGGL((wino4_gemm3_kernel<BM, BN>), dim3(nblocks), dim3(512), lds, st, V3, U3, Mo, NT, Cin, Cout, planes, mtiles,
                      nt_shift);
   UOC_LAUNCH_CHECK();

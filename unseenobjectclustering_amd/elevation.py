@@ -20,7 +20,6 @@ the host nor synchronises.  No CPU fallback."""
 from __future__ import annotations
 
 import collections
-import ctypes
 
 import numpy as np
 import torch
@@ -50,30 +49,15 @@ def elevation_records(labels, xyz, frame, grid, cell_mm, tau_mm, step_mm, min_pt
     B, H, W = (int(v) for v in labels.shape)
     G, Q = int(grid), len(queries)
     dev = labels.device
-    lib = _native.lib()
-    nws = lib.uoc_elevation_workspace_bytes(B, H, W, G)
-    if nws == 0:
-        raise _native.NativeError(f"heights: bad shape B={B} H={H} W={W} or grid={G} (a multiple of 8 in 8..{_native.PLACE_MAX_GRID})")
+    ws = _native.workspace("uoc_elevation_workspace_bytes", dev, B, H, W, G, who="heights", hint=f"B={B} H={H} W={W} or {placement.grid_hint(G)}")
     elev, owner, pts, near, dist2 = (torch.empty((B, G, G), dtype=torch.int32, device=dev) for _ in range(5))
     tops = torch.empty((B, NUM_IDS, 8), dtype=torch.int32, device=dev)
     info = torch.empty((B, 4), dtype=torch.int32, device=dev)
     answers = torch.empty((B, Q, 4), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    hq = (ctypes.c_int32 * (4 * max(Q, 1)))(*[int(x) for q in queries for x in q])
-    with torch.cuda.device(dev):
-        rc = lib.uoc_elevation(_native.ptr(labels), _native.ptr(xyz), _native.ptr(frame), B, H, W, G, int(cell_mm), int(tau_mm),
-                               int(step_mm), int(min_pts), ctypes.cast(hq, ctypes.c_void_p) if Q else None, Q, _native.ptr(elev),
-                               _native.ptr(owner), _native.ptr(pts), _native.ptr(near), _native.ptr(dist2), _native.ptr(tops),
-                               _native.ptr(info), _native.ptr(answers) if Q else None, _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_elevation")
+    _native.call("uoc_elevation", dev, labels, xyz, frame, B, H, W, G, int(cell_mm), int(tau_mm), int(step_mm), int(min_pts),
+                 _native.host_words(queries, 4) if Q else None, Q, elev, owner, pts, near, dist2, tops, info,
+                 answers if Q else None, ws, ws.numel())
     return elev, owner, pts, near, dist2, tops, info, answers
-
-
-def _mm(value, name):
-    mm = int(round(float(value) * 1000))
-    if not 1 <= mm <= _native.PLACE_MAX_MM:
-        raise ValueError(f"{name} = {value} m is {mm} mm, outside 1..{_native.PLACE_MAX_MM} mm")
-    return mm
 
 
 def _check_queries(queries):
@@ -93,13 +77,10 @@ def heights(labels, xyz, placed, step=0.005, min_pts=2, queries=None) -> Elevati
     on the device), grid, cell_mm and tau_mm are used, so that the two grids coincide cell for cell.  step: metres, used
     in whole millimetres (1..1000); min_pts in 1..65535; queries: up to 16 (need2, id, hmin_mm, hmax_mm) from on_top().
     Returns an ElevationResult."""
-    step_mm = _mm(step, "step")
-    if not 1 <= int(min_pts) <= _native.PLACE_MAX_MIN_PTS:
-        raise ValueError(f"min_pts = {min_pts} outside 1..{_native.PLACE_MAX_MIN_PTS}")
+    step_mm = placement.millimetres(step, "step")
+    placement.check_min_pts(min_pts)
     qs = _check_queries(queries)
-    G, cell_mm, tau_mm = int(placed.grid), int(placed.cell_mm), int(placed.tau_mm)
-    if not (8 <= G <= _native.PLACE_MAX_GRID and G % 8 == 0):
-        raise ValueError(f"grid = {G} is not a multiple of 8 in 8..{_native.PLACE_MAX_GRID}")
+    G, cell_mm, tau_mm = placement.check_grid(int(placed.grid)), int(placed.cell_mm), int(placed.tau_mm)
     for mm, name in ((cell_mm, "cell_mm"), (tau_mm, "tau_mm")):
         if not 1 <= mm <= _native.PLACE_MAX_MM:
             raise ValueError(f"{name} = {mm} outside 1..{_native.PLACE_MAX_MM} mm")

@@ -31,7 +31,6 @@ PAD_FRACTION = 0.25   # :66
 DEPTH_FILTER = 0.8    # :252
 MAX_LABELS = 128
 
-_roi_ws = {}
 LAST_FRAME_STATS = {"rois": 0}      # number of stage-1 ROIs of the most recent frame (measurement bookkeeping)
 
 
@@ -43,11 +42,8 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _ws(dev):
-    key = _native.stream_key(dev)      # one scratch buffer per stream: two frames in flight must not share it
-    if key not in _roi_ws:
-        _roi_ws[key] = torch.empty(_native.lib().uoc_roi_workspace_bytes() + 256, dtype=torch.uint8, device=dev)
-    return _roi_ws[key]
+# one scratch buffer per stream: two frames in flight must not share it
+_ws = _native.PerStream(lambda dev, _: torch.empty(_native.lib().uoc_roi_workspace_bytes() + 256, dtype=torch.uint8, device=dev)).get
 
 
 def _pixel_major(features: torch.Tensor) -> torch.Tensor:
@@ -113,13 +109,8 @@ def filter_labels_depth(labels, depth, threshold):
     lab = _labels_to_device(labels, dev).clone()
     d = depth.to(dev).float().contiguous()
     B, H, W = lab.shape
-    L = _native.lib()
     ws = _ws(dev)
-    zptr = ctypes.c_void_p(d.data_ptr() + 2 * H * W * 4)
-    with torch.cuda.device(dev):
-        rc = L.uoc_filter_labels_depth(_native.ptr(lab), zptr, 3 * H * W, B, H, W, float(threshold), _native.ptr(ws),
-                                       ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_filter_labels_depth")
+    _native.call("uoc_filter_labels_depth", dev, lab, d.data_ptr() + 2 * H * W * 4, 3 * H * W, B, H, W, float(threshold), ws, ws.numel())
     return lab.to(labels.dtype).to(labels.device)
 
 
@@ -130,18 +121,13 @@ def _read_table(table_dev: torch.Tensor) -> _native.RoiTable:
 
 def _check_clustering(dev):
     """Raise if a clustering launch since the last check reported a timed-out grid exchange (uoc_ms_check)."""
-    with torch.cuda.device(dev):
-        _native.check(_native.lib().uoc_ms_check(_native.stream_ptr(dev)), "uoc_ms_check")
+    _native.call("uoc_ms_check", dev)
 
 
 def _build_rois(lab0: torch.Tensor, z_plane_ptr, H, W, dev, threshold=DEPTH_FILTER):
-    L = _native.lib()
     table = torch.empty(_native.ROI_TABLE_BYTES, dtype=torch.uint8, device=dev)
     ws = _ws(dev)
-    with torch.cuda.device(dev):
-        rc = L.uoc_roi_build(_native.ptr(lab0), z_plane_ptr, H, W, float(threshold), PAD_FRACTION, _native.ptr(table),
-                             _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_roi_build")
+    _native.call("uoc_roi_build", dev, lab0, z_plane_ptr, H, W, float(threshold), PAD_FRACTION, table, ws, ws.numel())
     return table
 
 
@@ -156,14 +142,9 @@ def _crop(rgb, depth, lab0, table, K, H, W, dev, out=None):
     """The K ROI crops of one image -> (rgb_crops, mask_crops, depth_crops): new tensors, or the views `out` (same order)
     of a batch that holds the crops of several images."""
     S = cfg.TRAIN.SYN_CROP_SIZE
-    L = _native.lib()
     rgb_crops, mask_crops, depth_crops = out = out if out is not None else _crop_buffers(K, depth is not None, dev)
     if K > 0:
-        with torch.cuda.device(dev):
-            rc = L.uoc_roi_crop(_native.ptr(rgb), _native.ptr(depth), _native.ptr(lab0), H, W, _native.ptr(table), K, S,
-                                _native.ptr(rgb_crops), _native.ptr(depth_crops), _native.ptr(mask_crops),
-                                _native.stream_ptr(dev))
-        _native.check(rc, "uoc_roi_crop")
+        _native.call("uoc_roi_crop", dev, rgb, depth, lab0, H, W, table, K, S, rgb_crops, depth_crops, mask_crops)
     return out
 
 
@@ -212,38 +193,25 @@ class _HostMirror:
         self.stage2_done = torch.cuda.Event(blocking=blocking)
 
 
-_mirrors = {}
-
-
-def _mirror(dev, frames=1) -> _HostMirror:
-    key = _native.stream_key(dev)
-    if key not in _mirrors or _mirrors[key].frames < frames:
-        _mirrors[key] = _HostMirror(frames)
-    return _mirrors[key]
+_mirror = _native.PerStream(lambda dev, frames: _HostMirror(frames), size=lambda m: m.frames).get
 
 
 def _match_stats(labels_crop_i32, mask_crops, depth_crops, K, dev):
     """Overlap / mean-depth statistics of the K clustered crops (:118-148), one launch over all ROIs.
     Returns the device buffer [K*128 keep flags | K mean depths]."""
     S = cfg.TRAIN.SYN_CROP_SIZE
-    L = _native.lib()
     ws = _ws(dev)
     # keep table and mean depths share one buffer (one D2H), paint order and id map another (one H2D)
     stats = torch.empty((K * MAX_LABELS + K,), dtype=torch.int32, device=dev)
     keep = stats[:K * MAX_LABELS].view(K, MAX_LABELS)
     meanz = stats[K * MAX_LABELS:].view(torch.float32) if depth_crops is not None else None
-    with torch.cuda.device(dev):
-        rc = L.uoc_roi_match_stats(_native.ptr(labels_crop_i32), _native.ptr(mask_crops), _native.ptr(depth_crops), K, S,
-                                   _native.ptr(keep), _native.ptr(meanz), _native.ptr(ws), ws.numel(),
-                                   _native.stream_ptr(dev))
-    _native.check(rc, "uoc_roi_match_stats")
+    _native.call("uoc_roi_match_stats", dev, labels_crop_i32, mask_crops, depth_crops, K, S, keep, meanz, ws, ws.numel())
     return stats
 
 
 def _paste(labels_crop_i32, table_dev, table_host, stats_h, has_depth, K, H, W, dev):
     """Host ordering of the ROIs (:129-151) from the statistics read back, then one paste launch (:156-177)."""
     S = cfg.TRAIN.SYN_CROP_SIZE
-    L = _native.lib()
     keep_h = stats_h[:K * MAX_LABELS].view(K, MAX_LABELS).numpy()
     if has_depth:
         sort_key = stats_h[K * MAX_LABELS:K * MAX_LABELS + K].view(torch.float32)
@@ -255,23 +223,14 @@ def _paste(labels_crop_i32, table_dev, table_host, stats_h, has_depth, K, H, W, 
     plan = torch.from_numpy(flat).to(dev)
     order_d, map_d = plan[:K], plan[K:]
     refined = torch.empty((H * W,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.uoc_roi_paste(_native.ptr(labels_crop_i32), _native.ptr(table_dev), _native.ptr(map_d), _native.ptr(order_d),
-                             K, S, H, W, _native.ptr(refined), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_roi_paste")
+    _native.call("uoc_roi_paste", dev, labels_crop_i32, table_dev, map_d, order_d, K, S, H, W, refined)
     return refined
 
 
-_order_status = {}
-
-
-def _status_word(dev) -> torch.Tensor:
-    """Per-stream sticky device flag of uoc_roi_match (bit 0: NaN sort keys with >= 64 ROIs — the one ordering case the
-    device kernel does not restate; the caller then orders on the host)."""
-    key = _native.stream_key(dev)
-    if key not in _order_status:
-        _order_status[key] = torch.zeros(1, dtype=torch.int32, device=dev)
-    return _order_status[key]
+# Per-stream sticky device flag of uoc_roi_match (bit 0: NaN sort keys with >= 64 ROIs — the one ordering case the device
+# kernel does not restate; the caller then orders on the host).
+_order_status = _native.PerStream(lambda dev, _: torch.zeros(1, dtype=torch.int32, device=dev))
+_status_word = _order_status.get
 
 
 def _match_device(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, dev, want_keep=False):
@@ -279,16 +238,12 @@ def _match_device(labels_crop_i32, mask_crops, depth_crops, table, K, H, W, dev,
     sorted(reverse=True) semantics restated on the device), renumbering and paste in one call (uoc_roi_match).
     -> refined int32 [H*W] (device), keep table [K,128] (device) or None."""
     S = cfg.TRAIN.SYN_CROP_SIZE
-    L = _native.lib()
     ws = _ws(dev)
     refined = torch.empty((H * W,), dtype=torch.int32, device=dev)
     keep = torch.empty((K, MAX_LABELS), dtype=torch.int32, device=dev) if want_keep else None
     status = _status_word(dev)
-    with torch.cuda.device(dev):
-        rc = L.uoc_roi_match(_native.ptr(labels_crop_i32), _native.ptr(mask_crops), _native.ptr(depth_crops), _native.ptr(table),
-                             K, S, H, W, _native.ptr(refined), _native.ptr(keep), None, _native.ptr(status), _native.ptr(ws),
-                             ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_roi_match")
+    _native.call("uoc_roi_match", dev, labels_crop_i32, mask_crops, depth_crops, table, K, S, H, W, refined, keep, None, status, ws,
+                 ws.numel())
     return refined, keep
 
 
@@ -304,7 +259,7 @@ def _finish_block(dev):
     """End of a block of frames whose per-frame checks were deferred (the frame-parallel runner): the clustering status
     (uoc_ms_check) and the ordering flag of every stream of `dev`."""
     _check_clustering(dev)
-    flags = [_take_order_flag(status) for key, status in _order_status.items() if key[:2] == (dev.type, dev.index)]
+    flags = [_take_order_flag(status) for status in _order_status.of_device(dev)]
     if any(flags):
         raise HostOrderNeeded("a frame had NaN ROI sort keys with >= 64 ROIs: re-run with the ROI ordering on the host")
 
@@ -404,11 +359,8 @@ def _stage1_launches(network, image, depth, firsts, thr, label=None, refine=None
     zptr = lambda f: ctypes.c_void_p(depth.data_ptr() + ((3 * f + 2) * H * W) * 4 if thr is not None else 0)   # z plane of item f
     tables = [_build_rois(labels[f], zptr(f), H, W, dev, thr if thr is not None else 0.0) for f in range(R)]
     if R < N and thr is not None:
-        L, ws = _native.lib(), _ws(dev)
-        with torch.cuda.device(dev):
-            _native.check(L.uoc_filter_labels_depth(_native.ptr(labels[R:]), zptr(R), 3 * H * W, N - R, H, W, float(thr),
-                                                    _native.ptr(ws), ws.numel(), _native.stream_ptr(dev)),
-                          "uoc_filter_labels_depth")
+        ws = _ws(dev)
+        _native.call("uoc_filter_labels_depth", dev, labels[R:], zptr(R), 3 * H * W, N - R, H, W, float(thr), ws, ws.numel())
     return labels, tables
 
 

@@ -15,7 +15,6 @@ being moved does not block itself).  Integer arithmetic in HIP kernels: defined 
 batch.  `fit` neither copies to the host nor synchronises.  No CPU fallback."""
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -66,18 +65,18 @@ def footprint_records(state, owner, dist2, frame, dirs, rects, unknown_blocks):
     """The raw uoc_footprint call on bare grids: (fits [B,F,G,G], count [B,F,32], best [B,F,8]) int32 on the device, no
     synchronisation.  state, owner, dist2: device tensors [B,G,G] or [G,G] of any integer type and layout (they are made
     int32 and contiguous); frame: [B,16] int64 on the device, or None; dirs: [A,2] integers in -S..S; rects: [F,8]."""
-    for t, what in ((state, "state"), (owner, "owner"), (dist2, "dist2")):
-        if not _native.on_gpu(t):
-            raise _native.NativeError(f"footprint: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    state, owner, dist2 = (t[None] if t.dim() == 2 else t for t in (state, owner, dist2))
-    if state.dim() != 3 or state.shape[1] != state.shape[2] or any(tuple(t.shape) != tuple(state.shape) or t.device != state.device
-                                                                     for t in (owner, dist2)):
-        raise _native.NativeError(f"footprint: state {tuple(state.shape)}, owner {tuple(owner.shape)} and dist2 {tuple(dist2.shape)} "
+    if not _native.on_gpu(dist2):
+        raise _native.NativeError("footprint: dist2 must be a tensor on the GPU (there is no CPU fallback)")
+    st, ow = _native.grid_inputs("footprint", state, owner)
+    d2 = _native.as_labels(dist2[None] if dist2.dim() == 2 else dist2)
+    if tuple(d2.shape) != tuple(st.shape) or d2.device != st.device:
+        raise _native.NativeError(f"footprint: state {tuple(st.shape)}, owner {tuple(ow.shape)} and dist2 {tuple(d2.shape)} "
                                   "are not three [B,G,G] grids on one device")
-    B, G = int(state.shape[0]), int(state.shape[1])
+    B, G = int(st.shape[0]), int(st.shape[1])
+    dev = st.device
     if frame is not None:
-        if not (isinstance(frame, torch.Tensor) and frame.device == state.device and frame.dtype == torch.int64 and tuple(frame.shape) == (B, 16)):
-            raise _native.NativeError(f"footprint: the frame records do not match the {B} frames on {state.device}")
+        if not (isinstance(frame, torch.Tensor) and frame.device == dev and frame.dtype == torch.int64 and tuple(frame.shape) == (B, 16)):
+            raise _native.NativeError(f"footprint: the frame records do not match the {B} frames on {dev}")
         frame = frame.contiguous()
     d = np.ascontiguousarray(np.asarray(dirs, dtype=np.int64))
     if d.ndim != 2 or d.shape[1] != 2:
@@ -89,23 +88,12 @@ def footprint_records(state, owner, dist2, frame, dirs, rects, unknown_blocks):
         raise ValueError(f"dirs has a component outside -{_native.GRASP_SCALE}..{_native.GRASP_SCALE}")
     r = _check_rects(rects)
     F = len(r)
-    dev = state.device
-    lib = _native.lib()
-    nws = lib.uoc_footprint_workspace_bytes(B, G, A, F)
-    if nws == 0:
-        raise _native.NativeError(f"footprint: bad shape B={B} or grid={G} (a multiple of 8 in 8..{_native.PLACE_MAX_GRID})")
-    st, ow, d2 = (t.to(torch.int32).contiguous() for t in (state, owner, dist2))
+    ws = _native.workspace("uoc_footprint_workspace_bytes", dev, B, G, A, F, who="footprint", hint=f"B={B} or {placement.grid_hint(G)}")
     fits = torch.empty((B, F, G, G), dtype=torch.int32, device=dev)
     count = torch.empty((B, F, 32), dtype=torch.int32, device=dev)
     best = torch.empty((B, F, 8), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    hd = (ctypes.c_int32 * (2 * A))(*[int(x) for x in d.reshape(-1)])
-    hr = (ctypes.c_int32 * (8 * F))(*[int(x) for x in r.reshape(-1)])
-    with torch.cuda.device(dev):
-        rc = lib.uoc_footprint(_native.ptr(st), _native.ptr(ow), _native.ptr(d2), _native.ptr(frame) if frame is not None else None, B, G,
-                               ctypes.cast(hd, ctypes.c_void_p), A, ctypes.cast(hr, ctypes.c_void_p), F, 1 if unknown_blocks else 0,
-                               _native.ptr(fits), _native.ptr(count), _native.ptr(best), _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_footprint")
+    _native.call("uoc_footprint", dev, st, ow, d2, frame, B, G, _native.host_words(d, 2), A, _native.host_words(r, 8), F,
+                 1 if unknown_blocks else 0, fits, count, best, ws, ws.numel())
     return fits, count, best
 
 

@@ -16,7 +16,6 @@ there (`w` cells), whether another object or the grid's border lies between the 
 neither copies to the host nor synchronises.  No CPU fallback."""
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -77,15 +76,7 @@ def grasp_records(state, owner, dirs, offsets, max_open, gap, finger, pad, unkno
     """The raw uoc_grasp call on bare grids: (cand [B,128,A,2M+1,2], best [B,128,8]) int32 on the device, no
     synchronisation.  state, owner: device tensors [B,G,G] or [G,G] of any integer type and layout (they are made int32
     and contiguous); dirs: [A,2] integers in -S..S; the other parameters in cells."""
-    for t, what in ((state, "state"), (owner, "owner")):
-        if not _native.on_gpu(t):
-            raise _native.NativeError(f"grasp: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    if state.dim() == 2:
-        state = state[None]
-    if owner.dim() == 2:
-        owner = owner[None]
-    if state.dim() != 3 or state.shape[1] != state.shape[2] or tuple(owner.shape) != tuple(state.shape) or owner.device != state.device:
-        raise _native.NativeError(f"grasp: state {tuple(state.shape)} and owner {tuple(owner.shape)} are not two [B,G,G] grids on one device")
+    st, ow = _native.grid_inputs("grasp", state, owner)
     d = np.ascontiguousarray(np.asarray(dirs, dtype=np.int64))
     if d.ndim != 2 or d.shape[1] != 2:
         raise ValueError(f"dirs has shape {d.shape}, not [A,2]")
@@ -93,23 +84,13 @@ def grasp_records(state, owner, dirs, offsets, max_open, gap, finger, pad, unkno
     _check_cells(A, M, Wmax, gap, F, Hp)
     if np.abs(d).max() > _native.GRASP_SCALE:
         raise ValueError(f"dirs has a component outside -{_native.GRASP_SCALE}..{_native.GRASP_SCALE}")
-    B, G = int(state.shape[0]), int(state.shape[1])
-    dev = state.device
-    lib = _native.lib()
-    nws = lib.uoc_grasp_workspace_bytes(B, G, A, M)
-    if nws == 0:
-        raise _native.NativeError(f"grasp: bad shape B={B} or grid={G} (a multiple of 8 in 8..{_native.PLACE_MAX_GRID})")
-    st = state.to(torch.int32).contiguous()
-    ow = owner.to(torch.int32).contiguous()
+    B, G = int(st.shape[0]), int(st.shape[1])
+    dev = st.device
+    ws = _native.workspace("uoc_grasp_workspace_bytes", dev, B, G, A, M, who="grasp", hint=f"B={B} or {placement.grid_hint(G)}")
     cand = torch.empty((B, NUM_IDS, A, 2 * M + 1, 2), dtype=torch.int32, device=dev)
     best = torch.empty((B, NUM_IDS, 8), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    hd = (ctypes.c_int32 * (2 * A))(*[int(x) for x in d.reshape(-1)])
-    with torch.cuda.device(dev):
-        rc = lib.uoc_grasp(_native.ptr(st), _native.ptr(ow), B, G, ctypes.cast(hd, ctypes.c_void_p), A, M, Wmax, gap, F, Hp,
-                           1 if unknown_blocks else 0, _native.ptr(cand), _native.ptr(best), _native.ptr(ws), nws,
-                           _native.stream_ptr(dev))
-    _native.check(rc, "uoc_grasp")
+    _native.call("uoc_grasp", dev, st, ow, B, G, _native.host_words(d, 2), A, M, Wmax, gap, F, Hp, 1 if unknown_blocks else 0,
+                 cand, best, ws, ws.numel())
     return cand, best
 
 

@@ -87,9 +87,6 @@ def prepare_on_device(sample, device, out=None):
         image = torch.empty((1, 3, H, W), dtype=torch.float32, device=device)
         xyz = torch.empty((1, 3, H, W), dtype=torch.float32, device=device)
     f32 = lambda v: float(np.float32(v))
-    with torch.cuda.device(device):
-        rc = _native.lib().uoc_prep_rgbd(_native.ptr(bgr), _native.ptr(dep), H, W, f32(cam["fx"]), f32(cam["fy"]),
-                                         f32(cam["x_offset"]), f32(cam["y_offset"]), float(mean[0]), float(mean[1]),
-                                         float(mean[2]), _native.ptr(image), _native.ptr(xyz), _native.stream_ptr(device))
-    _native.check(rc, "uoc_prep_rgbd")
+    _native.call("uoc_prep_rgbd", device, bgr, dep, H, W, f32(cam["fx"]), f32(cam["fy"]), f32(cam["x_offset"]), f32(cam["y_offset"]),
+                 float(mean[0]), float(mean[1]), float(mean[2]), image, xyz)
     return {"image_color": image, "depth": xyz}

@@ -108,8 +108,7 @@ class SEGNET(nn.Module):
         products, fp32 accumulation; csrc/wino4_split.hip).  Not bit-identical to the fp32 path; reported under its own key."""
         self.split_precision = bool(on)
         if self._handle is not None:
-            with torch.cuda.device(self._handle_device):
-                _native.check(_native.lib().uoc_net_set_split_precision(self._handle, 1 if on else 0), "uoc_net_set_split_precision")
+            _native.call("uoc_net_set_split_precision", self._handle_device, self._handle, 1 if on else 0, stream=False)
             self._native_gen += 1         # captured graphs bake the launch sequence
         return self
 
@@ -123,18 +122,16 @@ class SEGNET(nn.Module):
         self._release()
         L = _native.lib()
         h = ctypes.c_void_p()
-        _native.check(L.uoc_net_create_mode(ctypes.byref(h), _MODE_ID[self.mode]), "uoc_net_create_mode")
+        _native.call("uoc_net_create_mode", None, ctypes.byref(h), _MODE_ID[self.mode])
         for key, t in self.state_dict().items():
             if key.endswith("num_batches_tracked"):
                 continue
             ht = t.detach().to("cpu", torch.float32).contiguous()
             _native.check(L.uoc_net_load_param(h, key.encode(), ctypes.c_void_p(ht.data_ptr()), ht.numel()),
                           f"uoc_net_load_param({key})")
-        with torch.cuda.device(device):
-            _native.check(L.uoc_net_finalize(h), "uoc_net_finalize")
+        _native.call("uoc_net_finalize", device, h, stream=False)
         if getattr(self, "split_precision", False):
-            with torch.cuda.device(device):
-                _native.check(L.uoc_net_set_split_precision(h, 1), "uoc_net_set_split_precision")
+            _native.call("uoc_net_set_split_precision", device, h, 1, stream=False)
         self._handle = h
         self._handle_device = device
         self._native_gen = getattr(self, "_native_gen", 0) + 1
@@ -161,10 +158,7 @@ class SEGNET(nn.Module):
         embed = torch.empty((B, 2, H * W, 64) if cat else (B, H * W, 64), dtype=torch.float32, device=dev)
         nbytes = L.uoc_net_workspace_bytes(self._handle, B, H, W)
         ws = _net_workspace(dev, nbytes)
-        with torch.cuda.device(dev):
-            rc = L.uoc_net_forward(self._handle, _native.ptr(img), _native.ptr(depth), B, H, W, _native.ptr(embed),
-                                   _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-        _native.check(rc, "uoc_net_forward")
+        _native.call("uoc_net_forward", dev, self._handle, img, depth, B, H, W, embed, ws, ws.numel())
         if cat:
             # [B,128,H,W] like SEG.py:110 (a copy: the kernels keep 128-d fields as two 64-channel planes);
             # the plane tensor rides along so that clustering_features consumes it without converting back
@@ -180,17 +174,9 @@ class SEGNET(nn.Module):
         return [p for n, p in self.named_parameters() if "bias" in n]
 
 
-_net_ws = {}
-
-
-def _net_workspace(device, nbytes):
-    key = _native.stream_key(device)      # one activation arena per stream (frames in flight do not share it)
-    ws = _net_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _native.retire(ws)          # a captured hipGraph may have baked the old arena's address
-        ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
-        _net_ws[key] = ws
-    return ws
+# one activation arena per stream (frames in flight do not share it)
+_net_workspace = _native.PerStream(lambda device, nbytes: torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device),
+                                   size=torch.Tensor.numel).get
 
 
 def update_model(model, data):

@@ -72,21 +72,12 @@ def normals_records(xyz, labels, planes, step, window, jump_mm, min_pairs, dirs,
         raise ValueError(f"{A} directions outside 1..{_native.NORMALS_MAX_DIRS}")
     if np.abs(d).max() > _native.PLACE_SCALE:
         raise ValueError(f"dirs has a component outside -{_native.PLACE_SCALE}..{_native.PLACE_SCALE}")
-    lib = _native.lib()
-    nws = lib.uoc_normals_workspace_bytes(B, H, W)
-    if nws == 0:
-        raise _native.NativeError(f"normals: bad shape B={B} H={H} W={W}")
+    ws = _native.workspace("uoc_normals_workspace_bytes", dev, B, H, W, who="normals", hint=f"B={B} H={H} W={W}")
     packed = torch.empty((B, H, W, 4), dtype=torch.int32, device=dev)
     un = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if unit else None
     faces = torch.empty((B, NUM_IDS, FACE_WORDS), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    hd = (ctypes.c_int32 * (2 * A))(*[int(x) for x in d.reshape(-1)])
-    with torch.cuda.device(dev):
-        rc = lib.uoc_normals(_native.ptr(xyz), _native.ptr(labels), _native.ptr(planes), B, H, W, int(step), int(window),
-                             int(jump_mm), int(min_pairs), ctypes.cast(hd, ctypes.c_void_p), A, int(c_up), int(s_side),
-                             _native.ptr(packed), _native.ptr(un), _native.ptr(faces), _native.ptr(ws), nws,
-                             _native.stream_ptr(dev))
-    _native.check(rc, "uoc_normals")
+    _native.call("uoc_normals", dev, xyz, labels, planes, B, H, W, int(step), int(window), int(jump_mm), int(min_pairs),
+                 _native.host_words(d, 2), A, int(c_up), int(s_side), packed, un, faces, ws, ws.numel())
     return packed, un, faces
 
 

@@ -9,7 +9,6 @@ batch); the only host traffic is one small read of the per-object counts that si
 """
 from __future__ import annotations
 
-import ctypes
 
 import torch
 
@@ -60,11 +59,7 @@ def object_records(labels, xyz, attrs=None, max_points_per_object=None, capacity
     nws = lib.uoc_objects_workspace_bytes(B, H, W)
     ws = _workspace(dev, nws)
     M = 0 if max_points_per_object is None else int(max_points_per_object)
-    with torch.cuda.device(dev):
-        rc = lib.uoc_objects(_native.ptr(labels), _native.ptr(xyz), _native.ptr(attrs), C, B, H, W, M, _native.ptr(rec),
-                             _native.ptr(pts), _native.ptr(pat), _native.ptr(pix), ctypes.c_long(cap), _native.ptr(total),
-                             _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_objects")
+    _native.call("uoc_objects", dev, labels, xyz, attrs, C, B, H, W, M, rec, pts, pat, pix, cap, total, ws, nws)
     return rec, pts, pat, pix, total
 
 

@@ -65,29 +65,41 @@ def placement_records(labels, xyz, planes, grid, cell_mm, h_obs_mm, tau_mm, min_
     B, H, W = (int(v) for v in labels.shape)
     G, Q = int(grid), len(queries)
     dev = labels.device
-    lib = _native.lib()
-    nws = lib.uoc_placement_workspace_bytes(B, H, W, G)
-    if nws == 0:
-        raise _native.NativeError(f"free_space: bad shape B={B} H={H} W={W} or grid={G} (a multiple of 8 in 8..{_native.PLACE_MAX_GRID})")
+    ws = _native.workspace("uoc_placement_workspace_bytes", dev, B, H, W, G, who="free_space", hint=f"B={B} H={H} W={W} or {grid_hint(G)}")
     state, owner, dist2 = (torch.empty((B, G, G), dtype=torch.int32, device=dev) for _ in range(3))
     counts = torch.empty((B, NUM_IDS), dtype=torch.int32, device=dev)
     frame = torch.empty((B, 16), dtype=torch.int64, device=dev)
     answers = torch.empty((B, Q, 4), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    hq = (ctypes.c_int32 * (4 * max(Q, 1)))(*[int(x) for q in queries for x in q])
-    with torch.cuda.device(dev):
-        rc = lib.uoc_placement(_native.ptr(labels), _native.ptr(xyz), _native.ptr(planes), B, H, W, G, int(cell_mm), int(h_obs_mm),
-                               int(tau_mm), int(min_pts), int(unknown_blocks), ctypes.cast(hq, ctypes.c_void_p) if Q else None, Q,
-                               _native.ptr(state), _native.ptr(owner), _native.ptr(dist2), _native.ptr(counts), _native.ptr(frame),
-                               _native.ptr(answers) if Q else None, _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_placement")
+    _native.call("uoc_placement", dev, labels, xyz, planes, B, H, W, G, int(cell_mm), int(h_obs_mm), int(tau_mm), int(min_pts),
+                 int(unknown_blocks), _native.host_words(queries, 4) if Q else None, Q, state, owner, dist2, counts, frame,
+                 answers if Q else None, ws, ws.numel())
     return state, owner, dist2, counts, frame, answers
 
 
-def _mm(value, name, lo):
+# ---- the range checks every table-grid stage shares -----------------------------------------------------------------
+def check_grid(grid) -> int:
+    G = int(grid)
+    if not (8 <= G <= _native.PLACE_MAX_GRID and G % 8 == 0):
+        raise ValueError(f"grid = {grid} is not a multiple of 8 in 8..{_native.PLACE_MAX_GRID}")
+    return G
+
+
+def grid_hint(G) -> str:
+    """How a *_workspace_bytes of 0 names the grid in the stage's NativeError."""
+    return f"grid={G} (a multiple of 8 in 8..{_native.PLACE_MAX_GRID})"
+
+
+def check_min_pts(min_pts) -> int:
+    if not 1 <= int(min_pts) <= _native.PLACE_MAX_MIN_PTS:
+        raise ValueError(f"min_pts = {min_pts} outside 1..{_native.PLACE_MAX_MIN_PTS}")
+    return int(min_pts)
+
+
+def millimetres(value, name, lo=1, hi=_native.PLACE_MAX_MM) -> int:
+    """Metres -> whole millimetres in lo..hi."""
     mm = int(round(float(value) * 1000))
-    if not lo <= mm <= _native.PLACE_MAX_MM:
-        raise ValueError(f"{name} = {value} m is {mm} mm, outside {lo}..{_native.PLACE_MAX_MM} mm")
+    if not lo <= mm <= hi:
+        raise ValueError(f"{name} = {value} m is {mm} mm, outside {lo}..{hi} mm")
     return mm
 
 
@@ -109,12 +121,9 @@ def free_space(labels, xyz, plane, grid=256, cell=0.010, h_obs=0.010, tau=0.010,
     or a tuple (normal, d, centroid, u, v) that is packed into records.  grid: cells per side, a multiple of 8 in 8..512;
     cell, h_obs, tau: metres, used in whole millimetres (cell, tau in 1..1000, h_obs in 0..1000); min_pts in 1..65535;
     queries: up to 16 (need2, ai, aj, mode) from widest() / nearest().  Returns a PlacementResult."""
-    G = int(grid)
-    if not (8 <= G <= _native.PLACE_MAX_GRID and G % 8 == 0):
-        raise ValueError(f"grid = {grid} is not a multiple of 8 in 8..{_native.PLACE_MAX_GRID}")
-    cell_mm, h_obs_mm, tau_mm = _mm(cell, "cell", 1), _mm(h_obs, "h_obs", 0), _mm(tau, "tau", 1)
-    if not 1 <= int(min_pts) <= _native.PLACE_MAX_MIN_PTS:
-        raise ValueError(f"min_pts = {min_pts} outside 1..{_native.PLACE_MAX_MIN_PTS}")
+    G = check_grid(grid)
+    cell_mm, h_obs_mm, tau_mm = millimetres(cell, "cell"), millimetres(h_obs, "h_obs", 0), millimetres(tau, "tau")
+    check_min_pts(min_pts)
     qs = _check_queries(queries)
     labels, xyz = _native.frame_inputs("free_space", labels, xyz)
     B = int(labels.shape[0])

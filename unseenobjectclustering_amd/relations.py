@@ -32,17 +32,10 @@ def relation_records(labels, xyz, connectivity, gap_mm, min_pairs):
     the device, no synchronisation.  labels int32 [B,H,W] and xyz float32 [B,3,H,W] contiguous on one GPU."""
     B, H, W = (int(v) for v in labels.shape)
     dev = labels.device
-    lib = _native.lib()
-    nws = lib.uoc_relations_workspace_bytes(B, H, W)
-    if nws == 0:
-        raise _native.NativeError(f"relate: bad shape B={B} H={H} W={W} (H*W must be below 2^29)")
+    ws = _native.workspace("uoc_relations_workspace_bytes", dev, B, H, W, who="relate", hint=f"B={B} H={H} W={W} (H*W must be below 2^29)")
     pairs = torch.empty((B, 3, NUM_IDS, NUM_IDS), dtype=torch.int32, device=dev)
     objs = torch.empty((B, NUM_IDS, len(OBJECT_FIELDS)), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    with torch.cuda.device(dev):
-        rc = lib.uoc_relations(_native.ptr(labels), _native.ptr(xyz), B, H, W, int(connectivity), int(gap_mm), int(min_pairs),
-                               _native.ptr(pairs), _native.ptr(objs), _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_relations")
+    _native.call("uoc_relations", dev, labels, xyz, B, H, W, int(connectivity), int(gap_mm), int(min_pairs), pairs, objs, ws, ws.numel())
     return pairs, objs
 
 

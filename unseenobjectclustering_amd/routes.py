@@ -17,7 +17,6 @@ orthogonal and 7 per diagonal step, never across a blocked corner; a cost is a c
 batch.  `plan` neither copies to the host nor synchronises.  No CPU fallback."""
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -61,38 +60,25 @@ def _check_queries(queries, G=None):
 
 def _call(state, owner, frame, queries, unknown_blocks, max_path):
     """uoc_routes; returns (cost, info, path, workspace).  The workspace's first B*Q int32 words are the sweeps taken."""
-    for t, what in ((state, "state"), (owner, "owner")):
-        if not _native.on_gpu(t):
-            raise _native.NativeError(f"routes: {what} must be a tensor on the GPU (there is no CPU fallback)")
-    state, owner = (t[None] if t.dim() == 2 else t for t in (state, owner))
-    if state.dim() != 3 or state.shape[1] != state.shape[2] or tuple(owner.shape) != tuple(state.shape) or owner.device != state.device:
-        raise _native.NativeError(f"routes: state {tuple(state.shape)} and owner {tuple(owner.shape)} are not two [B,G,G] grids on one device")
-    B, G = int(state.shape[0]), int(state.shape[1])
+    st, ow = _native.grid_inputs("routes", state, owner)
+    B, G = int(st.shape[0]), int(st.shape[1])
+    dev = st.device
     if frame is not None:
-        if not (isinstance(frame, torch.Tensor) and frame.device == state.device and frame.dtype == torch.int64 and tuple(frame.shape) == (B, 16)):
-            raise _native.NativeError(f"routes: the frame records do not match the {B} frames on {state.device}")
+        if not (isinstance(frame, torch.Tensor) and frame.device == dev and frame.dtype == torch.int64 and tuple(frame.shape) == (B, 16)):
+            raise _native.NativeError(f"routes: the frame records do not match the {B} frames on {dev}")
         frame = frame.contiguous()
     P = int(max_path)
     if not 1 <= P <= _native.ROUTES_MAX_PATH:
         raise ValueError(f"max_path = {max_path} outside 1..{_native.ROUTES_MAX_PATH}")
-    lib = _native.lib()
-    if lib.uoc_routes_workspace_bytes(B, G, 1) == 0:
-        raise _native.NativeError(f"routes: bad shape B={B} or grid={G} (a multiple of 8 in 8..{_native.PLACE_MAX_GRID})")
+    _native.workspace("uoc_routes_workspace_bytes", dev, B, G, 1, who="routes", hint=f"B={B} or {_placement.grid_hint(G)}")    # the shape, before the queries
     q = _check_queries(queries, G)
     Q = len(q)
-    nws = lib.uoc_routes_workspace_bytes(B, G, Q)
-    dev = state.device
-    st, ow = (t.to(torch.int32).contiguous() for t in (state, owner))
+    ws = _native.workspace("uoc_routes_workspace_bytes", dev, B, G, Q, who="routes", hint=f"B={B} or {_placement.grid_hint(G)}")
     cost = torch.empty((B, Q, G, G), dtype=torch.int32, device=dev)
     info = torch.empty((B, Q, 8), dtype=torch.int32, device=dev)
     path = torch.empty((B, Q, P, 2), dtype=torch.int32, device=dev)
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    hq = (ctypes.c_int32 * (8 * Q))(*[int(x) for x in q.reshape(-1)])
-    with torch.cuda.device(dev):
-        rc = lib.uoc_routes(_native.ptr(st), _native.ptr(ow), _native.ptr(frame) if frame is not None else None, B, G,
-                            ctypes.cast(hq, ctypes.c_void_p), Q, 1 if unknown_blocks else 0, P, _native.ptr(cost), _native.ptr(info),
-                            _native.ptr(path), _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_routes")
+    _native.call("uoc_routes", dev, st, ow, frame, B, G, _native.host_words(q, 8), Q, 1 if unknown_blocks else 0, P, cost, info, path,
+                 ws, ws.numel())
     return cost, info, path, ws
 
 

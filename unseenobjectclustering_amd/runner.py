@@ -203,7 +203,6 @@ def _run_block_pipelined(frame_fn, lo: int, hi: int, block: torch.Tensor, device
     tops = torch.zeros(len(streams), dtype=torch.int32, device=device)   # largest label id per stream (uoc_labels_to_u8)
     for st in streams:
         st.wait_stream(main)                      # inputs / weights (and `tops`) were produced on the caller's stream
-    L = _native.lib()
     nxt = lo
     group = max(1, int(getattr(frame_fn, "frames_per_launch", 1)))
     poll = os.environ.get("UOC_PIPE_POLL", "1") != "0"
@@ -243,10 +242,7 @@ def _run_block_pipelined(frame_fn, lo: int, hi: int, block: torch.Tensor, device
                 if job.pending_event(2) is not None:      # the slot is freed when stage 2 has run (FrameGroupJob.pending_event)
                     return True
             for i, m in zip(idx, job.final_maps()):       # int32 [H, W] (contiguous) -> the uint8 row of the block
-                with torch.cuda.device(device):
-                    _native.check(L.uoc_labels_to_u8(_native.ptr(m), m.numel(), _native.ptr(block[i - lo]),
-                                                     _native.ptr(tops[slot:slot + 1]), _native.stream_ptr(device)),
-                                  "uoc_labels_to_u8")
+                _native.call("uoc_labels_to_u8", device, m, m.numel(), block[i - lo], tops[slot:slot + 1])
         done_counts[idx[0]] = list(job.K)
         slots[slot] = None
         return True

@@ -60,19 +60,13 @@ def plane_records(labels, xyz, num_hyp, tau_mm, seed, height_map=False):
     float32 [B,3,H,W] contiguous on one GPU."""
     B, H, W = (int(v) for v in labels.shape)
     dev = labels.device
-    lib = _native.lib()
-    nws = lib.uoc_plane_workspace_bytes(B, H, W, int(num_hyp))
-    if nws == 0:
-        raise _native.NativeError(f"fit_plane: bad shape B={B} H={H} W={W} or num_hyp={num_hyp} (1..{_native.PLANE_MAX_HYP})")
+    ws = _native.workspace("uoc_plane_workspace_bytes", dev, B, H, W, int(num_hyp), who="fit_plane",
+                           hint=f"B={B} H={H} W={W} or num_hyp={num_hyp} (1..{_native.PLANE_MAX_HYP})")
     planes = torch.empty((B, _PW), dtype=torch.int32, device=dev)
     objs = torch.empty((B, NUM_IDS, _OW), dtype=torch.int32, device=dev)
     height = torch.empty((B, H, W), dtype=torch.float32, device=dev) if height_map else None
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)      # from torch's stream-ordered cache: no allocation in steady state
-    with torch.cuda.device(dev):
-        rc = lib.uoc_support_plane(_native.ptr(labels), _native.ptr(xyz), B, H, W, int(num_hyp), int(tau_mm),
-                                   int(seed) & 0xFFFFFFFF, _native.ptr(planes), _native.ptr(objs), _native.ptr(height),
-                                   _native.ptr(ws), nws, _native.stream_ptr(dev))
-    _native.check(rc, "uoc_support_plane")
+    _native.call("uoc_support_plane", dev, labels, xyz, B, H, W, int(num_hyp), int(tau_mm), int(seed) & 0xFFFFFFFF, planes, objs,
+                 height, ws, ws.numel())
     return planes, objs, height
 
 
@@ -153,23 +147,16 @@ def planes_records(labels, xyz, max_planes, num_hyp, tau_mm, rem_mm, min_inliers
     B, H, W = (int(v) for v in labels.shape)
     K = int(max_planes)
     dev = labels.device
-    lib = _native.lib()
-    nws = lib.uoc_planes_workspace_bytes(B, H, W, int(num_hyp), K)
-    if nws == 0:
-        raise _native.NativeError(f"fit_planes: bad shape B={B} H={H} W={W}, num_hyp={num_hyp} (1..{_native.PLANE_MAX_HYP}), "
-                                  f"max_planes={K} (1..{_native.PLANES_MAX}) or B * max_planes above 65535")
+    ws = _native.workspace("uoc_planes_workspace_bytes", dev, B, H, W, int(num_hyp), K, who="fit_planes",
+                           hint=f"B={B} H={H} W={W}, num_hyp={num_hyp} (1..{_native.PLANE_MAX_HYP}), "
+                                f"max_planes={K} (1..{_native.PLANES_MAX}) or B * max_planes above 65535")
     count = torch.empty((B,), dtype=torch.int32, device=dev)
     planes = torch.empty((B, K, _PW), dtype=torch.int32, device=dev)
     info = torch.empty((B, K, _IW), dtype=torch.int32, device=dev)
     index = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     objs = torch.empty((B, K, NUM_IDS, _OW), dtype=torch.int32, device=dev) if objects else None
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.uoc_support_planes(_native.ptr(labels), _native.ptr(xyz), B, H, W, K, int(num_hyp), int(tau_mm), int(rem_mm),
-                                    int(min_inliers), int(seed) & 0xFFFFFFFF, _native.ptr(count), _native.ptr(planes),
-                                    _native.ptr(info), _native.ptr(index), _native.ptr(objs), _native.ptr(ws), nws,
-                                    _native.stream_ptr(dev))
-    _native.check(rc, "uoc_support_planes")
+    _native.call("uoc_support_planes", dev, labels, xyz, B, H, W, K, int(num_hyp), int(tau_mm), int(rem_mm), int(min_inliers),
+                 int(seed) & 0xFFFFFFFF, count, planes, info, index, objs, ws, ws.numel())
     return count, planes, info, index, objs
 
 

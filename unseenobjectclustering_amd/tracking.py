@@ -53,13 +53,9 @@ class Tracker:
         key = (dev, B, H, W)
         if self._key == key:
             return
-        lib = _native.lib()
-        nbytes = lib.uoc_track_state_bytes(B, H, W)
-        if nbytes == 0:
-            raise _native.NativeError(f"Tracker: bad shape B={B} H={H} W={W} (H*W must be below 2^31)")
-        self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._state = _native.workspace("uoc_track_state_bytes", dev, B, H, W, who="Tracker", hint=f"B={B} H={H} W={W} (H*W must be below 2^31)")
         self._words = self._state.view(torch.int32).view(B, -1)
-        self._ws = torch.empty(max(lib.uoc_track_workspace_bytes(B), 16), dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(max(_native.lib().uoc_track_workspace_bytes(B), 16), dtype=torch.uint8, device=dev)
         self._lut = torch.zeros((B, NUM_SLOTS), dtype=torch.int32, device=dev)
         self._tracks = torch.zeros((B, NUM_SLOTS, _NF), dtype=torch.int32, device=dev)
         self._key = key
@@ -67,9 +63,7 @@ class Tracker:
 
     def _reset(self, which):
         dev, B, H, W = self._key
-        with torch.cuda.device(dev):
-            rc = _native.lib().uoc_track_reset(_native.ptr(self._state), B, H, W, which, _native.stream_ptr(dev))
-        _native.check(rc, "uoc_track_reset")
+        _native.call("uoc_track_reset", dev, self._state, B, H, W, which)
 
     def reset(self, stream=None):
         """Forgets every track of `stream` (all streams when None): its next update starts again at slot 1, uid 1."""
@@ -85,11 +79,7 @@ class Tracker:
     # ---- stepping ------------------------------------------------------------------------------------
     def _step(self, lab, out, lut, tracks):
         dev, B, H, W = self._key
-        with torch.cuda.device(dev):
-            rc = _native.lib().uoc_track_step(_native.ptr(lab), B, H, W, self.q, self.max_age, _native.ptr(self._state),
-                                              _native.ptr(out), _native.ptr(lut), _native.ptr(tracks), _native.ptr(self._ws),
-                                              self._ws.numel(), _native.stream_ptr(dev))
-        _native.check(rc, "uoc_track_step")
+        _native.call("uoc_track_step", dev, lab, B, H, W, self.q, self.max_age, self._state, out, lut, tracks, self._ws, self._ws.numel())
 
     def update(self, labels):
         """labels: device tensor [H,W] (one stream) or [streams,H,W] of int32 / int64 / float ids.  Returns the tracked

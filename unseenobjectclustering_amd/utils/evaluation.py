@@ -66,10 +66,7 @@ def pair_stats(prediction, gt, bound_th=0.003):
         _ws[key] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
     ws = _ws[key]
     radius = int(bound_pixels((H, W), bound_th))
-    with torch.cuda.device(dev):
-        rc = L.uoc_eval_pair_stats(_native.ptr(p), _native.ptr(g), H, W, radius, _native.ptr(tables), _native.ptr(ws),
-                                   ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_eval_pair_stats")
+    _native.call("uoc_eval_pair_stats", dev, p, g, H, W, radius, tables, ws, ws.numel())
     t = _Tables.from_buffer_copy(tables.cpu().numpy().tobytes())
     if t.bad_label:
         raise ValueError(f"label ids must be in [0, {MAX_LABELS})")

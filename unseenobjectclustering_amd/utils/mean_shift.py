@@ -22,17 +22,9 @@ from .. import _native
 from ..fcn.config import cfg, euclidean_enabled
 
 EMBED_DIM = 64          # one 64-channel "half"; 128-d ('cat' fusion) fields are two of them
-_ws_cache = {}
-
-
-def _workspace(device, nbytes: int) -> torch.Tensor:
-    key = _native.stream_key(device)      # one scratch buffer per stream (frames in flight do not share it)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _native.retire(ws)          # a captured hipGraph may have baked the old buffer's address
-        ws = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
-    return ws
+# one scratch buffer per stream (frames in flight do not share it), grown by a quarter beyond what is asked
+_workspace = _native.PerStream(lambda device, nbytes: torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device),
+                               size=torch.Tensor.numel).get
 
 
 def _check_points(X: torch.Tensor, what="X") -> torch.Tensor:
@@ -111,11 +103,8 @@ def cluster_batch(X: torch.Tensor, first_index, kappa: float = 20.0, num_seeds: 
     Z = torch.empty(X.shape[:-2] + (num_seeds, EMBED_DIM), dtype=torch.float32, device=dev)
     seed_labels = torch.empty((B, num_seeds), dtype=torch.int32, device=dev)
     ws = _workspace(dev, L.uoc_ms_workspace_bytes_wide(B, n, num_seeds, H))
-    with torch.cuda.device(dev):
-        rc = L.uoc_ms_cluster_wide_ex(_native.ptr(X), H, B, n, num_seeds, float(kappa), int(max_iters), float(epsilon),
-                                      met, _native.ptr(first), _native.ptr(labels), _native.ptr(indices), _native.ptr(Z),
-                                      _native.ptr(seed_labels), _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_cluster_wide_ex")
+    _native.call("uoc_ms_cluster_wide_ex", dev, X, H, B, n, num_seeds, float(kappa), int(max_iters), float(epsilon), met, first,
+                 labels, indices, Z, seed_labels, ws, ws.numel())
     if return_parts:
         return labels, indices, Z, seed_labels
     return labels, indices
@@ -133,8 +122,7 @@ def mean_shift_smart_init(X, kappa, num_seeds=100, max_iters=10, metric="cosine"
         Xb = to_planes(Xb.float())
     labels, indices = cluster_batch(Xb, [first], kappa, num_seeds, max_iters, metric=metric)
     idx = indices[0].long().cpu()            # synchronises; then ask whether the grid exchange completed
-    with torch.cuda.device(labels.device):
-        _native.check(_native.lib().uoc_ms_check(_native.stream_ptr(labels.device)), "uoc_ms_check")
+    _native.call("uoc_ms_check", labels.device)
     return labels[0].long(), idx
 
 
@@ -168,10 +156,7 @@ def select_smart_seeds(X, num_seeds, return_selected_indices=False, init_seeds=N
         first = torch.tensor([np.random.randint(0, n)], dtype=torch.int32).to(dev)
     indices = torch.empty((num_seeds,), dtype=torch.int32, device=dev)
     ws = _workspace(dev, L.uoc_ms_workspace_bytes(1, n, num_seeds))
-    with torch.cuda.device(dev):
-        rc = L.uoc_ms_select_seeds_ex(_native.ptr(X), 1, n, num_seeds, num_init, _native.ptr(first), _native.ptr(seeds),
-                                      _native.ptr(indices), met, _native.ptr(ws), ws.numel(), _native.stream_ptr(dev))
-    _native.check(rc, "uoc_ms_select_seeds_ex")
+    _native.call("uoc_ms_select_seeds_ex", dev, X, 1, n, num_seeds, num_init, first, seeds, indices, met, ws, ws.numel())
     if return_selected_indices:
         return seeds, indices.long().cpu()
     return (seeds,)
@@ -185,10 +170,7 @@ def seed_hill_climbing_ball(X, Z, kappa, max_iters=10, metric="cosine"):
     n, m = X.shape[0], Zc.shape[0]
     L = _native.lib()
     ws = _workspace(X.device, L.uoc_ms_workspace_bytes(1, n, m))
-    with torch.cuda.device(X.device):
-        rc = L.uoc_ms_hill_climb_ex(_native.ptr(X), 1, n, _native.ptr(Zc), m, float(kappa), int(max_iters), met,
-                                    _native.ptr(ws), ws.numel(), _native.stream_ptr(X.device))
-    _native.check(rc, "uoc_ms_hill_climb_ex")
+    _native.call("uoc_ms_hill_climb_ex", X.device, X, 1, n, Zc, m, float(kappa), int(max_iters), met, ws, ws.numel())
     return Zc
 
 
@@ -197,13 +179,9 @@ def connected_components(Z, epsilon, metric="cosine"):
     met = _surface_metric(metric)
     Zc = _check_points(Z, "Z")
     m = Zc.shape[0]
-    L = _native.lib()
     out = torch.empty((m,), dtype=torch.int32, device=Zc.device)
     nu = torch.empty((1,), dtype=torch.int32, device=Zc.device)
-    with torch.cuda.device(Zc.device):
-        rc = L.uoc_ms_seed_components_ex(_native.ptr(Zc), 1, m, float(epsilon), met, _native.ptr(out), _native.ptr(nu),
-                                         _native.stream_ptr(Zc.device))
-    _native.check(rc, "uoc_ms_seed_components_ex")
+    _native.call("uoc_ms_seed_components_ex", Zc.device, Zc, 1, m, float(epsilon), met, out, nu)
     return out.long().cpu()
 
 
