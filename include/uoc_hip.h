@@ -1003,6 +1003,81 @@ int uoc_normals(const float *d_xyz, const int32_t *d_labels, const uoc_plane *d_
 
 
 /* ------------------------------------------------------------------------------------------
+ * Re-identification: appearance signatures and identities (no reference counterpart).  The
+ * tracker keeps an id while masks overlap; this layer gives an object the same id again after a jump with IoU 0 or an
+ * occlusion longer than max_age, by what it looks like.  Integers only; the result is defined exactly and does not
+ * depend on launch order or batch.  id(p) = L when 1 <= L <= 127, else 0 (background).
+ *
+ * S. Signature of an id: UOC_SIG_WORDS = 104 int32.  Word 0 pixels n; word 1 valid = its pixels with z_mm >= 0, where
+ * z_mm = (int) rintf(z * 1000.0f) when z > 0 && z <= 65, else -1 (NaN: -1), 0 without d_xyz; words 2, 3 the low and
+ * high word of the unsigned 64-bit sum over the valid pixels of (z_mm * z_mm) >> 10, a visible metric area up to a
+ * constant; words 4..7 zero; words 8..88 the chromaticity histogram, 9 x 9, bin 8 + iu * 9 + iv; word 89 =
+ * UOC_SIG_DARK the dark bin; words 90..98 the intensity histogram; words 99..103 zero.  Row 0 and the rows of absent
+ * ids are all zero.
+ * Votes of a pixel with the bytes (b, g, r) and s = b + g + r.  Chroma when s >= 48: u = (64 b) / s, v = (64 g) / s,
+ * ul = u >> 3, uf = u & 7, vl = v >> 3, vf = v & 7; bin (ul + du, vl + dv), du, dv in {0, 1}, gets the weight
+ * (du ? uf : 8 - uf) * (dv ? vf : 8 - vf); a zero weight is no vote, so ul == 8 never reaches a row 9.  Dark when s < 48:
+ * 64 into the dark bin.  Intensity always: y = s / 3, yl = y >> 5, yf = (y & 31) >> 2; 8 (8 - yf) into bin yl and, when
+ * yf != 0, 8 yf into bin yl + 1.  Every pixel adds 64 to the chroma / dark part and 64 to the intensity part.
+ * Stored: q = (h * 768) / n for the chroma and dark bins, (h * 256) / n for the intensity bins, h the raw 32-bit counter,
+ * the product in 64 bits: a signature sums to at most 65536.  A counter holds at most 64 n, hence H*W <= UOC_SIG_MAX_N.
+ * M. Similarity.  sim(a, b) = the sum over the words 8..98 of min(qa, qb), 0 when either pixels is 0; in 0..65536.
+ * I. Identities.  State per stream (caller-owned device memory, uoc_ident_state_bytes(B) / B bytes each, 16-byte
+ * aligned): int32 [1024] header = the table [128][5] = pid, uid, seen, hits, pixels (entry 0 unused; pid 0 = free, all
+ * zero), then at word 640 the pids handed out, the step counter and `evicted`; then the entries' last signatures
+ * [128][104].  An all-zero state is a reset stream.  One step with the tracker's table T (after its step) and the
+ * signatures S of the TRACKED map, so both keyed by track slot; the uids of T's slots are distinct:
+ *  1. step += 1; an entry with pid != 0 and step - seen > max_lost is zeroed.
+ *  2. Slot s is visible when T[s].uid != 0, T[s].age == 0 and S[s].pixels > 0.  A visible slot whose uid is an entry's
+ *     uid is bound to it; the other visible slots are newcomers; entries with pid != 0 bound to no slot are lost.
+ *  3. Candidates: (newcomer s, lost e) with sim(S[s], sig[e]) >= q and, when r > 0, both areas non-zero and
+ *     min(As, Ae) * 256 >= r * max(As, Ae) in 64 bits.
+ *  4. Greedy matching: the candidate of largest sim among unmatched s and e; ties: larger seen, lower e, lower s.  A
+ *     match binds s to e and sets e.uid = T[s].uid.
+ *  5. The newcomers left, in ascending s, take the free entries in ascending order (those freed in 1 included); with
+ *     none free, the lost entry left with the smallest seen (ties: lower e), and `evicted` grows.  Such an entry gets
+ *     pid = ++pids, hits = 0 and the newcomer's uid.
+ *  6. Every bound pair: seen = step, hits += 1, pixels and the signature are S[s]'s, lut[s] = e; every other lut word
+ *     is 0.  out = lut[id(tracked)].
+ * Out of scope: position or motion costs, telling two look-alike objects apart (the tie rule decides), blending
+ * signatures over time.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_SIG_WORDS 104
+#define UOC_SIG_MAX_N (1 << 24)
+#define UOC_SIG_PIXELS 0
+#define UOC_SIG_VALID 1
+#define UOC_SIG_AREA 2                 /* words 2, 3 */
+#define UOC_SIG_HIST 8                 /* words 8..88: chroma bin 8 + iu * 9 + iv */
+#define UOC_SIG_DARK 89
+#define UOC_SIG_INTENSITY 90           /* words 90..98 */
+#define UOC_IDENT_WORDS 5              /* an entry of the table: pid, uid, seen, hits, pixels */
+#define UOC_IDENT_HEADER_WORDS 1024    /* int32 words of a stream's state before its signatures */
+#define UOC_IDENT_META_WORD 640        /* words 640, 641, 642 = pids handed out, step, evicted */
+
+/* 0 for B outside 1..65535. */
+size_t uoc_signature_workspace_bytes(int B);
+/* d_labels [B][H*W] int32; d_image [B][H*W][3] uint8, BGR; d_xyz [B][3][H*W] fp32, nullable; d_sig [B][128][104].  The
+ * workspace holds the vote accumulators: it must be ALL ZERO before the first call that uses it and every call leaves
+ * it all zero, so it is zeroed once, not per call.  d_sig and d_ws 16-byte aligned.  Returns UOC_EINVAL before any
+ * device work for null d_labels / d_image / d_sig / d_ws, a bad shape, H*W above UOC_SIG_MAX_N, a short workspace.
+ * Two launches on `stream`, nothing synchronises. */
+int uoc_signature(const int32_t *d_labels, const uint8_t *d_image, const float *d_xyz, int B, int H, int W, int32_t *d_sig,
+                  void *d_ws, size_t ws_bytes, void *stream);
+/* d_sim [B][128][128]: d_sim[b][i][j] = sim(d_sig_a[b][i], d_sig_b[b][j]).  Signatures 16-byte aligned. */
+int uoc_sig_similarity(const int32_t *d_sig_a, const int32_t *d_sig_b, int B, int32_t *d_sim, void *stream);
+size_t uoc_ident_state_bytes(int B);
+size_t uoc_ident_workspace_bytes(int B);
+/* Zeroes the state of stream `which`, or of all B streams when which = -1. */
+int uoc_ident_reset(void *d_state, int B, int which, void *stream);
+/* d_tracked, d_out [B][H*W] int32 (distinct buffers), H*W below 2^31; d_tracks [B][128]; d_sig [B][128][104]; q = round(min_sim * 65536) in [1, 65536]; r = round(min_size *
+ * 256) in [0, 256]; max_lost >= 0; d_lut (nullable) [B][128]: slot -> entry of this step; d_ident (nullable)
+ * [B][128][5]: the table after the step.  Two launches on `stream`, nothing synchronises. */
+int uoc_ident_step(const int32_t *d_tracked, const uoc_track *d_tracks, const int32_t *d_sig, int B, int H, int W, int q, int r,
+                   int max_lost, void *d_state, int32_t *d_out, int32_t *d_lut, int32_t *d_ident, void *d_ws, size_t ws_bytes,
+                   void *stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl
  * (lib/datasets/ocid_object.py:105, osd_object.py:92): LZF decoder for `DATA binary_compressed` PCD files.
  * `in`/`out` are HOST pointers.  Returns the number of bytes written or a negative code.

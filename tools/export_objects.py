@@ -5,6 +5,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
     python tools/export_objects.py --imgdir tests/golden/demo --out objs/ [--max-points 2048]
                                    [--pretrained ckpt.pth --pretrained_crop crop.pth] [--cfg experiments/cfgs/<experiment>.yml]
                                    [--track [--track-min-iou 0.3] [--track-max-age 5]]
+                                   [--reid [--reid-min-sim 0.7] [--reid-min-size 0.25] [--reid-max-lost 300]]
                                    [--components {all,largest} [--min-area 1]]
                                    [--plane [--min-height M]]
                                    [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
@@ -25,6 +26,11 @@ With --track the frames are taken as one stream in file order: every final label
 (unseenobjectclustering_amd/tracking.py) and the objects are extracted from the TRACKED map, so `label` is the track slot
 an object keeps from frame to frame, `label_map` the tracked map, `raw_label_map` the segmentation's own numbering and
 `track_uid` the stream-wide object number of every row.
+
+With --reid (it needs --track) the tracked map and the colour image also go through the device-side re-identification
+(unseenobjectclustering_amd/identity.py): per row `identity`, the identity entry in 1..127 that the object keeps across a
+jump with no mask overlap or an occlusion longer than --track-max-age, and `identity_pid`, that identity's stream-wide
+number; `identity_map` is the label map renumbered by identity.  Every other key is as without the flag.
 
 With --components the final label map is first split into its spatially connected pieces on the device
 (unseenobjectclustering_amd/components.py): `largest` keeps the largest piece of every id and drops the rest (speckle),
@@ -132,6 +138,7 @@ from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_sp
 from unseenobjectclustering_amd.relations import relate  # noqa: E402
 from unseenobjectclustering_amd.support import choose_support, fit_plane, fit_planes, standing_objects, standing_on  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
+from unseenobjectclustering_amd import identity  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
           "obb_center", "obb_half", "offsets", "points", "pixel_index")
@@ -284,6 +291,10 @@ def build_parser():
     ap.add_argument("--track", action="store_true", help="stable ids across the frames (taken in file order)")
     ap.add_argument("--track-min-iou", type=float, default=0.3)
     ap.add_argument("--track-max-age", type=int, default=5)
+    ap.add_argument("--reid", action="store_true", help="with --track: identities that survive a jump or a long occlusion")
+    ap.add_argument("--reid-min-sim", type=float, default=0.7)
+    ap.add_argument("--reid-min-size", type=float, default=0.25)
+    ap.add_argument("--reid-max-lost", type=int, default=300)
     ap.add_argument("--components", choices=["all", "largest"], default=None,
                     help="split the label map into connected components first (off by default)")
     ap.add_argument("--min-area", type=int, default=1, help="components below this many pixels become background")
@@ -324,6 +335,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.confidence is not None and not 0.0 <= args.confidence <= 1.0:
         ap.error("--confidence WEAK: a margin in 0..1")
+    if args.reid and not args.track:
+        ap.error("--reid needs --track (identities are kept per track)")
+    if args.reid and not (0.0 < args.reid_min_sim <= 1.0 and 0.0 <= args.reid_min_size <= 1.0 and args.reid_max_lost >= 0):
+        ap.error("--reid-min-sim in (0, 1], --reid-min-size in [0, 1], --reid-max-lost not negative")
     if args.planes is not None:
         if not 1 <= args.planes <= 8:
             ap.error("--planes K: K in 1..8")
@@ -364,6 +379,7 @@ def main():
     network_crop = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained_crop)).eval()
     os.makedirs(args.out, exist_ok=True)
     tracker = Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None
+    identifier = identity.Identifier(min_sim=args.reid_min_sim, min_size=args.reid_min_size, max_lost=args.reid_max_lost) if args.reid else None
     for fc, fd in zip(colors, depths):
         sample = uio.read_sample(fc, fd, cam)
         conf = None
@@ -388,6 +404,11 @@ def main():
             final = tracked[None].cpu()
         rec = {k: getattr(objs, k).cpu().numpy() for k in FIELDS}
         rec["label_map"] = final[0].numpy().astype(np.int32)
+        if identifier is not None:          # per row: the identity entry of its track slot and that identity's running number
+            who = identifier.update(tracked, tracker, identity.image_u8(sample).to(cfg.device), sample["depth"][:1].to(cfg.device))
+            entries = identifier.lut[0][objs.label.long()]
+            rec["identity"], rec["identity_pid"] = entries.cpu().numpy(), identifier.table[0, :, 0][entries.long()].cpu().numpy()
+            rec["identity_map"] = who.cpu().numpy().astype(np.int32)
         if tracker is not None:
             rec["raw_label_map"], rec["track_uid"] = raw_map, track_uid
         if comp is not None:           # per row: the component its pixels came from (through the tracker's lut when tracking)

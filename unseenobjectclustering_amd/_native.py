@@ -102,6 +102,13 @@ ABI = {
     "uoc_conf_objects": (I, [P, P, I, I, I, I, P, P]),
     "uoc_normals_workspace_bytes": (Z, [I, I, I]),
     "uoc_normals": (I, [P, P, P, I, I, I, I, I, I, I, P, I, I, I, P, P, P, P, Z, P]),
+    "uoc_signature_workspace_bytes": (Z, [I]),
+    "uoc_signature": (I, [P, P, P, I, I, I, P, P, Z, P]),
+    "uoc_sig_similarity": (I, [P, P, I, P, P]),
+    "uoc_ident_state_bytes": (Z, [I]),
+    "uoc_ident_workspace_bytes": (Z, [I]),
+    "uoc_ident_reset": (I, [P, I, I, P]),
+    "uoc_ident_step": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P, P, Z, P]),
     "uoc_lzf_decompress": (L, [P, Z, P, Z]),
     "uoc_prof_enable": (I, [I]),
     "uoc_prof_reset": (I, []),
@@ -212,6 +219,13 @@ CONF_ONE = 65536                                # the fixed-point unit of uoc_co
 NORMAL_UP, NORMAL_SIDE, NORMAL_OBLIQUE, NORMAL_DOWN = 1, 2, 3, 4      # include/uoc_hip.h: UOC_NORMAL_*, the class of a normal
 NORMALS_MAX_DIRS = 32                           # UOC_NORMALS_MAX_DIRS: A in 1..32
 NORMALS_FACE_WORDS = 40                         # UOC_NORMALS_FACE_WORDS: eight counters and the histogram per id
+SIG_WORDS = 104                                 # include/uoc_hip.h: UOC_SIG_*, the words of a signature
+SIG_MAX_N = 1 << 24                             # pixels per frame of uoc_signature: a vote counter is 32 bits
+SIG_PIXELS, SIG_VALID, SIG_AREA, SIG_HIST, SIG_DARK, SIG_INTENSITY = 0, 1, 2, 8, 89, 90
+IDENT_WORDS = 5                                 # UOC_IDENT_*: an entry of the identity table, IDENT_FIELDS below
+IDENT_HEADER_WORDS = 1024                       # int32 words of a stream's identity state before its signatures
+IDENT_META_WORD = 640                           # ... of which words 640, 641, 642 = pids handed out, step, evicted
+IDENT_FIELDS = ("pid", "uid", "seen", "hits", "pixels")
 
 
 class UocTrack(ctypes.Structure):

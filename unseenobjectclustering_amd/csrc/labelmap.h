@@ -19,4 +19,8 @@ __device__ __forceinline__ int obj_id(int l) { return ((unsigned)(l - 1) < (unsi
 __device__ __forceinline__ int obj_key(int l) { return ((unsigned)(l - 1) < (unsigned)(NUM_IDS - 1)) ? l : -1; }
 __device__ __forceinline__ int label_row(int l) { return ((unsigned)l < (unsigned)NUM_IDS) ? l : -1; }
 
+// The depth of a pixel in whole millimetres as relations.hip and identity.hip read it: -1 of an invalid one (NaN fails
+// both comparisons).
+__device__ __forceinline__ int depth_mm(float z) { return (z > 0.0f && z <= 65.0f) ? (int)rintf(z * 1000.0f) : -1; }
+
 }  // namespace uoc

@@ -42,9 +42,6 @@ constexpr int MAX_PIXELS = (1 << 29) - 1;
 static_assert(4 * SPAN < 65536, "a 16-bit counter of a pair block must not wrap");
 static_assert(sizeof(uoc_relation_object) == 11 * sizeof(int32_t), "uoc_relation_object is eleven int32");
 
-// zq of a valid depth, -1 of an invalid one (NaN fails both comparisons).
-__device__ __forceinline__ int depth_mm(float z) { return (z > 0.0f && z <= 65.0f) ? (int)rintf(z * 1000.0f) : -1; }
-
 // One distinct event per loop turn: the wave's lanes holding it are counted with one ballot and added once.
 __device__ __forceinline__ void wave_add_events(unsigned *__restrict__ s_tab, int code, int lane) {
   for_each_wave_key(code, [&](int c, unsigned long long m, int first) {
