@@ -1076,6 +1076,55 @@ int uoc_ident_step(const int32_t *d_tracked, const uoc_track *d_tracks, const in
                    int max_lost, void *d_state, int32_t *d_out, int32_t *d_lut, int32_t *d_ident, void *d_ws, size_t ws_bytes,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Object motion: planar registration on the table grid.  How an object that stays on the table
+ * moved between two frames: a rotation about the plane normal and an in-plane shift, found by an exhaustive integer
+ * search over both.  Inputs are the state / owner grids of uoc_placement for the same B frames "before" (x = a) and
+ * "after" (x = b), rasterised in ONE plane frame, a host table of A rotations, a radius R and P host pairs (id_a, id_b).
+ *  C. Cell (i, j) of grid x belongs to id `a` iff its state is 2 and its owner is exactly `a`.  n_a, n_b: the counts;
+ *     still = n_a + n_b - 2 |A n B|, the cost of "did not move".
+ *  P. The pivots p = (floor_div(2 sum(i) + n_a, 2 n_a), floor_div(2 sum(j) + n_a, 2 n_a)) over A's cells, q the same
+ *     over B's.
+ *  T. S = 16384.  h_rot[k] = (Cx_k, Cy_k) = (rint(cos(2 pi k / A) S), rint(sin(2 pi k / A) S)), a full turn; every word
+ *     in -S..S.  rd(x) = floor_div(2 x + S, 2 S).  Forward F_k(di, dj) = (rd(di Cx - dj Cy), rd(di Cy + dj Cx)); inverse
+ *     I_k(ei, ej) = (rd(ei Cx + ej Cy), rd(-ei Cy + ej Cx)).  Every product stays below 2^24.
+ *  X. For k in 0..A-1 and a shift s = (si, sj), |si|, |sj| <= R:
+ *       cost(k, s) = #{c in A : q + s + F_k(c - p) not in B} + #{c' in B : p + I_k(c' - q - s) not in A}.
+ *     A cell outside the grid is in neither set.
+ *  K. The answer is the minimum of the key (cost << 33) | (s2 << 23) | (kk << 17) | (k << 11) | sidx with s2 = si^2 +
+ *     sj^2, kk = min(k, A - k), sidx = (si + R)(2R + 1) + (sj + R): least cost, then least shift, then least turn, then
+ *     lowest k, then lowest shift index.  A strict total order.
+ *  O. d_rot[b][p][k] = (cost, si, sj, 0), the key's minimum over s for that k; rows k >= A are (-1, 0, 0, 0).
+ *     d_best[b][p] = 16 words (status, k, si, sj, cost, n_a, n_b, still, pi, pj, qi, qj, ti, tj, second, 0) with
+ *     t = q + s - p, the pivot's travel in cells, and second = the least d_rot cost over the rotations at circular
+ *     distance >= 2 from k, -1 when there is none.
+ *  S. status 1: evaluated.  0: no common frame (frame records given, and word 13 of either is not 1 or the 16 words of
+ *     the two differ).  2: n_a = 0 or n_b = 0.  3: n_a or n_b above UOC_MOTION_MAX_CELLS.  For a status other than 1,
+ *     d_best is (status, -1, 0, 0, 0, n_a, n_b, 0, 0...) and every d_rot row is (-1, 0, 0, 0); n_a = n_b = 0 for status
+ *     0.  With both frame pointers NULL every frame is evaluated as it stands.
+ * Out of scope: heights, out-of-plane motion, objects leaving the plane, partial occlusion, sub-cell refinement, more
+ * than 64 rotations.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_MOTION_MAX_ROT 64
+#define UOC_MOTION_MAX_RADIUS 16
+#define UOC_MOTION_MAX_PAIRS 16
+#define UOC_MOTION_MAX_CELLS 4096
+#define UOC_MOTION_SCALE 16384
+#define UOC_MOTION_ROT_WORDS 4
+#define UOC_MOTION_BEST_WORDS 16
+
+/* 0 for B outside 1..65535, G not a multiple of 8 in 8..512, A outside 1..64, P outside 1..16. */
+size_t uoc_motion_workspace_bytes(int B, int G, int A, int P);
+/* d_state_x, d_owner_x [B][G][G] int32; d_frame_a, d_frame_b [B][16] int64 or both NULL; h_rot [A][2] and h_pairs [P][2]
+ * on the host, read before the call returns; d_rot [B][P][64][4], d_best [B][P][16] int32.  Returns UOC_EINVAL before any
+ * device work, outputs and workspace untouched, for null pointers other than the two frame pointers, one frame pointer
+ * NULL and one not, B / G / A / R / P out of range, a table word outside -S..S, an id outside 1..127, a workspace below
+ * uoc_motion_workspace_bytes(B, G, A, P) or one that is not 16-byte aligned.  One memset and three launches on `stream`,
+ * nothing synchronises. */
+int uoc_motion(const int32_t *d_state_a, const int32_t *d_owner_a, const int64_t *d_frame_a, const int32_t *d_state_b,
+               const int32_t *d_owner_b, const int64_t *d_frame_b, int B, int G, const int32_t *h_rot, int A, int R,
+               const int32_t *h_pairs, int P, int32_t *d_rot, int32_t *d_best, void *d_ws, size_t ws_bytes, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl

@@ -6,6 +6,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--pretrained ckpt.pth --pretrained_crop crop.pth] [--cfg experiments/cfgs/<experiment>.yml]
                                    [--track [--track-min-iou 0.3] [--track-max-age 5]]
                                    [--reid [--reid-min-sim 0.7] [--reid-min-size 0.25] [--reid-max-lost 300]]
+                                   [--motion [--motion-angles 32] [--motion-radius 8]]
                                    [--components {all,largest} [--min-area 1]]
                                    [--plane [--min-height M]]
                                    [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
@@ -71,6 +72,13 @@ level.  Per row `top_cells` and `top_level`, the object's solid and level cells;
 the most room ((-1, -1) without one), `top_clear_m`, the distance from there to the nearest cell that is not level,
 `top_height_m`, its height above the plane, and `top_xyz`, its centre lifted onto the top, camera coordinates (NaN
 without a level cell).  With --placement RADIUS_M also `top_fits`: whether a disc of RADIUS_M metres fits there.
+
+With --motion (it needs --track) every object's motion on the table since the frame before is registered on the device
+(unseenobjectclustering_amd/motion.py) on the --grid x --grid grid: a rotation about the plane normal, one of
+--motion-angles over a full turn, and an in-plane shift.  The support plane fitted on the FIRST frame serves the whole
+stream (the camera must stand still), the ids are those of the exported label map (the identities under --reid).  Every
+frame but the first gets `motion_ids` [P], `motion_best` [P,16] = (status, k, si, sj, cost, n_a, n_b, still, pi, pj, qi,
+qj, ti, tj, second, 0) and `motion_T` [P,4,4], the rigid motion in camera coordinates (NaN where status is not 1).
 
 With --putdown LENGTH_M WIDTH_M the oriented put-down poses of a LENGTH_M x WIDTH_M rectangle (conservative: inflated by
 0.72 cell) are computed on the device (unseenobjectclustering_amd/footprint.py) on the --grid x --grid grid of the
@@ -139,6 +147,7 @@ from unseenobjectclustering_amd.relations import relate  # noqa: E402
 from unseenobjectclustering_amd.support import choose_support, fit_plane, fit_planes, standing_objects, standing_on  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 from unseenobjectclustering_amd import identity  # noqa: E402
+from unseenobjectclustering_amd import motion  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
           "obb_center", "obb_half", "offsets", "points", "pixel_index")
@@ -264,6 +273,20 @@ def relation_arrays(related, ids):
     return rec
 
 
+MOTION_KEYS = ("motion_ids", "motion_best", "motion_T")
+
+
+def motion_arrays(res):
+    """The --motion arrays of one frame against the frame before: frame 0 of `res` (a motion.register result, None when no
+    id is on both grids).  motion_ids [P], the ids followed; motion_best [P,16], motion.BEST_FIELDS per id; motion_T
+    [P,4,4], the rigid motion in camera coordinates (NaN for an id that was not evaluated)."""
+    if res is None:
+        return {"motion_ids": np.zeros((0,), np.int32), "motion_best": np.zeros((0, 16), np.int32), "motion_T": np.zeros((0, 4, 4), np.float64)}
+    moves = [motion.transform(res, 0, p) for p in range(len(res.pairs))]
+    return {"motion_ids": np.asarray(res.pairs[:, 0], np.int32), "motion_best": res.best[0].cpu().numpy(),
+            "motion_T": np.stack([np.full((4, 4), np.nan) if m is None else m.T for m in moves])}
+
+
 def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm, keep=None):
     """The --placement arrays of one frame: the grid maps and the widest spot for a disc of `radius` metres.  keep: a list
     that receives the placement result (--route goes on from it)."""
@@ -295,6 +318,9 @@ def build_parser():
     ap.add_argument("--reid-min-sim", type=float, default=0.7)
     ap.add_argument("--reid-min-size", type=float, default=0.25)
     ap.add_argument("--reid-max-lost", type=int, default=300)
+    ap.add_argument("--motion", action="store_true", help="with --track: how every object moved on the table since the frame before")
+    ap.add_argument("--motion-angles", type=int, default=32, help="with --motion: rotations over a full turn (1..64)")
+    ap.add_argument("--motion-radius", type=int, default=8, help="with --motion: the largest shift past the centroids' travel, cells (0..16)")
     ap.add_argument("--components", choices=["all", "largest"], default=None,
                     help="split the label map into connected components first (off by default)")
     ap.add_argument("--min-area", type=int, default=1, help="components below this many pixels become background")
@@ -339,6 +365,10 @@ def parse_args(argv=None):
         ap.error("--reid needs --track (identities are kept per track)")
     if args.reid and not (0.0 < args.reid_min_sim <= 1.0 and 0.0 <= args.reid_min_size <= 1.0 and args.reid_max_lost >= 0):
         ap.error("--reid-min-sim in (0, 1], --reid-min-size in [0, 1], --reid-max-lost not negative")
+    if args.motion and not args.track:
+        ap.error("--motion needs --track (an object is followed by the id it keeps)")
+    if args.motion and not (1 <= args.motion_angles <= 64 and 0 <= args.motion_radius <= 16):
+        ap.error("--motion-angles in 1..64, --motion-radius in 0..16")
     if args.planes is not None:
         if not 1 <= args.planes <= 8:
             ap.error("--planes K: K in 1..8")
@@ -380,6 +410,7 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     tracker = Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None
     identifier = identity.Identifier(min_sim=args.reid_min_sim, min_size=args.reid_min_size, max_lost=args.reid_max_lost) if args.reid else None
+    follower = None
     for fc, fd in zip(colors, depths):
         sample = uio.read_sample(fc, fd, cam)
         conf = None
@@ -411,6 +442,14 @@ def main():
             rec["identity_map"] = who.cpu().numpy().astype(np.int32)
         if tracker is not None:
             rec["raw_label_map"], rec["track_uid"] = raw_map, track_uid
+        if args.motion:
+            ids_map = torch.from_numpy(rec["identity_map"] if identifier is not None else rec["label_map"]).to(cfg.device)
+            if follower is None:            # the plane of the first frame serves the whole stream: the camera stands still
+                follower = motion.Follower(fit_plane(ids_map, sample["depth"][0].to(cfg.device)), grid=args.grid, cell=args.cell_mm / 1000.0,
+                                           angles=args.motion_angles, radius=args.motion_radius)
+                follower.update(ids_map, sample["depth"][0].to(cfg.device))
+            else:
+                rec.update(motion_arrays(follower.update(ids_map, sample["depth"][0].to(cfg.device))))
         if comp is not None:           # per row: the component its pixels came from (through the tracker's lut when tracking)
             ids = objs.label.long()
             if tracker is not None:    # track slot -> the split map's id

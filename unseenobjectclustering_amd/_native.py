@@ -109,6 +109,8 @@ ABI = {
     "uoc_ident_workspace_bytes": (Z, [I]),
     "uoc_ident_reset": (I, [P, I, I, P]),
     "uoc_ident_step": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P, P, Z, P]),
+    "uoc_motion_workspace_bytes": (Z, [I, I, I, I]),
+    "uoc_motion": (I, [P, P, P, P, P, P, I, I, P, I, I, P, I, P, P, P, Z, P]),
     "uoc_lzf_decompress": (L, [P, Z, P, Z]),
     "uoc_prof_enable": (I, [I]),
     "uoc_prof_reset": (I, []),
@@ -226,6 +228,12 @@ IDENT_WORDS = 5                                 # UOC_IDENT_*: an entry of the i
 IDENT_HEADER_WORDS = 1024                       # int32 words of a stream's identity state before its signatures
 IDENT_META_WORD = 640                           # ... of which words 640, 641, 642 = pids handed out, step, evicted
 IDENT_FIELDS = ("pid", "uid", "seen", "hits", "pixels")
+MOTION_MAX_ROT = 64                             # include/uoc_hip.h: UOC_MOTION_*: A in 1..64 over a full turn
+MOTION_MAX_RADIUS = 16                          # R in 0..16 cells
+MOTION_MAX_PAIRS = 16                           # P in 1..16
+MOTION_MAX_CELLS = 4096                         # cells of a mask; above it status 3
+MOTION_SCALE = 16384                            # S of the rotation table
+MOTION_ROT_WORDS, MOTION_BEST_WORDS = 4, 16     # a row of rot (cost, si, sj, 0) and of best (motion.BEST_FIELDS)
 
 
 class UocTrack(ctypes.Structure):
