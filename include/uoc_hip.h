@@ -1125,6 +1125,80 @@ int uoc_motion(const int32_t *d_state_a, const int32_t *d_owner_a, const int64_t
                const int32_t *d_owner_b, const int64_t *d_frame_b, int B, int G, const int32_t *h_rot, int A, int R,
                const int32_t *h_pairs, int P, int32_t *d_rot, int32_t *d_best, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scene memory: the table grid fused over time.  A per-stream memory of the state / owner grids
+ * of uoc_placement: cells observed in this frame overwrite it, cells not observed keep what was last seen there for at
+ * most max_age steps, and a cell whose observation contradicts the memory is flagged.  The fused grids have the
+ * meaning of uoc_placement's, so every stage that takes those takes these.  Integers only.
+ * State.  Caller-owned, 16-byte aligned, uoc_scene_state_bytes(B, G) bytes; stream b at b * (that / B).  Per stream:
+ *     int64 [16]   the lattice record: the frame record (uoc_placement's d_frame) of the grid the memory lives on
+ *     int32 [16]   meta: word 0 = steps taken, word 1 = restarts, the rest 0
+ *     int32 [G*G]  memory words  state | owner << 8 | age << 16,  state 0..2, owner 0..127, age 0..32767: never negative
+ *   In int32 words: the meta at UOC_SCENE_META_WORD, the memory at UOC_SCENE_MEM_WORD.  All zero is a reset stream.
+ *  L. The lattice, per frame.  With d_frame given and word 13 (found) of the frame's record not 1: status 0, the
+ *     stream's state is untouched, state / owner / dist2 / change / ids / answers are those of a frame without a plane
+ *     in uoc_placement (zeros, (-1, -1, 0, 0) per query), age is -1 everywhere and info = (0, steps, 0, ...).  With a
+ *     record given and steps > 0, if the stored record differs from it in any of the 16 words: a restart, every memory
+ *     word counts as 0 for this step, restarts goes up by 1 and the status is 2.  Otherwise the status is 1.  The given
+ *     record is stored on the first step (steps = 0) and on a restart.  d_frame == NULL: the lattice is the caller's
+ *     word, nothing is compared or stored, status 1.  With status 1 and 2 steps goes up by 1.
+ *  N. The current cell: s = state_cur when that is 1 or 2, else 0; o = owner_cur when s == 2 and 1 <= owner_cur <= 127,
+ *     else 0 (an obstacle without an id keeps owner 0 and is a real obstacle).
+ *  U. The update, with the memory word (ms, mo, ma).
+ *     Observed, s != 0: the new word is (s, o, 0); the change code against the old word is APPEARED (1) when ms == 1
+ *     and s == 2, VANISHED (2) when ms == 2 and s == 1, REOWNED (3) when ms == 2, s == 2 and mo != o, else SAME (0),
+ *     also when ms == 0.
+ *     Not observed, s == 0: kept as (ms, mo, ma + 1) when ms != 0, ma < max_age and not (ms == 2 and bit mo of the
+ *     frame's drop mask is set); the drop mask is 128 bits, bit a = bit (a & 31) of word d_drop[b][a >> 5], no bits
+ *     with d_drop == NULL.  Otherwise forgotten: the word becomes 0.  The change code is 0.
+ *     Per cell: state and owner come from the new word; age is 0 where observed, ma + 1 where kept, -1 where the new
+ *     word is 0; change is the change code.
+ *  E. Clearance on the fused grid, rule E of uoc_placement: a cell is blocking when its fused state is 2, or 0 with
+ *     unknown_blocks; every cell outside the grid is blocking; dist2 is the exact squared Euclidean distance, in cells,
+ *     to the nearest blocking cell.
+ *  Q. Queries on the fused grid, rule Q of uoc_placement: the candidates are the cells of fused state 1, the same keys
+ *     and ties.
+ *  T. ids[b][a][8] for a = 0..127 (row 0: the obstacles without an id):
+ *       0 cells_now     observed obstacle cells with o == a          4 vanished     VANISHED cells with mo == a
+ *       1 cells_kept    kept obstacle cells with mo == a             5 reowned_in   REOWNED cells with o == a
+ *       2 oldest        the largest age among them, 0 without one    6 reowned_out  REOWNED cells with mo == a
+ *       3 appeared      APPEARED cells with o == a                   7 forgotten    memory obstacle cells with mo == a
+ *                                                                                   forgotten in this step, by age or drop
+ *     info[b][8] = (status, steps after this step, observed cells, kept cells, forgotten cells of any state, appeared,
+ *     vanished, reowned).  Every count is a sum of ones and oldest a maximum: no result depends on launch order or on
+ *     the other frames of the batch.
+ * Out of scope: a moving camera (a new plane is a restart), deciding that a remembered object has moved away (the
+ * caller says so through d_drop), heights, blending or voting over several sightings, image-space label smoothing.
+ * ---------------------------------------------------------------------------------------- */
+#define UOC_SCENE_META_WORD 32         /* int32 words of a stream's state before its meta words */
+#define UOC_SCENE_MEM_WORD 48          /* ... and before its memory words */
+#define UOC_SCENE_MAX_AGE 32767
+#define UOC_SCENE_ID_WORDS 8
+#define UOC_SCENE_INFO_WORDS 8
+#define UOC_SCENE_SAME 0
+#define UOC_SCENE_APPEARED 1
+#define UOC_SCENE_VANISHED 2
+#define UOC_SCENE_REOWNED 3
+
+/* B * (192 + 4 G G); 0 for B outside 1..65535 or G not a multiple of 8 in 8..512. */
+size_t uoc_scene_state_bytes(int B, int G);
+size_t uoc_scene_workspace_bytes(int B, int G);
+/* Zeroes the state of stream `which`, or of all B streams when which = -1.  UOC_EINVAL for a null or misaligned state,
+ * a bad B or G, which outside -1..B-1. */
+int uoc_scene_reset(void *d_state, int B, int G, int which, void *stream);
+/* d_state_cur, d_owner_cur [B][G][G] int32; d_frame (nullable) [B][16] int64; d_drop (nullable) [B][4] int32; h_queries
+ * [Q][4] on the host as for uoc_placement, read before the call returns; d_mem: the state; d_state, d_owner, d_dist2,
+ * d_age, d_change [B][G][G], d_ids [B][128][8], d_info [B][8], d_answers [B][Q][4] int32.  Returns UOC_EINVAL before any
+ * device work, outputs, state and workspace untouched, for null pointers other than d_frame, d_drop and, with Q = 0,
+ * h_queries and d_answers; B outside 1..65535; G not a multiple of 8 in 8..512; max_age outside 0..32767;
+ * unknown_blocks neither 0 nor 1; Q outside 0..16 or a query out of uoc_placement's ranges; a workspace below
+ * uoc_scene_workspace_bytes(B, G); a state or workspace that is not 16-byte aligned.  One memset and two launches on
+ * `stream`, a third with queries; nothing synchronises. */
+int uoc_scene_step(const int32_t *d_state_cur, const int32_t *d_owner_cur, const int64_t *d_frame, const int32_t *d_drop,
+                   int B, int G, int max_age, int unknown_blocks, const int32_t *h_queries, int Q, void *d_mem,
+                   int32_t *d_state, int32_t *d_owner, int32_t *d_dist2, int32_t *d_age, int32_t *d_change,
+                   int32_t *d_ids, int32_t *d_info, int32_t *d_answers, void *d_ws, size_t ws_bytes, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Host-side data formats (no device work) — what the dataset loaders need in place of python-pcl

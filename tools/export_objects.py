@@ -10,7 +10,7 @@ tools/test_images.py, then extract_objects on the device (unseenobjectclustering
                                    [--components {all,largest} [--min-area 1]]
                                    [--plane [--min-height M]]
                                    [--relations [--relations-gap 0.015] [--relations-min-pairs 8]]
-                                   [--placement RADIUS_M [--grid 256] [--cell-mm 10]]
+                                   [--placement RADIUS_M [--grid 256] [--cell-mm 10] [--memory AGE]]
                                    [--grasp MAX_OPEN_M [--grasp-angles 16] [--grasp-offsets 2]]
                                    [--elevation STEP_M [--elevation-min-pts 2]]
                                    [--putdown LENGTH_M WIDTH_M [--putdown-angles 16]]
@@ -80,6 +80,15 @@ stream (the camera must stand still), the ids are those of the exported label ma
 frame but the first gets `motion_ids` [P], `motion_best` [P,16] = (status, k, si, sj, cost, n_a, n_b, still, pi, pj, qi,
 qj, ti, tj, second, 0) and `motion_T` [P,4,4], the rigid motion in camera coordinates (NaN where status is not 1).
 
+With --memory AGE (it needs --placement) the table grid is fused over the frames on the device
+(unseenobjectclustering_amd/scene.py): a cell that this frame does not observe keeps its last sighting for AGE steps, a
+cell whose observation contradicts the memory is flagged.  The support plane of the FIRST frame serves the whole stream
+(the camera must stand still).  Every frame gets `memory_state`, `memory_owner`, `memory_age` (steps since the cell was
+seen, -1: unknown), `memory_change` (0 same, 1 appeared, 2 vanished, 3 reowned) [G,G], `memory_ids` [128,8] =
+(cells_now, cells_kept, oldest, appeared, vanished, reowned_in, reowned_out, forgotten) per owner id and `memory_info` [8]
+= (status, steps, observed, kept, forgotten, appeared, vanished, reowned).  With --motion the remembered cells of the ids
+that moved (motion.moved) are dropped, and the ids are those --motion follows.
+
 With --putdown LENGTH_M WIDTH_M the oriented put-down poses of a LENGTH_M x WIDTH_M rectangle (conservative: inflated by
 0.72 cell) are computed on the device (unseenobjectclustering_amd/footprint.py) on the --grid x --grid grid of the
 placement stage, which runs for it with its defaults whether or not --placement is given, over --putdown-angles
@@ -148,6 +157,7 @@ from unseenobjectclustering_amd.support import choose_support, fit_plane, fit_pl
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
 from unseenobjectclustering_amd import identity  # noqa: E402
 from unseenobjectclustering_amd import motion  # noqa: E402
+from unseenobjectclustering_amd import scene  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
           "obb_center", "obb_half", "offsets", "points", "pixel_index")
@@ -287,6 +297,25 @@ def motion_arrays(res):
             "motion_T": np.stack([np.full((4, 4), np.nan) if m is None else m.T for m in moves])}
 
 
+MEMORY_KEYS = ("memory_state", "memory_owner", "memory_age", "memory_change", "memory_ids", "memory_info")
+
+
+def memory_arrays(res):
+    """The --memory arrays of one frame: frame 0 of `res` (a scene.Memory.update result).  memory_state, memory_owner,
+    memory_age, memory_change [G,G]: the fused grid, how many steps ago each cell was seen (-1: unknown) and its change
+    code (scene.CODES); memory_ids [128,8], scene.ID_FIELDS per owner id; memory_info [8], scene.INFO_FIELDS."""
+    return {"memory_" + k: getattr(res, k)[0].cpu().numpy() for k in ("state", "owner", "age", "change", "ids", "info")}
+
+
+def moved_ids_mask(res, device):
+    """[1,128] bool on the device: the ids motion.moved reports for frame 0 of `res` (None: no id), built without a host
+    read; what --memory drops."""
+    mask = torch.zeros((1, 128), dtype=torch.bool, device=device)
+    if res is not None:
+        mask[0, torch.from_numpy(np.asarray(res.pairs[:, 0], np.int64)).to(device)] = motion.moved(res)[0]
+    return mask
+
+
 def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm, keep=None):
     """The --placement arrays of one frame: the grid maps and the widest spot for a disc of `radius` metres.  keep: a list
     that receives the placement result (--route goes on from it)."""
@@ -333,6 +362,8 @@ def build_parser():
                     help="add the free space on the support plane and the widest spot for a disc of this radius (metres)")
     ap.add_argument("--grid", type=int, default=256, help="with --placement: cells per side (a multiple of 8 in 8..512)")
     ap.add_argument("--cell-mm", type=int, default=10, help="with --placement: cell size in millimetres")
+    ap.add_argument("--memory", type=int, default=None, metavar="AGE",
+                    help="with --placement: fuse the table grid over the frames; a hidden cell keeps its last sighting for AGE steps")
     ap.add_argument("--grasp", type=float, default=None, metavar="MAX_OPEN_M",
                     help="add the parallel-jaw grasp candidates of the objects for a gripper that opens this far (metres)")
     ap.add_argument("--grasp-angles", type=int, default=16, help="with --grasp: closing directions over half a turn (1..32)")
@@ -369,6 +400,11 @@ def parse_args(argv=None):
         ap.error("--motion needs --track (an object is followed by the id it keeps)")
     if args.motion and not (1 <= args.motion_angles <= 64 and 0 <= args.motion_radius <= 16):
         ap.error("--motion-angles in 1..64, --motion-radius in 0..16")
+    if args.memory is not None:
+        if args.placement is None:
+            ap.error("--memory needs --placement (it remembers the grid that --placement computes)")
+        if not 0 <= args.memory <= 32767:
+            ap.error("--memory AGE: AGE in 0..32767")
     if args.planes is not None:
         if not 1 <= args.planes <= 8:
             ap.error("--planes K: K in 1..8")
@@ -411,6 +447,8 @@ def main():
     tracker = Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None
     identifier = identity.Identifier(min_sim=args.reid_min_sim, min_size=args.reid_min_size, max_lost=args.reid_max_lost) if args.reid else None
     follower = None
+    memory = scene.Memory(args.grid, max_age=args.memory, device=cfg.device) if args.memory is not None else None
+    memory_plane = None
     for fc, fd in zip(colors, depths):
         sample = uio.read_sample(fc, fd, cam)
         conf = None
@@ -420,7 +458,7 @@ def main():
         else:
             out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
         final = out_refined if out_refined is not None else out_label
-        track_uid = raw_map = comp = None
+        track_uid = raw_map = comp = moved = None
         if args.components is not None:
             split, table, _ = split_components(final[0].to(cfg.device), connectivity=8, min_area=args.min_area,
                                                mode=args.components)
@@ -449,7 +487,8 @@ def main():
                                            angles=args.motion_angles, radius=args.motion_radius)
                 follower.update(ids_map, sample["depth"][0].to(cfg.device))
             else:
-                rec.update(motion_arrays(follower.update(ids_map, sample["depth"][0].to(cfg.device))))
+                moved = follower.update(ids_map, sample["depth"][0].to(cfg.device))
+                rec.update(motion_arrays(moved))
         if comp is not None:           # per row: the component its pixels came from (through the tracker's lut when tracking)
             ids = objs.label.long()
             if tracker is not None:    # track slot -> the split map's id
@@ -479,6 +518,11 @@ def main():
                 query = routes.of_object(kept[0], fitted, 0, args.route[0], (int(spot[0]), int(spot[1])) if spot[0] >= 0 else None,
                                          radius_m=args.route[1])
                 rec.update(route_arrays(routes.plan(kept[0], [query])))
+        if memory is not None:              # the plane of the first frame serves the whole stream: the camera stands still
+            memory_plane = fitted if memory_plane is None else memory_plane
+            seen = free_space(torch.from_numpy(rec["identity_map"] if args.motion and identifier is not None else rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), memory_plane,
+                              grid=args.grid, cell=args.cell_mm / 1000.0)
+            rec.update(memory_arrays(memory.update(seen, drop=moved_ids_mask(moved, cfg.device) if args.motion else None)))
         if args.grasp is not None:
             placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
                                 grid=args.grid, cell=args.cell_mm / 1000.0)

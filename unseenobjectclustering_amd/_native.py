@@ -111,6 +111,10 @@ ABI = {
     "uoc_ident_step": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P, P, Z, P]),
     "uoc_motion_workspace_bytes": (Z, [I, I, I, I]),
     "uoc_motion": (I, [P, P, P, P, P, P, I, I, P, I, I, P, I, P, P, P, Z, P]),
+    "uoc_scene_state_bytes": (Z, [I, I]),
+    "uoc_scene_workspace_bytes": (Z, [I, I]),
+    "uoc_scene_reset": (I, [P, I, I, I, P]),
+    "uoc_scene_step": (I, [P, P, P, P, I, I, I, I, P, I, P, P, P, P, P, P, P, P, P, P, Z, P]),
     "uoc_lzf_decompress": (L, [P, Z, P, Z]),
     "uoc_prof_enable": (I, [I]),
     "uoc_prof_reset": (I, []),
@@ -234,6 +238,10 @@ MOTION_MAX_PAIRS = 16                           # P in 1..16
 MOTION_MAX_CELLS = 4096                         # cells of a mask; above it status 3
 MOTION_SCALE = 16384                            # S of the rotation table
 MOTION_ROT_WORDS, MOTION_BEST_WORDS = 4, 16     # a row of rot (cost, si, sj, 0) and of best (motion.BEST_FIELDS)
+SCENE_META_WORD, SCENE_MEM_WORD = 32, 48        # include/uoc_hip.h: UOC_SCENE_*: int32 words of a stream's state before its meta / memory words
+SCENE_MAX_AGE = 32767                           # max_age in 0..32767
+SCENE_ID_WORDS, SCENE_INFO_WORDS = 8, 8         # a row of ids (scene.ID_FIELDS) and of info (scene.INFO_FIELDS)
+SCENE_SAME, SCENE_APPEARED, SCENE_VANISHED, SCENE_REOWNED = 0, 1, 2, 3      # a cell's change code
 
 
 class UocTrack(ctypes.Structure):

@@ -1,8 +1,9 @@
-// The table grid, once: what placement.hip, elevation.hip, grasp.hip, footprint.hip, routes.hip and normals.hip share
-// (DESIGN.md §23).  The integer frame of a support plane and its 16-word record, the projection of a point into a cell,
-// the pixel sweep of the raster passes, the per-wave combination of distinct cells, the two passes of the exact distance
-// transform, the runs of FREE cells, the widest-cell key and the host-side shape checks.  Every stage that names a cell
-// means the cell these functions give it.  Integers only; everything returns the same bits from run to run.
+// The table grid, once: what placement.hip, elevation.hip, grasp.hip, footprint.hip, routes.hip, normals.hip and
+// scene.hip share.  The integer frame of a support plane and its 16-word record, the projection of a
+// point into a cell, the pixel sweep of the raster passes, the per-wave combination of distinct cells, the two passes of
+// the exact distance transform, the runs of FREE cells, the widest-cell key, the placement queries and the host-side
+// shape checks.  Every stage that names a cell means the cell these functions give it.  Integers only; everything
+// returns the same bits from run to run.
 #pragma once
 #include "labelmap.h"
 
@@ -289,6 +290,92 @@ __device__ __forceinline__ unsigned long long widest_key(int dist2, int idx) {
 }
 __device__ __forceinline__ int key_dist2(unsigned long long key) { return (int)(key >> 18) - 1; }
 
+// ---- the placement queries --------------------------------------------------------------------------------------------
+// Rule Q of uoc_placement, for every stage that answers it on a state grid (placement.hip, scene.hip).  Keys (0: no
+// candidate).  dist2 <= (G/2)^2 = 2^16, idx = i*G + j < 2^18, da = (i-ai)^2 + (j-aj)^2 <= 2 * (4096 + 511)^2 < 2^26:
+//   widest   ((dist2 + 1) << 18) | (0x3FFFF - idx)
+//   nearest  ((2^27 - 1 - da) << 35) | (dist2 << 18) | (0x3FFFF - idx)      for the candidates with dist2 >= need2
+constexpr int PLACE_MAX_Q = UOC_PLACE_MAX_QUERIES;
+
+static_assert(2ll * (MAX_ANCHOR + MAX_G) * (MAX_ANCHOR + MAX_G) < (1ll << 27) - 1, "the anchor distance must fit 27 bits");
+
+struct PlaceQueries {
+  int v[PLACE_MAX_Q][4];  // need2, ai, aj, mode
+};
+
+// The row pass with the query keys, the body of a kernel on grid (rows, frames) with ROW_THREADS threads: dist2 holds g
+// as the column pass left it and gets the squared distance in place; per query one 64-bit key per candidate cell (state
+// 1), the maximum per wave by shuffles, per block through LDS, per frame by atomicMax into keys [B][PLACE_MAX_Q] (zeroed).
+__device__ __forceinline__ void row_pass_and_keys(const int *__restrict__ state, int G, const PlaceQueries &qs, int Q,
+                                                  int *__restrict__ dist2, unsigned long long *__restrict__ keys) {
+  __shared__ __attribute__((aligned(16))) int s_g2[MAX_G];
+  __shared__ unsigned long long s_key[PLACE_MAX_Q];
+  const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x, b = blockIdx.y;
+  const size_t off = ((size_t)b * G + i) * G;
+  row_fill_g2(s_g2, dist2 + off, G);
+  if (tid < PLACE_MAX_Q) s_key[tid] = 0ull;
+  __syncthreads();
+  unsigned long long key[PLACE_MAX_Q];
+#pragma unroll
+  for (int q = 0; q < PLACE_MAX_Q; ++q) key[q] = 0ull;
+  for (int j = tid; j < G; j += ROW_THREADS) {
+    const int best = row_min_dist2(s_g2, j, G);
+    dist2[off + j] = best;
+    if (Q > 0 && state[off + j] == 1) {
+      const unsigned long long low = cell_key(i * G + j);
+#pragma unroll
+      for (int q = 0; q < PLACE_MAX_Q; ++q) {
+        unsigned long long k64 = 0ull;
+        if (q >= Q) {  // uniform
+        } else if (qs.v[q][3] == UOC_PLACE_WIDEST) {
+          k64 = widest_key(best, i * G + j);
+        } else if (best >= qs.v[q][0]) {
+          const int di = i - qs.v[q][1], dj = j - qs.v[q][2];
+          const unsigned long long da = (unsigned long long)(di * di + dj * dj);
+          k64 = (((1ull << 27) - 1ull - da) << 35) | ((unsigned long long)best << 18) | low;
+        }
+        key[q] = max(key[q], k64);
+      }
+    }
+  }
+  if (Q == 0) return;
+#pragma unroll
+  for (int q = 0; q < PLACE_MAX_Q; ++q) {
+    if (q < Q) {  // uniform
+      const unsigned long long k64 = wave_max64(key[q]);
+      if (lane == 0 && k64) atomicMax(&s_key[q], k64);
+    }
+  }
+  __syncthreads();
+  if (tid < Q && s_key[tid]) atomicMax(&keys[(size_t)b * PLACE_MAX_Q + tid], s_key[tid]);
+}
+
+// The keys back into (i, j, dist2, ok), the body of a kernel of one block per frame with at least PLACE_MAX_Q threads.
+__device__ __forceinline__ void answer_queries(const unsigned long long *__restrict__ keys, int G, const PlaceQueries &qs, int Q,
+                                               int *__restrict__ answers) {
+  const int q = threadIdx.x, b = blockIdx.x;
+  if (q >= Q) return;
+  const unsigned long long k64 = keys[(size_t)b * PLACE_MAX_Q + q];
+  int4 a = make_int4(-1, -1, 0, 0);
+  if (k64) {
+    const int idx = key_cell(k64);
+    a.x = idx / G;
+    a.y = idx % G;
+    if (qs.v[q][3] == UOC_PLACE_WIDEST) {
+      a.z = key_dist2(k64);
+      a.w = a.z >= qs.v[q][0];
+    } else {
+      a.z = (int)((k64 >> 18) & 0x1FFFFull);
+      a.w = 1;
+    }
+  }
+  int *A = answers + ((size_t)b * Q + q) * 4;
+  A[0] = a.x;
+  A[1] = a.y;
+  A[2] = a.z;
+  A[3] = a.w;
+}
+
 // ---- the runs of FREE cells -------------------------------------------------------------------------------------------
 template <int TABLES>
 struct RunIgnore {
@@ -350,5 +437,21 @@ inline bool grid_ok(int G) { return G >= 8 && G <= MAX_G && G % 8 == 0; }
 inline bool batch_ok(int B) { return B > 0 && B <= 65535; }
 inline bool image_ok(int B, int H, int W) { return batch_ok(B) && H > 0 && W > 0 && (long long)H * W <= INT_MAX; }
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The host table of Q placement queries into qs, the rest zero; UOC_EINVAL in `who`'s name for a Q, a pointer or a
+// word out of range.
+inline int load_place_queries(const char *who, const int32_t *h_queries, const void *d_answers, int Q, PlaceQueries &qs) {
+  UOC_REQUIRE(Q >= 0 && Q <= PLACE_MAX_Q, "%s: %d queries outside [0, %d]", who, Q, PLACE_MAX_Q);
+  UOC_REQUIRE(Q == 0 || (h_queries && d_answers), "%s: null queries / answers with Q = %d", who, Q);
+  for (int q = 0; q < PLACE_MAX_Q; ++q)
+    for (int k = 0; k < 4; ++k) qs.v[q][k] = q < Q ? h_queries[q * 4 + k] : 0;
+  for (int q = 0; q < Q; ++q) {
+    UOC_REQUIRE(qs.v[q][0] >= 0 && qs.v[q][0] <= (1 << 30), "%s: query %d: need2 = %d outside [0, 2^30]", who, q, qs.v[q][0]);
+    UOC_REQUIRE(qs.v[q][1] >= -MAX_ANCHOR && qs.v[q][1] < MAX_ANCHOR && qs.v[q][2] >= -MAX_ANCHOR && qs.v[q][2] < MAX_ANCHOR,
+                "%s: query %d: anchor (%d, %d) outside [-4096, 4095]", who, q, qs.v[q][1], qs.v[q][2]);
+    UOC_REQUIRE(qs.v[q][3] == UOC_PLACE_WIDEST || qs.v[q][3] == UOC_PLACE_NEAREST, "%s: query %d: mode = %d", who, q, qs.v[q][3]);
+  }
+  return UOC_OK;
+}
 
 }  // namespace uoc

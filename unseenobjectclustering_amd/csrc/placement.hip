@@ -29,23 +29,15 @@
 // The frame and its record, step P, the pixel sweep, the merge of equal events (wave_distinct), the segment scan of the
 // column pass, the row minimum and the widest key are grid.h's, shared with the other stages on this grid.
 //
-// Query keys (0: no candidate).  dist2 <= (G/2)^2 = 2^16, idx = i*G + j < 2^18, da = (i-ai)^2 + (j-aj)^2 <=
-// 2 * (4096 + 511)^2 < 2^26:
-//   widest   ((dist2 + 1) << 18) | (0x3FFFF - idx)
-//   nearest  ((2^27 - 1 - da) << 35) | (dist2 << 18) | (0x3FFFF - idx)      for the candidates with dist2 >= need2
+// The query keys and the answer are grid.h's too (rule Q), shared with scene.hip.
 #include "grid.h"
 #include "prof.h"
 
 namespace uoc {
 namespace {
 
-constexpr int MAX_Q = UOC_PLACE_MAX_QUERIES;
-
-static_assert(2ll * (MAX_ANCHOR + MAX_G) * (MAX_ANCHOR + MAX_G) < (1ll << 27) - 1, "the anchor distance must fit 27 bits");
-
-struct Queries {
-  int v[MAX_Q][4];  // need2, ai, aj, mode
-};
+constexpr int MAX_Q = PLACE_MAX_Q;
+using Queries = PlaceQueries;
 
 struct Thresholds {
   int cell_div;         // cell_mm * S
@@ -134,71 +126,12 @@ __global__ __launch_bounds__(STRIP *SEGS) void column_kernel(const int *__restri
 // ---- 3. the row pass and the queries -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(ROW_THREADS) void row_kernel(const int *__restrict__ state, int G, Queries qs, int Q,
                                                           int *__restrict__ dist2, unsigned long long *__restrict__ keys) {
-  __shared__ __attribute__((aligned(16))) int s_g2[MAX_G];
-  __shared__ unsigned long long s_key[MAX_Q];
-  const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x, b = blockIdx.y;
-  const size_t off = ((size_t)b * G + i) * G;
-  row_fill_g2(s_g2, dist2 + off, G);
-  if (tid < MAX_Q) s_key[tid] = 0ull;
-  __syncthreads();
-  unsigned long long key[MAX_Q];
-#pragma unroll
-  for (int q = 0; q < MAX_Q; ++q) key[q] = 0ull;
-  for (int j = tid; j < G; j += ROW_THREADS) {
-    const int best = row_min_dist2(s_g2, j, G);
-    dist2[off + j] = best;
-    if (Q > 0 && state[off + j] == 1) {
-      const unsigned long long low = cell_key(i * G + j);
-#pragma unroll
-      for (int q = 0; q < MAX_Q; ++q) {
-        unsigned long long k64 = 0ull;
-        if (q >= Q) {  // uniform
-        } else if (qs.v[q][3] == UOC_PLACE_WIDEST) {
-          k64 = widest_key(best, i * G + j);
-        } else if (best >= qs.v[q][0]) {
-          const int di = i - qs.v[q][1], dj = j - qs.v[q][2];
-          const unsigned long long da = (unsigned long long)(di * di + dj * dj);
-          k64 = (((1ull << 27) - 1ull - da) << 35) | ((unsigned long long)best << 18) | low;
-        }
-        key[q] = max(key[q], k64);
-      }
-    }
-  }
-  if (Q == 0) return;
-#pragma unroll
-  for (int q = 0; q < MAX_Q; ++q) {
-    if (q < Q) {  // uniform
-      const unsigned long long k64 = wave_max64(key[q]);
-      if (lane == 0 && k64) atomicMax(&s_key[q], k64);
-    }
-  }
-  __syncthreads();
-  if (tid < Q && s_key[tid]) atomicMax(&keys[(size_t)b * MAX_Q + tid], s_key[tid]);
+  row_pass_and_keys(state, G, qs, Q, dist2, keys);
 }
 
 __global__ __launch_bounds__(64) void answer_kernel(const unsigned long long *__restrict__ keys, int G, Queries qs, int Q,
                                                     int *__restrict__ answers) {
-  const int q = threadIdx.x, b = blockIdx.x;
-  if (q >= Q) return;
-  const unsigned long long k64 = keys[(size_t)b * MAX_Q + q];
-  int4 a = make_int4(-1, -1, 0, 0);
-  if (k64) {
-    const int idx = key_cell(k64);
-    a.x = idx / G;
-    a.y = idx % G;
-    if (qs.v[q][3] == UOC_PLACE_WIDEST) {
-      a.z = key_dist2(k64);
-      a.w = a.z >= qs.v[q][0];
-    } else {
-      a.z = (int)((k64 >> 18) & 0x1FFFFull);
-      a.w = 1;
-    }
-  }
-  int *A = answers + ((size_t)b * Q + q) * 4;
-  A[0] = a.x;
-  A[1] = a.y;
-  A[2] = a.z;
-  A[3] = a.w;
+  answer_queries(keys, G, qs, Q, answers);
 }
 
 bool shape_ok(int B, int H, int W, int G) { return image_ok(B, H, W) && grid_ok(G); }
@@ -245,18 +178,8 @@ int uoc_placement(const int32_t *d_labels, const float *d_xyz, const uoc_plane *
   UOC_REQUIRE(tau_mm >= 1 && tau_mm <= 1000, "uoc_placement: tau_mm = %d outside [1, 1000]", tau_mm);
   UOC_REQUIRE(min_pts >= 1 && min_pts <= 65535, "uoc_placement: min_pts = %d outside [1, 65535]", min_pts);
   UOC_REQUIRE(unknown_blocks == 0 || unknown_blocks == 1, "uoc_placement: unknown_blocks = %d is neither 0 nor 1", unknown_blocks);
-  UOC_REQUIRE(Q >= 0 && Q <= MAX_Q, "uoc_placement: %d queries outside [0, %d]", Q, MAX_Q);
-  UOC_REQUIRE(Q == 0 || (h_queries && d_answers), "uoc_placement: null queries / answers with Q = %d", Q);
   Queries qs;
-  for (int q = 0; q < MAX_Q; ++q)
-    for (int k = 0; k < 4; ++k) qs.v[q][k] = q < Q ? h_queries[q * 4 + k] : 0;
-  for (int q = 0; q < Q; ++q) {
-    UOC_REQUIRE(qs.v[q][0] >= 0 && qs.v[q][0] <= (1 << 30), "uoc_placement: query %d: need2 = %d outside [0, 2^30]", q, qs.v[q][0]);
-    UOC_REQUIRE(qs.v[q][1] >= -MAX_ANCHOR && qs.v[q][1] < MAX_ANCHOR && qs.v[q][2] >= -MAX_ANCHOR && qs.v[q][2] < MAX_ANCHOR,
-                "uoc_placement: query %d: anchor (%d, %d) outside [-4096, 4095]", q, qs.v[q][1], qs.v[q][2]);
-    UOC_REQUIRE(qs.v[q][3] == UOC_PLACE_WIDEST || qs.v[q][3] == UOC_PLACE_NEAREST, "uoc_placement: query %d: mode = %d", q,
-                qs.v[q][3]);
-  }
+  if (const int rc = load_place_queries("uoc_placement", h_queries, d_answers, Q, qs)) return rc;
   const Ws w = carve(d_ws, B, G);
   UOC_REQUIRE(ws_bytes >= w.total, "uoc_placement: workspace %zu < %zu bytes", ws_bytes, w.total);
   UOC_REQUIRE(aligned16(d_ws), "uoc_placement: workspace not 16-byte aligned");

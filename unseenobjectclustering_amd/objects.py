@@ -124,7 +124,8 @@ def extract_objects(labels, xyz, attrs=None, max_points_per_object=None, min_poi
 def segment_objects(sample, network, network_crop, use_refined=True, plane=False, plane_args=None, relations=False,
                     relations_args=None, placement=False, placement_args=None, grasp=False, grasp_args=None, elevation=False,
                     elevation_args=None, footprint=False, footprint_args=None, routes=False, routes_args=None, confidence=False,
-                    confidence_args=None, normals=False, normals_args=None, planes=False, planes_args=None, **kw):
+                    confidence_args=None, normals=False, normals_args=None, planes=False, planes_args=None, memory=None, memory_args=None,
+                    **kw):
     """One frame through the two-stage path (test_dataset._run_frame, device label maps), then extract_objects on the
     refined map (item 0, as the reference refines only item 0) where there is one and use_refined, else on the stage-1
     maps.  Returns (out_label, out_label_refined, objects): the label maps exactly as test_sample returns them (float32,
@@ -147,7 +148,9 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     item of all, the several planes of the same maps (support.fit_planes; planes_args = its keyword arguments, and `up`,
     `tol`, `par_deg` of support.choose_support among them).  With it the plane of plane=True (and so of placement=True
     and every switch that implies it) is not fit_plane's but res.plane(choose_support(res, ...)), the plane most objects
-    stand on, chosen on the device; plane_args is then not used."""
+    stand on, chosen on the device; plane_args is then not used.  memory=a scene.Memory implies placement=True, fuses this
+    frame's free space into that memory (Memory.update, memory_args = its keyword arguments) and adds the SceneResult as
+    the last item of all; the placement item and the stages on it stay those of this frame alone."""
     if footprint and "rects" not in (footprint_args or {}):
         raise ValueError("segment_objects: footprint=True needs footprint_args with `rects`")
     if routes and "queries" not in (routes_args or {}):
@@ -167,7 +170,7 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     xyz = sample["depth"].to(dev)
     src, src_xyz = (refined[:1], xyz[:1]) if use_refined and refined is not None else (labels, xyz)
     objs = extract_objects(src, src_xyz, **kw)
-    placement = placement or grasp or elevation or footprint or routes
+    placement = placement or grasp or elevation or footprint or routes or memory is not None
     plane = plane or placement or normals
     if planes:
         from .support import choose_support, fit_planes
@@ -200,9 +203,11 @@ def segment_objects(sample, network, network_crop, use_refined=True, plane=False
     if normals:
         from .normals import estimate
         estimated = estimate(src_xyz, src, fitted, **(normals_args or {}))
+    if memory is not None:
+        remembered = memory.update(placed, **(memory_args or {}))
     out_label = labels.float().cpu()
     out_refined = refined.float().cpu() if refined is not None else None
     return (out_label, out_refined, objs) + ((fitted,) if plane else ()) + ((related,) if relations else ()) \
         + ((placed,) if placement else ()) + ((grasped,) if grasp else ()) + ((raised,) if elevation else ()) \
         + ((fitting,) if footprint else ()) + ((routed,) if routes else ()) + ((conf,) if confidence else ()) \
-        + ((estimated,) if normals else ()) + ((several,) if planes else ())
+        + ((estimated,) if normals else ()) + ((several,) if planes else ()) + ((remembered,) if memory is not None else ())
