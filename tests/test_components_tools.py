@@ -1,26 +1,10 @@
 """Where users meet the component split: the opt-in --components / --min-area of tools/export_objects.py (GPU: the step
 has no CPU path)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import components_reference as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
-COMPONENT_KEYS = {"component_src", "component_area", "component_siblings"}
-
-
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
+from tests.tool_cases import BASE_KEYS, COMPONENT_KEYS, export
 
 
 @pytest.mark.gpu

@@ -2,10 +2,6 @@
 the arrays the tool adds are checked on the CPU (the tool's own confidence_arrays on a synthetic summary); the command
 line on the GPU (the stage has no CPU path): tests/test_confidence_gpu.py holds the stage against the reference end to
 end, segment_objects(..., confidence=True) included."""
-import importlib
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -13,20 +9,9 @@ import pytest
 import torch
 
 from tests import confidence_reference as R
+from tests.tool_cases import BASE_KEYS, export, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
 CONFIDENCE_KEYS = {"conf_map", "conf_mean", "conf_min", "conf_weak_share"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_confidence_arguments_and_arrays(tool):
@@ -46,14 +31,6 @@ def test_confidence_arguments_and_arrays(tool):
     assert rec["conf_map"].shape == (3, 4) and rec["conf_map"].dtype == np.float32 and (rec["conf_map"] == 0.75).all()
     assert rec["conf_mean"].tolist() == [0.5, 0.25] and rec["conf_min"].tolist() == [0.25, 0.125]
     assert rec["conf_weak_share"].tolist() == [0.125, 0.125] and rec["conf_mean"].dtype == np.float64
-
-
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
 
 
 @pytest.mark.gpu

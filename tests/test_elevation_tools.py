@@ -2,11 +2,6 @@
 --elevation-min-pts of tools/export_objects.py.  The argument wiring and the arrays the tool adds are checked on the CPU
 (the tool's own elevation_arrays on a synthetic result); the command line and segment_objects on the GPU (the step has
 no CPU path): tests/test_elevation_gpu.py holds the stage against the reference end to end."""
-import importlib
-import json
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -14,21 +9,9 @@ import pytest
 import torch
 
 from tests import elevation_reference as R
+from tests.tool_cases import BASE_KEYS, PLACEMENT_KEYS, demo_sample, export, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
-PLACEMENT_KEYS = {"place_state", "place_dist2", "place_widest_cell", "place_widest_xyz"}
 ELEVATION_KEYS = {"top_cells", "top_level", "top_cell", "top_clear_m", "top_height_m", "top_xyz"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_elevation_arguments_and_arrays(tool):
@@ -54,14 +37,6 @@ def test_elevation_arguments_and_arrays(tool):
     assert tool.elevation_arrays(syn, [5, 3], 0.01)["top_fits"].tolist() == [False, True]        # need2 = 4
     assert tool.elevation_arrays(syn, [5, 3], 0.011)["top_fits"].tolist() == [False, False]      # need2 = 9
     assert tool.elevation_arrays(syn, [])["top_xyz"].shape == (0, 3)
-
-
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
 
 
 def check_rows(z, fits):
@@ -93,10 +68,8 @@ def test_export_objects_elevation_cli(device, golden_dir, tmp_path):
     level = both["top_level"] > 0
     assert np.array_equal(both["top_fits"][level], both["top_clear_m"][level] >= 0.04 - 1e-12)      # need2 = (3 + 1)^2 cells of 1 cm
     # top_cell agrees with tops: the stage on the exported label map, with the tool's defaults
-    from unseenobjectclustering_amd import elevation, io as uio, placement, support
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    xyz = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0].to(device)
+    from unseenobjectclustering_amd import elevation, placement, support
+    xyz = demo_sample(golden_dir)["depth"][0].to(device)
     lab = torch.from_numpy(z["label_map"]).to(device)
     placed = placement.free_space(lab, xyz, support.fit_plane(lab, xyz))
     res = elevation.heights(lab, xyz, placed)
@@ -107,10 +80,8 @@ def test_export_objects_elevation_cli(device, golden_dir, tmp_path):
 
 
 def _demo(golden_dir):
-    from unseenobjectclustering_amd import io as uio, networks, synth
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    sample = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)
+    from unseenobjectclustering_amd import networks, synth
+    sample = demo_sample(golden_dir)
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.calibrated_state_dict().items()}
     return sample, networks.seg_resnet34_8s_embedding(2, 64, sd).eval(), networks.seg_resnet34_8s_embedding(2, 64, sd).eval()
 

@@ -3,11 +3,6 @@ tools/export_objects.py.  The argument wiring and the arrays the tool adds are c
 putdown_arrays on a synthetic result); the command line on the GPU (the step has no CPU path):
 tests/test_footprint_gpu.py holds the stage against the reference end to end, segment_objects(..., footprint=True)
 included."""
-import importlib
-import json
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -15,21 +10,9 @@ import pytest
 import torch
 
 from tests import footprint_reference as R
+from tests.tool_cases import BASE_KEYS, PLACEMENT_KEYS, demo_sample, export, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
-PLACEMENT_KEYS = {"place_state", "place_dist2", "place_widest_cell", "place_widest_xyz"}
 PUTDOWN_KEYS = {"putdown_fits", "putdown_count", "putdown_best", "putdown_dirs", "putdown_center", "putdown_axis"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_putdown_arguments_and_arrays(tool):
@@ -64,14 +47,6 @@ def test_putdown_arguments_and_arrays(tool):
     assert np.isnan(rec["putdown_center"]).all() and np.isnan(rec["putdown_axis"]).all() and rec["putdown_center"].shape == (3,)
 
 
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
-
-
 @pytest.mark.gpu
 def test_export_objects_putdown_cli(device, golden_dir, tmp_path):
     plain = export(golden_dir, tmp_path / "plain")
@@ -83,10 +58,8 @@ def test_export_objects_putdown_cli(device, golden_dir, tmp_path):
     assert z["putdown_fits"].shape == (256, 256) and z["putdown_count"].shape == (32,) and z["putdown_best"].shape == (8,)
     assert z["putdown_dirs"].tolist() == R.direction_table(8).tolist()
     # the stage on the exported label map, with the tool's defaults, against the reference
-    from unseenobjectclustering_amd import footprint, io as uio, placement, support
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    xyz = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0].to(device)
+    from unseenobjectclustering_amd import footprint, placement, support
+    xyz = demo_sample(golden_dir)["depth"][0].to(device)
     lab = torch.from_numpy(z["label_map"]).to(device)
     placed = placement.free_space(lab, xyz, support.fit_plane(lab, xyz))
     assert np.array_equal(z["place_state"], placed.state[0].cpu().numpy())

@@ -2,31 +2,15 @@
 tools/export_objects.py.  The argument wiring and the arrays the tool adds are checked on the CPU (the tool's own
 grasp_arrays on a synthetic result); the command line itself on the GPU (the step has no CPU path), its arrays against
 each other: tests/test_grasp_gpu.py holds the stage against the reference end to end."""
-import importlib
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 from tests import grasp_reference as R
+from tests.tool_cases import BASE_KEYS, export, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
 GRASP_KEYS = {"grasp_best", "grasp_cand", "grasp_dirs", "grasp_center", "grasp_axis", "grasp_width", "grasp_opening"}
 S = 16384
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_grasp_arguments(tool):
@@ -65,14 +49,6 @@ def test_grasp_arrays_of_a_synthetic_result(tool):
     assert np.allclose([rec["grasp_width"][1], rec["grasp_opening"][1]], [0.03, 0.05], rtol=0, atol=1e-12)
     empty = tool.grasp_arrays(res, [])
     assert empty["grasp_center"].shape == (0, 3) and empty["grasp_best"].shape == (0, 8) and empty["grasp_width"].shape == (0,)
-
-
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
 
 
 @pytest.mark.gpu

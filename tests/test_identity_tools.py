@@ -3,8 +3,6 @@ tools/export_objects.py, both on top of --track.  A stub segmentation whose seco
 pixel with the old one comes out with a new track slot under --track alone and with the same id under --reid (GPU: the
 stages have no CPU path).  The argument errors are in tests/test_identity_host.py."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,7 +10,8 @@ import torch
 
 from tests import fake_ros
 from tests.test_ros_node import K
-from tests.test_tracking_tools import ROOT, load_tracked_module, rosmod  # noqa: F401  (rosmod is a fixture)
+from tests.test_tracking_tools import load_tracked_module, rosmod  # noqa: F401  (rosmod is a fixture)
+from tests.tool_cases import run_tool
 from unseenobjectclustering_amd.fcn.config import cfg
 
 pytestmark = pytest.mark.gpu
@@ -79,9 +78,7 @@ def test_reid_publishes_the_same_id_after_a_jump(rosmod, device):
 
 
 def test_export_objects_reid_cli(device, golden_dir, tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(tmp_path), "--max-points", "500", "--track", "--reid"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = run_tool(os.path.join(golden_dir, "demo"), tmp_path, "--max-points", "500", "--track", "--reid")
     assert r.returncode == 0, r.stdout + r.stderr
     z = np.load(tmp_path / "000002_objects.npz")
     assert {"identity", "identity_pid", "identity_map", "label_map", "raw_label_map", "track_uid"} <= set(z.files)

@@ -2,29 +2,14 @@
 top of --track.  The argument wiring and the arrays the tool adds are checked on the CPU (the tool's own motion_arrays on a
 result built from the reference); the command line on the GPU (the stage has no CPU path): tests/test_motion_gpu.py holds
 the stage against the reference end to end."""
-import importlib
-import os
-import shutil
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 from tests import motion_reference as R
+from tests.tool_cases import demo_frames, demo_sample, run_tool, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MOTION_KEYS = {"motion_ids", "motion_best", "motion_T"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_motion_arguments_and_arrays(tool):
@@ -63,18 +48,10 @@ def test_motion_arguments_and_arrays(tool):
 
 @pytest.mark.gpu
 def test_export_objects_motion_cli(device, golden_dir, tmp_path):
-    frames = tmp_path / "frames"
-    frames.mkdir()
-    for k in (2, 3):                                               # the demo frame twice: nothing moves
-        for kind in ("color", "depth"):
-            shutil.copy(os.path.join(golden_dir, "demo", f"000002-{kind}.png"), frames / f"00000{k}-{kind}.png")
-    shutil.copy(os.path.join(golden_dir, "demo", "camera_params.json"), frames / "camera_params.json")
-    tool_py = os.path.join(ROOT, "tools", "export_objects.py")
-    common = [sys.executable, tool_py, "--imgdir", str(frames), "--out", str(tmp_path / "out"), "--max-points", "500"]
-    r = subprocess.run(common + ["--motion"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    frames = demo_frames(golden_dir, tmp_path / "frames")        # the demo frame twice: nothing moves
+    r = run_tool(frames, tmp_path / "out", "--max-points", "500", "--motion")
     assert r.returncode != 0 and "--motion needs --track" in r.stderr
-    r = subprocess.run(common + ["--track", "--motion", "--motion-angles", "16", "--motion-radius", "4"], capture_output=True, text=True,
-                       timeout=600, cwd=ROOT)
+    r = run_tool(frames, tmp_path / "out", "--max-points", "500", "--track", "--motion", "--motion-angles", "16", "--motion-radius", "4")
     assert r.returncode == 0, r.stdout + r.stderr
     first, second = np.load(tmp_path / "out" / "000002_objects.npz"), np.load(tmp_path / "out" / "000003_objects.npz")
     assert not MOTION_KEYS & set(first.files) and MOTION_KEYS <= set(second.files)
@@ -83,10 +60,8 @@ def test_export_objects_motion_cli(device, golden_dir, tmp_path):
     assert set(ids.tolist()) <= set(np.unique(first["label_map"]).tolist()) & set(np.unique(second["label_map"]).tolist())
     # the stage on the two exported label maps, with the tool's settings, against the reference
     import json
-    from unseenobjectclustering_amd import io as uio, motion, placement, support
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    xyz = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0].to(device)
+    from unseenobjectclustering_amd import motion, placement, support
+    xyz = demo_sample(golden_dir)["depth"][0].to(device)
     la, lb = (torch.from_numpy(z["label_map"]).to(device) for z in (first, second))
     fitted = support.fit_plane(la, xyz)
     pa, pb = placement.free_space(la, xyz, fitted), placement.free_space(lb, xyz, fitted)

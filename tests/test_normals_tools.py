@@ -2,10 +2,7 @@
 arrays the tool adds are checked on the CPU (the tool's own normals_arrays on a synthetic result); the command line on
 the GPU (the stage has no CPU path): tests/test_normals_gpu.py holds the stage against the reference end to end,
 segment_objects(..., normals=True) included."""
-import importlib
 import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -14,20 +11,9 @@ import torch
 
 from tests import normals_reference as R
 from tests import placement_reference as S15
+from tests.tool_cases import BASE_KEYS, demo_sample, run_tool, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
 NORMALS_KEYS = {"normal", "normal_info", "faces"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_normals_arguments_and_arrays(tool):
@@ -51,9 +37,7 @@ def test_normals_arguments_and_arrays(tool):
 
 @pytest.mark.gpu
 def test_export_objects_normals_cli(device, golden_dir, tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir", os.path.join(golden_dir, "demo"),
-                        "--out", str(tmp_path), "--max-points", "500", "--normals", "--plane"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = run_tool(os.path.join(golden_dir, "demo"), tmp_path, "--max-points", "500", "--normals", "--plane")
     assert r.returncode == 0, r.stdout + r.stderr
     z = np.load(tmp_path / "000002_objects.npz")
     assert NORMALS_KEYS <= set(z.files) and BASE_KEYS <= set(z.files)
@@ -64,11 +48,7 @@ def test_export_objects_normals_cli(device, golden_dir, tmp_path):
     ids = z["label"].astype(int)
     assert np.array_equal(z["faces"][:, 0], z["pixels"])
     # the exported arrays are the reference's on the exported label map and plane; the frame's cloud comes from the tool's loader
-    from unseenobjectclustering_amd import io as uio
-    import json
-    d = os.path.join(golden_dir, "demo")
-    sample = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"),
-                             json.load(open(os.path.join(d, "camera_params.json"))))
+    sample = demo_sample(golden_dir)
     plane = dict(found=int(z["plane_found"]), normal=z["plane_normal"], d=z["plane_d"], centroid=z["plane_centroid"], u=z["plane_u"],
                  v=z["plane_v"])
     assert S15.frame_record(plane)[13] == 1

@@ -1,37 +1,10 @@
 """Where users meet the placement stage: the opt-in --placement RADIUS_M / --grid / --cell-mm of tools/export_objects.py,
 alone and on tracked and component-split maps (GPU: the step has no CPU path)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import placement_reference as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
-PLACEMENT_KEYS = {"place_state", "place_dist2", "place_widest_cell", "place_widest_xyz"}
-PLANE_KEYS = {"plane_" + k for k in ("found", "candidates", "inliers", "hyp", "normal", "d", "centroid", "eig", "rms", "u", "v")} \
-    | {"height_min", "height_max", "foot", "cov2", "upright_axis", "upright_half", "upright_center"}
-COMPONENT_KEYS = {"component_src", "component_area", "component_siblings"}
-
-
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
-
-
-def demo_xyz(golden_dir):
-    from unseenobjectclustering_amd import io as uio
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    return uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0].numpy()
+from tests.tool_cases import BASE_KEYS, COMPONENT_KEYS, PLACEMENT_KEYS, PLANE_KEYS, demo_xyz, export
 
 
 def check_against_reference(z, xyz, radius_mm, G, cell_mm):

@@ -2,11 +2,6 @@
 objects.segment_objects.  The argument wiring and the arrays the tool adds are checked on the CPU (the tool's own
 planes_arrays and the helpers of support.py on a synthetic result); the command line and segment_objects on the GPU (the
 stage has no CPU path): tests/test_planes_gpu.py holds the stage against the reference."""
-import importlib
-import json
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -14,21 +9,10 @@ import pytest
 import torch
 
 from tests import planes_reference as P
+from tests.tool_cases import BASE_KEYS, demo_sample, export, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
 PLANES_KEYS = {"plane_count", "plane_normal", "plane_d", "plane_inliers", "plane_cos0", "plane_offset0", "plane_extent",
                "plane_index", "stands_on", "plane_support"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def synthetic(K=3):
@@ -81,10 +65,8 @@ def test_planes_arguments_and_arrays(tool):
 
 
 def _demo(golden_dir):
-    from unseenobjectclustering_amd import io as uio, networks, synth
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    sample = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)
+    from unseenobjectclustering_amd import networks, synth
+    sample = demo_sample(golden_dir)
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.calibrated_state_dict().items()}
     return sample, networks.seg_resnet34_8s_embedding(2, 64, sd).eval(), networks.seg_resnet34_8s_embedding(2, 64, sd).eval()
 
@@ -120,14 +102,7 @@ def test_segment_objects_with_planes_end_to_end(device, golden_dir):
 
 @pytest.mark.gpu
 def test_export_objects_planes_cli(device, golden_dir, tmp_path):
-    def export(out, *flags):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                            os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                           capture_output=True, text=True, timeout=600, cwd=ROOT)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return np.load(out / "000002_objects.npz")
-
-    z = export(tmp_path / "planes", "--planes", "4", "--planes-up", "0", "-1", "-1", "--placement", "0.05")
+    z = export(golden_dir, tmp_path / "planes", "--planes", "4", "--planes-up", "0", "-1", "-1", "--placement", "0.05")
     assert BASE_KEYS | PLANES_KEYS <= set(z.files) and "place_state" in z.files and "plane_found" not in z.files
     K = len(z["label"])
     H, W = z["label_map"].shape

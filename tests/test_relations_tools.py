@@ -1,35 +1,16 @@
 """Where users meet the object relations: the opt-in --relations / --relations-gap / --relations-min-pairs of
 tools/export_objects.py, alone and on tracked and component-split maps (GPU: the step has no CPU path)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import relations_reference as R
+from tests.tool_cases import BASE_KEYS, COMPONENT_KEYS, demo_xyz, export
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
 RELATION_KEYS = {"layer", "free", "order", "n_above", "edge", "front", "touch"}
-COMPONENT_KEYS = {"component_src", "component_area", "component_siblings"}
-
-
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
 
 
 def demo_z(golden_dir):
-    from unseenobjectclustering_amd import io as uio
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    return uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0, 2].numpy()
+    return demo_xyz(golden_dir)[2]
 
 
 def check_against_reference(z, depth, gap_mm, min_pairs):

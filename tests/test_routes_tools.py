@@ -2,11 +2,6 @@
 the arrays the tool adds are checked on the CPU (the tool's own route_arrays on a synthetic result); the command line on
 the GPU (the step has no CPU path): tests/test_routes_gpu.py holds the stage against the reference end to end,
 segment_objects(..., routes=True) included."""
-import importlib
-import json
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -14,21 +9,9 @@ import pytest
 import torch
 
 from tests import routes_reference as R
+from tests.tool_cases import BASE_KEYS, PLACEMENT_KEYS, demo_sample, export, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE_KEYS = {"frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
-             "obb_center", "obb_half", "offsets", "points", "pixel_index", "label_map"}
-PLACEMENT_KEYS = {"place_state", "place_dist2", "place_widest_cell", "place_widest_xyz"}
 ROUTE_KEYS = {"route_cost", "route_info", "route_path", "route_xyz", "route_length_m"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_route_arguments_and_arrays(tool):
@@ -63,14 +46,6 @@ def test_route_arguments_and_arrays(tool):
     assert rec["route_path"].shape == (0, 2) and rec["route_xyz"].shape == (0, 3) and np.isnan(rec["route_length_m"])
 
 
-def export(golden_dir, out, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(out), "--max-points", "500", *flags],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out / "000002_objects.npz")
-
-
 @pytest.mark.gpu
 def test_export_objects_route_cli(device, golden_dir, tmp_path):
     plain = export(golden_dir, tmp_path / "plain", "--placement", "0.03")
@@ -82,10 +57,8 @@ def test_export_objects_route_cli(device, golden_dir, tmp_path):
         assert np.array_equal(plain[k], z[k], equal_nan=k == "place_widest_xyz"), k
     assert z["route_cost"].shape == (256, 256) and z["route_info"].shape == (8,) and z["route_path"].shape[1] == 2
     # the stage on the exported label map, with the tool's defaults, against the reference
-    from unseenobjectclustering_amd import io as uio, placement, routes, support
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    xyz = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0].to(device)
+    from unseenobjectclustering_amd import placement, routes, support
+    xyz = demo_sample(golden_dir)["depth"][0].to(device)
     lab = torch.from_numpy(z["label_map"]).to(device)
     fitted = support.fit_plane(lab, xyz)
     placed = placement.free_space(lab, xyz, fitted)

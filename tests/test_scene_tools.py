@@ -2,29 +2,14 @@
 argument wiring, the arrays the tool adds and the drop mask it builds from --motion are checked on the CPU (the tool's
 own functions on results built from the reference); the command line on the GPU (the stage has no CPU path):
 tests/test_scene_gpu.py holds the stage against the reference."""
-import importlib
-import os
-import shutil
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 from tests import scene_reference as R
+from tests.tool_cases import demo_frames, demo_sample, run_tool, tool  # noqa: F401  (tool is a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MEMORY_KEYS = {"memory_state", "memory_owner", "memory_age", "memory_change", "memory_ids", "memory_info"}
-
-
-@pytest.fixture(scope="module")
-def tool():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        yield importlib.import_module("export_objects")
-    finally:
-        sys.path.remove(os.path.join(ROOT, "tools"))
 
 
 def test_memory_arguments_and_arrays(tool):
@@ -63,25 +48,14 @@ def test_memory_arguments_and_arrays(tool):
 
 @pytest.mark.gpu
 def test_export_objects_memory_cli(device, golden_dir, tmp_path):
-    frames = tmp_path / "frames"
-    frames.mkdir()
-    for k in (2, 3):                                               # the demo frame twice
-        for kind in ("color", "depth"):
-            shutil.copy(os.path.join(golden_dir, "demo", f"000002-{kind}.png"), frames / f"00000{k}-{kind}.png")
-    shutil.copy(os.path.join(golden_dir, "demo", "camera_params.json"), frames / "camera_params.json")
-    tool_py = os.path.join(ROOT, "tools", "export_objects.py")
-    common = [sys.executable, tool_py, "--imgdir", str(frames), "--max-points", "500"]
-    r = subprocess.run(common + ["--out", str(tmp_path / "bad"), "--memory", "5"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    frames = demo_frames(golden_dir, tmp_path / "frames")        # the demo frame twice
+    r = run_tool(frames, tmp_path / "bad", "--max-points", "500", "--memory", "5")
     assert r.returncode != 0 and "--memory needs --placement" in r.stderr
     for out, extra in (("plain", []), ("mem", ["--memory", "5"])):
-        r = subprocess.run(common + ["--out", str(tmp_path / out), "--placement", "0.05", "--grid", "128"] + extra, capture_output=True,
-                           text=True, timeout=600, cwd=ROOT)
+        r = run_tool(frames, tmp_path / out, "--max-points", "500", "--placement", "0.05", "--grid", "128", *extra)
         assert r.returncode == 0, r.stdout + r.stderr
-    import json
-    from unseenobjectclustering_amd import io as uio, placement, support
-    d = os.path.join(golden_dir, "demo")
-    cam = json.load(open(os.path.join(d, "camera_params.json")))
-    xyz = uio.read_sample(os.path.join(d, "000002-color.png"), os.path.join(d, "000002-depth.png"), cam)["depth"][0].to(device)
+    from unseenobjectclustering_amd import placement, support
+    xyz = demo_sample(golden_dir)["depth"][0].to(device)
     fitted, ref = None, R.new_state(1, 128)
     for t, stem in enumerate(("000002", "000003")):
         plain, mem = np.load(tmp_path / "plain" / f"{stem}_objects.npz"), np.load(tmp_path / "mem" / f"{stem}_objects.npz")

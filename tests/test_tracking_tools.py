@@ -4,8 +4,6 @@ flag the node publishes exactly what it published before (CPU); with it, a stub 
 every frame comes out with constant ids (GPU: the tracker has no CPU path)."""
 import importlib.util
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,9 +11,8 @@ import torch
 
 from tests import fake_ros
 from tests.test_ros_node import K, frame, load_node_module, stub_segment
+from tests.tool_cases import ROOT, run_tool
 from unseenobjectclustering_amd.fcn.config import cfg
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def load_tracked_module():
@@ -118,9 +115,7 @@ def test_track_publishes_constant_ids(rosmod, device):
 
 @pytest.mark.gpu
 def test_export_objects_track_cli(device, golden_dir, tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "export_objects.py"), "--imgdir",
-                        os.path.join(golden_dir, "demo"), "--out", str(tmp_path), "--max-points", "500", "--track"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = run_tool(os.path.join(golden_dir, "demo"), tmp_path, "--max-points", "500", "--track")
     assert r.returncode == 0, r.stdout + r.stderr
     z = np.load(tmp_path / "000002_objects.npz")
     raw, tracked = z["raw_label_map"], z["label_map"]

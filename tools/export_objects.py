@@ -133,6 +133,8 @@ import glob
 import json
 import os
 import sys
+from functools import cached_property
+from types import SimpleNamespace
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -141,23 +143,17 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from test_images import load_weights  # noqa: E402
-from unseenobjectclustering_amd import io as uio, networks, synth  # noqa: E402
+from unseenobjectclustering_amd import footprint, identity, io as uio, motion, networks, normals, routes, scene, synth  # noqa: E402
 from unseenobjectclustering_amd.fcn.config import cfg, cfg_from_file, network_mode  # noqa: E402
 from unseenobjectclustering_amd.components import split_components  # noqa: E402
 from unseenobjectclustering_amd.confidence import summarize  # noqa: E402
 from unseenobjectclustering_amd.elevation import heights, spot  # noqa: E402
-from unseenobjectclustering_amd import footprint  # noqa: E402
-from unseenobjectclustering_amd import normals  # noqa: E402
-from unseenobjectclustering_amd import routes  # noqa: E402
 from unseenobjectclustering_amd.grasp import candidates, pose  # noqa: E402
 from unseenobjectclustering_amd.objects import extract_objects, segment_objects  # noqa: E402
 from unseenobjectclustering_amd.placement import WIDEST, cell_to_camera, free_space, need2  # noqa: E402
 from unseenobjectclustering_amd.relations import relate  # noqa: E402
 from unseenobjectclustering_amd.support import choose_support, fit_plane, fit_planes, standing_objects, standing_on  # noqa: E402
 from unseenobjectclustering_amd.tracking import Tracker  # noqa: E402
-from unseenobjectclustering_amd import identity  # noqa: E402
-from unseenobjectclustering_amd import motion  # noqa: E402
-from unseenobjectclustering_amd import scene  # noqa: E402
 
 FIELDS = ("frame", "label", "pixels", "count", "box", "centroid", "cov", "aabb_min", "aabb_max", "eigenvalues", "axes",
           "obb_center", "obb_half", "offsets", "points", "pixel_index")
@@ -316,13 +312,9 @@ def moved_ids_mask(res, device):
     return mask
 
 
-def placement_arrays(labels, xyz, fitted, radius, grid, cell_mm, keep=None):
-    """The --placement arrays of one frame: the grid maps and the widest spot for a disc of `radius` metres.  keep: a list
-    that receives the placement result (--route goes on from it)."""
-    cell = cell_mm / 1000.0
-    placed = free_space(labels, xyz, fitted, grid=grid, cell=cell, queries=[(need2(radius, cell), 0, 0, WIDEST)])
-    if keep is not None:
-        keep.append(placed)
+def placement_arrays(placed):
+    """The --placement arrays of one frame: the grid maps of frame 0 of `placed` (a placement.free_space result whose
+    query 0 is the widest spot for the disc) and that spot."""
     ans = placed.answers[0, 0].cpu().numpy()
     spot = cell_to_camera(placed, 0, ans[0], ans[1]) if ans[0] >= 0 else np.full(3, np.nan)
     return {"place_state": placed.state[0].cpu().numpy(), "place_dist2": placed.dist2[0].cpu().numpy(),
@@ -387,37 +379,30 @@ def build_parser():
     return ap
 
 
+CHECKS = (       # what parse_args refuses, in the order it looks: (whether the command line is wrong, what ap.error then says)
+    (lambda a: a.confidence is not None and not 0.0 <= a.confidence <= 1.0, "--confidence WEAK: a margin in 0..1"),
+    (lambda a: a.reid and not a.track, "--reid needs --track (identities are kept per track)"),
+    (lambda a: a.reid and not (0.0 < a.reid_min_sim <= 1.0 and 0.0 <= a.reid_min_size <= 1.0 and a.reid_max_lost >= 0),
+     "--reid-min-sim in (0, 1], --reid-min-size in [0, 1], --reid-max-lost not negative"),
+    (lambda a: a.motion and not a.track, "--motion needs --track (an object is followed by the id it keeps)"),
+    (lambda a: a.motion and not (1 <= a.motion_angles <= 64 and 0 <= a.motion_radius <= 16), "--motion-angles in 1..64, --motion-radius in 0..16"),
+    (lambda a: a.memory is not None and a.placement is None, "--memory needs --placement (it remembers the grid that --placement computes)"),
+    (lambda a: a.memory is not None and not 0 <= a.memory <= 32767, "--memory AGE: AGE in 0..32767"),
+    (lambda a: a.planes is not None and not 1 <= a.planes <= 8, "--planes K: K in 1..8"),
+    (lambda a: a.planes is not None and a.plane, "--planes and --plane both write plane_* arrays: give one of them"),
+    (lambda a: a.planes_up is not None and a.planes is None, "--planes-up needs --planes"),
+    (lambda a: a.planes_up is not None and not any(a.planes_up), "--planes-up X Y Z: not the zero vector"),
+    (lambda a: a.route is not None and a.placement is None, "--route needs --placement (it routes to the spot that --placement finds)"),
+)
+
+
 def parse_args(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.confidence is not None and not 0.0 <= args.confidence <= 1.0:
-        ap.error("--confidence WEAK: a margin in 0..1")
-    if args.reid and not args.track:
-        ap.error("--reid needs --track (identities are kept per track)")
-    if args.reid and not (0.0 < args.reid_min_sim <= 1.0 and 0.0 <= args.reid_min_size <= 1.0 and args.reid_max_lost >= 0):
-        ap.error("--reid-min-sim in (0, 1], --reid-min-size in [0, 1], --reid-max-lost not negative")
-    if args.motion and not args.track:
-        ap.error("--motion needs --track (an object is followed by the id it keeps)")
-    if args.motion and not (1 <= args.motion_angles <= 64 and 0 <= args.motion_radius <= 16):
-        ap.error("--motion-angles in 1..64, --motion-radius in 0..16")
-    if args.memory is not None:
-        if args.placement is None:
-            ap.error("--memory needs --placement (it remembers the grid that --placement computes)")
-        if not 0 <= args.memory <= 32767:
-            ap.error("--memory AGE: AGE in 0..32767")
-    if args.planes is not None:
-        if not 1 <= args.planes <= 8:
-            ap.error("--planes K: K in 1..8")
-        if args.plane:
-            ap.error("--planes and --plane both write plane_* arrays: give one of them")
-    if args.planes_up is not None:
-        if args.planes is None:
-            ap.error("--planes-up needs --planes")
-        if not any(args.planes_up):
-            ap.error("--planes-up X Y Z: not the zero vector")
+    for wrong, message in CHECKS:
+        if wrong(args):
+            ap.error(message)
     if args.route is not None:
-        if args.placement is None:
-            ap.error("--route needs --placement (it routes to the spot that --placement finds)")
         try:
             args.route = (int(args.route[0]), float(args.route[1]))
         except ValueError:
@@ -425,6 +410,113 @@ def parse_args(argv=None):
         if not 1 <= args.route[0] <= 127 or args.route[1] < 0:
             ap.error("--route ID RADIUS_M: ID in 1..127, RADIUS_M not negative")
     return args
+
+
+class Frame:
+    """One frame on its way through the stages.  `final` (host) and `labels` (device) are the label map the stages pass on,
+    from `record` on the exported one as int32; it and the XYZ planes go to the device once, here.  The methods below the
+    properties are stages: they take the stream's state and args and return the arrays they add to the file, if any."""
+
+    def __init__(self, args, sample, final, objs, conf):
+        self.args, self.sample, self.final, self.objs, self.conf, self.rec = args, sample, final, objs, conf, {}
+        self.xyz1 = sample["depth"][:1].to(cfg.device)     # [1,3,H,W], as extract_objects and the identifier take them
+        self.labels, self.xyz = final.to(cfg.device), self.xyz1[0]
+
+    @cached_property
+    def several(self):
+        return fit_planes(self.labels, self.xyz, max_planes=self.args.planes)
+
+    @cached_property
+    def plane(self):
+        """The support plane of the exported label map, fitted when a stage first asks: under --planes the one most objects stand on."""
+        if self.args.planes is None:
+            return fit_plane(self.labels, self.xyz)
+        return self.several.plane(choose_support(self.several, up=None if self.args.planes_up is None else tuple(self.args.planes_up)))
+
+    @cached_property
+    def grid(self):
+        """The table grid of --placement, --route, --grasp, --elevation and --putdown on that plane, with the widest-spot
+        query of --placement where that is given: the grid itself does not depend on the queries."""
+        a, cell = self.args, self.args.cell_mm / 1000.0
+        queries = None if a.placement is None else [(need2(a.placement, cell), 0, 0, WIDEST)]
+        return free_space(self.labels, self.xyz, self.plane, grid=a.grid, cell=cell, queries=queries)
+
+    def split(self, stream, args):
+        split, table, _ = split_components(self.labels, connectivity=8, min_area=args.min_area, mode=args.components)
+        if stream.tracker is None:
+            self.objs = extract_objects(split, self.xyz1, max_points_per_object=args.max_points)
+        self.comp, self.labels, self.final = table[0], split, split.cpu()
+
+    def track(self, stream, args):
+        self.raw_map = self.final.numpy().astype(np.int32)
+        self.labels = stream.tracker.update(self.labels)
+        self.objs = extract_objects(self.labels, self.xyz1, max_points_per_object=args.max_points)
+        self.final = self.labels.cpu()
+
+    def record(self, stream, args):
+        self.labels = self.ids_map = self.labels.to(torch.int32)     # ids_map: the ids --motion and --memory follow
+        self.ids = self.objs.label.long()
+        self.id_list = self.ids.cpu().tolist()
+        return {**{k: getattr(self.objs, k).cpu().numpy() for k in FIELDS}, "label_map": self.final.numpy().astype(np.int32)}
+
+    def identify(self, stream, args):       # per row: the identity entry of its track slot and that identity's running number
+        self.ids_map = stream.identifier.update(self.labels, stream.tracker, identity.image_u8(self.sample).to(cfg.device), self.xyz1)
+        entries = stream.identifier.lut[0][self.ids]
+        return {"identity": entries.cpu().numpy(), "identity_pid": stream.identifier.table[0, :, 0][entries.long()].cpu().numpy(),
+                "identity_map": self.ids_map.cpu().numpy().astype(np.int32)}
+
+    def follow(self, stream, args):
+        """The follower keeps a plane of its own for the whole stream, that of the first frame's id map (the camera stands
+        still); the first frame has nothing to be registered against."""
+        first = stream.follower is None
+        if first:
+            stream.follower = motion.Follower(fit_plane(self.ids_map, self.xyz), args.grid, args.cell_mm / 1000.0, args.motion_angles, args.motion_radius)
+        stream.moved = stream.follower.update(self.ids_map, self.xyz)
+        return None if first else motion_arrays(stream.moved)
+
+    def component_rows(self, stream, args):     # per row: the component its pixels came from
+        ids = self.ids
+        if stream.tracker is not None:          # through the tracker's lut: track slot -> the split map's id
+            inverse = torch.zeros(128, dtype=torch.int64, device=cfg.device)
+            inverse[stream.tracker.lut[0].long()] = torch.arange(128, device=cfg.device)
+            ids = inverse[ids]
+        rows = self.comp[ids].cpu().numpy()
+        return {"component_src": rows[:, 0], "component_area": rows[:, 1], "component_siblings": rows[:, 3]}
+
+    def route(self, stream, args):
+        spot = self.rec["place_widest_cell"]
+        goal = (int(spot[0]), int(spot[1])) if spot[0] >= 0 else None
+        return route_arrays(routes.plan(self.grid, [routes.of_object(self.grid, self.plane, 0, args.route[0], goal, radius_m=args.route[1])]))
+
+    def remember(self, stream, args):
+        """The memory keeps the support plane of the first frame for the whole stream (the camera stands still) and, beside
+        --motion, holds the ids that follows: a free_space of its own, which self.grid equals on the first frame alone."""
+        if stream.memory_plane is None:
+            stream.memory_plane = self.plane
+        seen = free_space(self.ids_map if args.motion else self.labels, self.xyz, stream.memory_plane, grid=args.grid, cell=args.cell_mm / 1000.0)
+        return memory_arrays(stream.memory.update(seen, drop=moved_ids_mask(stream.moved, cfg.device) if args.motion else None))
+
+
+STAGES = (      # in the order they run, which is the order of the keys in the file, each with the option that enables it
+    ("components", Frame.split),
+    ("track", Frame.track),
+    (None, Frame.record),
+    ("reid", Frame.identify),
+    ("track", lambda f, s, a: {"raw_label_map": f.raw_map, "track_uid": s.tracker.table[0, :, 0][f.ids].cpu().numpy()}),
+    ("motion", Frame.follow),
+    ("components", Frame.component_rows),
+    ("planes", lambda f, s, a: planes_arrays(f.several, f.ids, a.planes_up)),
+    ("plane", lambda f, s, a: plane_arrays(f.plane, f.ids, a.min_height)),
+    ("placement", lambda f, s, a: placement_arrays(f.grid)),
+    ("route", Frame.route),
+    ("memory", Frame.remember),
+    ("grasp", lambda f, s, a: grasp_arrays(candidates(f.grid, angles=a.grasp_angles, offsets=a.grasp_offsets, max_open=a.grasp), f.id_list)),
+    ("elevation", lambda f, s, a: elevation_arrays(heights(f.labels, f.xyz, f.grid, step=a.elevation, min_pts=a.elevation_min_pts), f.id_list, a.placement)),
+    ("putdown", lambda f, s, a: putdown_arrays(footprint.fit(f.grid, [footprint.rect(*a.putdown, a.cell_mm)], angles=a.putdown_angles))),
+    ("relations", lambda f, s, a: relation_arrays(relate(f.labels, f.xyz, connectivity=8, gap=a.relations_gap, min_pairs=a.relations_min_pairs), f.ids)),
+    ("confidence", lambda f, s, a: confidence_arrays(summarize(f.labels, f.conf.margin, weak=a.confidence), f.id_list, f.conf.margin)),
+    ("normals", lambda f, s, a: normals_arrays(normals.estimate(f.xyz, f.labels, f.plane), f.id_list)),
+)
 
 
 def main():
@@ -444,117 +536,24 @@ def main():
     network = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained)).eval()
     network_crop = networks.seg_resnet34_8s_embedding(2, cfg.TRAIN.NUM_UNITS, load_weights(args.pretrained_crop)).eval()
     os.makedirs(args.out, exist_ok=True)
-    tracker = Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None
-    identifier = identity.Identifier(min_sim=args.reid_min_sim, min_size=args.reid_min_size, max_lost=args.reid_max_lost) if args.reid else None
-    follower = None
-    memory = scene.Memory(args.grid, max_age=args.memory, device=cfg.device) if args.memory is not None else None
-    memory_plane = None
+    stream = SimpleNamespace(        # what lasts from frame to frame; the follower and the memory's plane are made on the first one
+        tracker=Tracker(min_iou=args.track_min_iou, max_age=args.track_max_age) if args.track else None,
+        identifier=identity.Identifier(min_sim=args.reid_min_sim, min_size=args.reid_min_size, max_lost=args.reid_max_lost) if args.reid else None,
+        memory=scene.Memory(args.grid, max_age=args.memory, device=cfg.device) if args.memory is not None else None,
+        follower=None, memory_plane=None, moved=None)
+    stages = [run for option, run in STAGES if option is None or (getattr(args, option) is not None and getattr(args, option) is not False)]
     for fc, fd in zip(colors, depths):
         sample = uio.read_sample(fc, fd, cam)
-        conf = None
-        if args.confidence is not None:
-            out_label, out_refined, objs, conf = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points,
-                                                                 confidence=True, confidence_args=dict(weak=args.confidence))
-        else:
-            out_label, out_refined, objs = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points)
-        final = out_refined if out_refined is not None else out_label
-        track_uid = raw_map = comp = moved = None
-        if args.components is not None:
-            split, table, _ = split_components(final[0].to(cfg.device), connectivity=8, min_area=args.min_area,
-                                               mode=args.components)
-            if tracker is None:
-                objs = extract_objects(split, sample["depth"][:1].to(cfg.device), max_points_per_object=args.max_points)
-            comp, final = table[0], split[None].cpu()
-        if tracker is not None:
-            raw_map = final[0].numpy().astype(np.int32)
-            tracked = tracker.update(final[0].to(cfg.device))
-            objs = extract_objects(tracked, sample["depth"][:1].to(cfg.device), max_points_per_object=args.max_points)
-            track_uid = tracker.table[0, :, 0][objs.label.long()].cpu().numpy()
-            final = tracked[None].cpu()
-        rec = {k: getattr(objs, k).cpu().numpy() for k in FIELDS}
-        rec["label_map"] = final[0].numpy().astype(np.int32)
-        if identifier is not None:          # per row: the identity entry of its track slot and that identity's running number
-            who = identifier.update(tracked, tracker, identity.image_u8(sample).to(cfg.device), sample["depth"][:1].to(cfg.device))
-            entries = identifier.lut[0][objs.label.long()]
-            rec["identity"], rec["identity_pid"] = entries.cpu().numpy(), identifier.table[0, :, 0][entries.long()].cpu().numpy()
-            rec["identity_map"] = who.cpu().numpy().astype(np.int32)
-        if tracker is not None:
-            rec["raw_label_map"], rec["track_uid"] = raw_map, track_uid
-        if args.motion:
-            ids_map = torch.from_numpy(rec["identity_map"] if identifier is not None else rec["label_map"]).to(cfg.device)
-            if follower is None:            # the plane of the first frame serves the whole stream: the camera stands still
-                follower = motion.Follower(fit_plane(ids_map, sample["depth"][0].to(cfg.device)), grid=args.grid, cell=args.cell_mm / 1000.0,
-                                           angles=args.motion_angles, radius=args.motion_radius)
-                follower.update(ids_map, sample["depth"][0].to(cfg.device))
-            else:
-                moved = follower.update(ids_map, sample["depth"][0].to(cfg.device))
-                rec.update(motion_arrays(moved))
-        if comp is not None:           # per row: the component its pixels came from (through the tracker's lut when tracking)
-            ids = objs.label.long()
-            if tracker is not None:    # track slot -> the split map's id
-                inverse = torch.zeros(128, dtype=torch.int64, device=cfg.device)
-                inverse[tracker.lut[0].long()] = torch.arange(128, device=cfg.device)
-                ids = inverse[ids]
-            rows = comp[ids].cpu().numpy()
-            rec["component_src"], rec["component_area"], rec["component_siblings"] = rows[:, 0], rows[:, 1], rows[:, 3]
-        placed = None                       # the grid of --grasp / --elevation, where one of them computes it: --putdown reuses it
-        if args.plane or args.placement is not None or args.grasp is not None or args.elevation is not None or args.putdown is not None \
-                or args.normals:
-            fitted = fit_plane(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device)) \
-                if args.planes is None else None
-        if args.planes is not None:
-            several = fit_planes(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
-                                 max_planes=args.planes)
-            rec.update(planes_arrays(several, objs.label.long(), args.planes_up))
-            fitted = several.plane(choose_support(several, up=None if args.planes_up is None else tuple(args.planes_up)))
-        if args.plane:
-            rec.update(plane_arrays(fitted, objs.label.long(), args.min_height))
-        if args.placement is not None:
-            kept = []
-            rec.update(placement_arrays(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
-                                        fitted, args.placement, args.grid, args.cell_mm, keep=kept))
-            if args.route is not None:
-                spot = rec["place_widest_cell"]
-                query = routes.of_object(kept[0], fitted, 0, args.route[0], (int(spot[0]), int(spot[1])) if spot[0] >= 0 else None,
-                                         radius_m=args.route[1])
-                rec.update(route_arrays(routes.plan(kept[0], [query])))
-        if memory is not None:              # the plane of the first frame serves the whole stream: the camera stands still
-            memory_plane = fitted if memory_plane is None else memory_plane
-            seen = free_space(torch.from_numpy(rec["identity_map"] if args.motion and identifier is not None else rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), memory_plane,
-                              grid=args.grid, cell=args.cell_mm / 1000.0)
-            rec.update(memory_arrays(memory.update(seen, drop=moved_ids_mask(moved, cfg.device) if args.motion else None)))
-        if args.grasp is not None:
-            placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
-                                grid=args.grid, cell=args.cell_mm / 1000.0)
-            grasped = candidates(placed, angles=args.grasp_angles, offsets=args.grasp_offsets, max_open=args.grasp)
-            rec.update(grasp_arrays(grasped, objs.label.long().cpu().tolist()))
-        if args.elevation is not None:
-            placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
-                                grid=args.grid, cell=args.cell_mm / 1000.0)
-            raised = heights(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), placed,
-                             step=args.elevation, min_pts=args.elevation_min_pts)
-            rec.update(elevation_arrays(raised, objs.label.long().cpu().tolist(), args.placement))
-        if args.putdown is not None:
-            if placed is None:
-                placed = free_space(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device), fitted,
-                                    grid=args.grid, cell=args.cell_mm / 1000.0)
-            rec.update(putdown_arrays(footprint.fit(placed, [footprint.rect(args.putdown[0], args.putdown[1], args.cell_mm)],
-                                                    angles=args.putdown_angles)))
-        if args.relations:
-            related = relate(torch.from_numpy(rec["label_map"]).to(cfg.device), sample["depth"][0].to(cfg.device),
-                             connectivity=8, gap=args.relations_gap, min_pairs=args.relations_min_pairs)
-            rec.update(relation_arrays(related, objs.label.long()))
-        if conf is not None:
-            summary = summarize(torch.from_numpy(rec["label_map"]).to(cfg.device), conf.margin, weak=args.confidence)
-            rec.update(confidence_arrays(summary, objs.label.long().cpu().tolist(), conf.margin))
-        if args.normals:
-            estimated = normals.estimate(sample["depth"][0].to(cfg.device), torch.from_numpy(rec["label_map"]).to(cfg.device), fitted)
-            rec.update(normals_arrays(estimated, objs.label.long().cpu().tolist()))
+        confident = dict(confidence=True, confidence_args=dict(weak=args.confidence)) if args.confidence is not None else {}
+        out_label, out_refined, objs, *conf = segment_objects(sample, network, network_crop, max_points_per_object=args.max_points, **confident)
+        frame = Frame(args, sample, (out_refined if out_refined is not None else out_label)[0], objs, conf[0] if conf else None)
+        for run in stages:
+            frame.rec.update(run(frame, stream, args) or {})
         stem = os.path.basename(fc)
         stem = stem[:-len("-color.png")] if stem.endswith("-color.png") else os.path.splitext(stem)[0]
         name = os.path.join(args.out, stem + "_objects.npz")
-        np.savez(name, **rec)
-        print("save objects to {}  ({} objects, {} points)".format(name, len(objs), int(objs.points.shape[0])))
+        np.savez(name, **frame.rec)
+        print("save objects to {}  ({} objects, {} points)".format(name, len(frame.objs), int(frame.objs.points.shape[0])))
 
 
 if __name__ == "__main__":
