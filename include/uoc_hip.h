@@ -192,10 +192,14 @@ int uoc_net_forward(uoc_net *net, const float *d_rgb, const float *d_xyz, int B,
  * uoc_conv2d_nhwc runs the direct implicit-GEMM kernel.  uoc_conv2d_nhwc_algo names the algorithm explicitly (no
  * environment variable decides it): UOC_CONV_DIRECT, or UOC_CONV_WINOGRAD4 = F(4x4,3x3) as the network runs its 3x3
  * stride-1 layers from 64 channels up (UOC_EINVAL if the shape is not eligible).  The Winograd path keeps its transformed weights and
- * scratch in buffers owned by this entry: one caller thread at a time. */
+ * scratch in buffers owned by this entry: one caller thread at a time.
+ * UOC_CONV_WINOGRAD4 runs, as the network does, the plan in which a tile whose fourth output row / column lies outside the
+ * image skips the frequency planes that only those outputs read; UOC_CONV_WINOGRAD4_DENSE runs the same kernels with every
+ * plane over every tile.  The two give the same bits; the tile entries below take either (same list, cfg = BN, bm). */
 #define UOC_CONV_DIRECT 0
 #define UOC_CONV_WINOGRAD4 4
 #define UOC_CONV_WINOGRAD4_BF16X3 5   /* EXPERIMENT: the same with the split-precision plane GEMM (see uoc_net_set_split_precision) */
+#define UOC_CONV_WINOGRAD4_DENSE 6    /* tests: UOC_CONV_WINOGRAD4's kernels on the dense plan, where every frequency plane covers every tile; the same bits */
 int uoc_conv2d_nhwc(const float *d_in, const float *d_w, const float *d_bias, const float *d_res, float *d_out,
                     int G, int B, int H, int W, int Cin, int Cout, int K, int stride, int dil, int pad, int relu,
                     void *stream);

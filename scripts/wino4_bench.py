@@ -2,7 +2,10 @@
 per launch set in stage 1, ~28 crops in stage 2, one frame alone) next to the direct kernel.  Times from the library's
 per-kernel-class HIP events; TF = algorithmic (direct 3x3) flops over the summed time of the layer's kernels.
 WINO4_BENCH_SHAPES=<substring> restricts the shapes.  (The A/B arms of rounds 3-5 — waves per block, tile overrides, planes
-as groups, F(2x2) — needed the development build that round 6 removed; their results are in HISTORY.md.)"""
+as groups, F(2x2) — needed the development build that round 6 removed; their results are in HISTORY.md.)
+The "F4 dense plan" arm runs the same kernels with every frequency plane over every tile (UOC_CONV_WINOGRAD4_DENSE): what the
+shipped arm saves by skipping the planes partial tiles never read (profiles/wino4_skip_planes.md).  WINO4_BENCH_ITERS=<n>
+launches per measurement (default 10)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,10 +24,12 @@ shapes = [  # name, B, H, W, C, dil
     ("s2 layer3 256 d2 28x28x28", 28, 28, 28, 256, 2),
     ("s2 layer2 128 d1 28x28x28", 28, 28, 28, 128, 1),
     ("s1 layer4 512 d4 1x60x80", 1, 60, 80, 512, 4),
+    ("s2 layer4 512 d4 7x28x28", 7, 28, 28, 512, 4),      # one frame alone: ~7 crops
+    ("s2 layer3 256 d2 7x28x28", 7, 28, 28, 256, 2),
 ]
 
 
-def measure(B, H, W, C, dil, algo, env, iters=10):
+def measure(B, H, W, C, dil, algo, env, iters=int(os.environ.get("WINO4_BENCH_ITERS", "10"))):
     for k in KNOBS:
         os.environ.pop(k, None)
     os.environ.update(env)
@@ -50,6 +55,8 @@ def measure(B, H, W, C, dil, algo, env, iters=10):
 
 
 arms = [("F4 shipped", 4, {})]
+if hasattr(_native, "CONV_WINOGRAD4_DENSE"):
+    arms.append(("F4 dense plan", _native.CONV_WINOGRAD4_DENSE, {}))
 arms.append(("direct", 0, {}))
 for name, B, H, W, C, dil in shapes:
     if os.environ.get("WINO4_BENCH_SHAPES") and os.environ["WINO4_BENCH_SHAPES"] not in name:
@@ -67,7 +74,7 @@ for name, B, H, W, C, dil in shapes:
             print(f"   {label:24s} failed: {e}")
             continue
         same = ""
-        if algo == 4 and "planes" not in label:        # every plane-GEMM arm must give the same bits
+        if algo != 0 and "planes" not in label:        # every plane-GEMM arm must give the same bits
             if ref is None:
                 ref = out.clone()
             same = "  bit-identical" if torch.equal(ref, out) else "  DIFFERS FROM THE FIRST F4 ARM"

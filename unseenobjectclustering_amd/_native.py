@@ -283,7 +283,7 @@ def lib():
     return _lib
 
 
-CONV_DIRECT, CONV_WINOGRAD4, CONV_WINOGRAD4_BF16X3 = 0, 4, 5       # include/uoc_hip.h: UOC_CONV_*
+CONV_DIRECT, CONV_WINOGRAD4, CONV_WINOGRAD4_BF16X3, CONV_WINOGRAD4_DENSE = 0, 4, 5, 6       # include/uoc_hip.h: UOC_CONV_*
 
 
 def config_fingerprint() -> int:

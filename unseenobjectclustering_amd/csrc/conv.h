@@ -38,11 +38,16 @@ struct W4Tile {
 };
 // (BN, BM) pairs of the fp32 plane GEMM (split = false) or of the split-precision one; what the static model picks
 int wino4_tile_list(bool split, int *out_pairs, int cap);
-void wino4_tile_choice(bool split, int NT, int Cout, int planes, int *bn, int *bm);
+// (dense: for the dense plan instead of the skipping one the network runs; the split-precision GEMM is always dense)
+void wino4_tile_choice(bool split, bool dense, int B, int H, int W, int d, int Cout, int G, int *bn, int *bm);
 int wino4_split_tile_list(int *out_pairs, int cap);
 void wino4_split_tile_choice(int NT, int Cout, int planes, int *bn, int *bm);
 // the shared cost model over a tile list {BM, BN} (the first of equal costs wins; bm / bn keep their value if no tile admits
-// Cout) and the grid of a plane GEMM with a given tile
+// Cout) and the grid of a plane GEMM with a given tile.  Work items are counted over the rows each plane covers (Wino4Rows,
+// csrc/wino4_math.h); the forms that take NT alone are the dense plan's: every one of `planes` planes covers all NT rows.
+struct Wino4Rows;
+void wino4_pick_tile(const int (*tiles)[2], int n, const Wino4Rows &rows, int Cout, int G, int &bm, int &bn);
+int wino4_plane_grid(const Wino4Rows &rows, int Cout, int G, int bm, int bn);
 void wino4_pick_tile(const int (*tiles)[2], int n, int NT, int Cout, int planes, int &bm, int &bn);
 int wino4_plane_grid(int NT, int Cout, int planes, int bm, int bn);
 
@@ -57,8 +62,9 @@ int launch_wino4_weights(const float *w, float *U, int G, int Cout, int Cin, hip
 // launch_wino4_split_weights ([G*36][3][Cout][Cin] bf16) — an experiment, never the default
 // tile != nullptr: the plane GEMM runs exactly that instantiation (UOC_EINVAL if there is none or Cout % bn != 0) instead of
 // the static model's choice; pair loop and grid follow the library's own rules for the tile
+// dense: the dense plan (natural tile order, every plane covers every tile) instead of the skipping plan; same kernels, same bits
 int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3 = nullptr,
-                      const W4Tile *tile = nullptr);
+                      const W4Tile *tile = nullptr, bool dense = false);
 int launch_wino4_split_weights(const float *U, unsigned short *U3, int G, int Cout, int Cin, hipStream_t st);
 int launch_wino4_slice_split(const ConvParams &p0, int Bg, int b0, const unsigned short *U3, float *ws, hipStream_t st,
                              const W4Tile *tile = nullptr);

@@ -456,7 +456,7 @@ static int conv2d_entry(const float *d_in, const float *d_w, const float *d_bias
   // one caller thread at a time, as the header says — the mutex makes a violation slow instead of wrong
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
-  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_BF16X3) {
+  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_DENSE || algo == UOC_CONV_WINOGRAD4_BF16X3) {
     UOC_REQUIRE(wino4_eligible(p), "conv2d: shape not eligible for Winograd F(4x4,3x3)");
     if (tile) {   // refuse an unknown tile before any device work
       int pairs[2 * 32];
@@ -491,7 +491,7 @@ static int conv2d_entry(const float *d_in, const float *d_w, const float *d_bias
       if (int rc = launch_wino4_split_weights(U4, U3, G, Cout, Cin, st)) return rc;
       return launch_wino4_conv(p, U4, ws4, st, U3, wt);
     }
-    return launch_wino4_conv(p, U4, ws4, st, nullptr, wt);
+    return launch_wino4_conv(p, U4, ws4, st, nullptr, wt, algo == UOC_CONV_WINOGRAD4_DENSE);
   }
   set_error("conv2d: unknown algorithm %d", algo);
   return UOC_EINVAL;
@@ -514,7 +514,7 @@ int uoc_conv2d_nhwc_tile(const float *d_in, const float *d_w, const float *d_bia
 int uoc_conv2d_tile_list(int algo, int32_t *out_pairs, int cap) {
   UOC_REQUIRE(cap >= 0 && (out_pairs || cap == 0), "tile list: null array");
   if (algo == UOC_CONV_DIRECT) return conv_tile_list(out_pairs, cap);
-  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_BF16X3)
+  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_DENSE || algo == UOC_CONV_WINOGRAD4_BF16X3)
     return wino4_tile_list(algo == UOC_CONV_WINOGRAD4_BF16X3, out_pairs, cap);
   set_error("tile list: unknown algorithm %d", algo);
   return UOC_EINVAL;
@@ -527,10 +527,10 @@ int uoc_conv2d_tile_choice(int G, int B, int H, int W, int Cin, int Cout, int K,
   UOC_REQUIRE(G >= 1 && B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && stride >= 1 && dil >= 1, "tile choice: bad shape");
   const ConvParams p = entry_params(G, B, H, W, Cin, Cout, K, stride, dil, K == 3 ? dil : 0, 0);
   if (algo == UOC_CONV_DIRECT) return conv_tile_choice(p, cfg, bm, family_bm);
-  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_BF16X3) {
+  if (algo == UOC_CONV_WINOGRAD4 || algo == UOC_CONV_WINOGRAD4_DENSE || algo == UOC_CONV_WINOGRAD4_BF16X3) {
     UOC_REQUIRE(wino4_eligible(p), "tile choice: shape not eligible for Winograd F(4x4,3x3)");
     int bn_ = 0, bm_ = 0;
-    wino4_tile_choice(algo == UOC_CONV_WINOGRAD4_BF16X3, wino4_num_tiles(B, H, W, dil), Cout, 36 * G, &bn_, &bm_);
+    wino4_tile_choice(algo == UOC_CONV_WINOGRAD4_BF16X3, algo == UOC_CONV_WINOGRAD4_DENSE, B, H, W, dil, Cout, G, &bn_, &bm_);
     *cfg = bn_;
     *bm = bm_;
     return UOC_OK;

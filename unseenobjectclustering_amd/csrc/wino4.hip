@@ -42,11 +42,13 @@ __global__ __launch_bounds__(256) void wino4_weight_kernel(const float *__restri
   }
 }
 
-template <int VEC>
+// PLAN: 1 = the dense plan, 0 = the skipping plan (wino4_math.h): one kernel source, instantiated once per plan
+template <int VEC, int PLAN>
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float *__restrict__ in, float *__restrict__ V,
                                                           Wino4Geom geo, int G, int C) {
   const int CV = C / VEC;
-  const long total = (long)G * geo.NT * CV;
+  const int nwork = PLAN == 1 ? geo.NT : geo.end[3];   // tiles with an output inside the image (the dense plan: all)
+  const long total = (long)G * nwork * CV;
 #ifndef W4_IN_XCD
 #define W4_IN_XCD 1
 #endif
@@ -56,23 +58,24 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float *__restric
   const long vblock = W4_IN_XCD ? (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : (long)blockIdx.x;
   for (long idx = vblock * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int cv = (int)(idx % CV);
-    const int tau = (int)((idx / CV) % geo.NT);
-    const int g = (int)(idx / ((long)CV * geo.NT));
-    wino4_input_body<VEC>(in, V, geo, C, g, tau, cv);
+    const int tau = (int)((idx / CV) % nwork);
+    const int g = (int)(idx / ((long)CV * nwork));
+    wino4_input_body<VEC, PLAN>(in, V, geo, C, g, tau, cv);
   }
 }
 
-template <int VEC>
+template <int VEC, int PLAN>
 __global__ __launch_bounds__(256, W4_OUT_MIN_BLOCKS) void wino4_output_kernel(const float *__restrict__ M, const float *__restrict__ bias,
                                                            const float *__restrict__ res, float *__restrict__ out,
                                                            Wino4Geom geo, int G, int Cout, int relu) {
   const int CV = Cout / VEC;
-  const long total = (long)G * geo.NT * CV;
+  const int nwork = PLAN == 1 ? geo.NT : geo.end[3];
+  const long total = (long)G * nwork * CV;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int cv = (int)(idx % CV);
-    const int tau = (int)((idx / CV) % geo.NT);
-    const int g = (int)(idx / ((long)CV * geo.NT));
-    wino4_output_body<VEC>(M, bias, res, out, geo, Cout, relu, g, tau, cv);
+    const int tau = (int)((idx / CV) % nwork);
+    const int g = (int)(idx / ((long)CV * nwork));
+    wino4_output_body<VEC, PLAN>(M, bias, res, out, geo, Cout, relu, g, tau, cv);
   }
 }
 
@@ -89,7 +92,8 @@ __device__ __forceinline__ f32x4 w4mfma(float a, float b, f32x4 c) {
 // per chunk, XOR swizzle on the source slot and on the fragment read), fed through raw buffer descriptors: per DMA one
 // loop-invariant lane offset (row of the block tile) + one scalar offset (plane, cin chunk).
 //
-// Work items are ordered (plane, m-tile, n-tile).  Each XCD takes a contiguous eighth of the list (so that the rows of
+// Work items are ordered (plane, m-tile, n-tile); a plane's m-tiles cover the rows [lo, hi) of the tile order that read the
+// plane (wino4_plane_rows: all NT rows in the dense plan), so the four kinds of planes have four item counts.  Each XCD takes a contiguous eighth of the list (so that the rows of
 // one plane are pulled into ONE L2) and deals its items round-robin to its blocks: at any time the blocks of an XCD
 // work on neighbouring items = the same one or two planes.
 // -DUOC_W4_ABLATE=n (dev builds only, scripts/w4_ablate.sh; the results are WRONG, only the time means something): 1 = no
@@ -119,7 +123,7 @@ __device__ __forceinline__ void w4_wait_vmcnt() {
 template <int BM, int BN, bool PAIR, int NW>
 __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__restrict__ V, const float *__restrict__ U,
                                                              float *__restrict__ Mo, int NT, int Cin, int Cout, int planes,
-                                                             int mtiles, int nt_shift) {
+                                                             Wino4Rows rows, int nt_shift) {
   static_assert(NW == 8 || NW == 4, "waves per block");
   constexpr int WAVES_N = NW / 2;   // 2 (m) x WAVES_N (n)
   constexpr int WM = BM / 2, WN = BN / WAVES_N;
@@ -132,9 +136,17 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
 
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [3 | 4][R][32]
 
+  // A plane covers the rows [lo, hi) of the tile order that read it (wino4_plane_rows): four kinds of planes, four item
+  // counts.  All of this is scalar work from plane % 36.
   const int ntiles = 1 << nt_shift;
-  const int per_plane = mtiles << nt_shift;
-  const int total = planes * per_plane;
+  const int lo5 = rows.lo5, hi0 = rows.hi[0], hi1 = rows.hi[1], hi2 = rows.hi[2], hi3 = rows.hi[3];
+  const int pp0 = ((hi0 + BM - 1) / BM) << nt_shift, pp1 = ((hi1 + BM - 1) / BM) << nt_shift,
+            pp2 = ((hi2 - lo5 + BM - 1) / BM) << nt_shift, pp3 = ((hi3 - lo5 + BM - 1) / BM) << nt_shift;
+#define W4_KIND_SEL(XI, A, B, C, D) ((XI) < 30 ? ((0x820820820ull >> (XI)) & 1 ? (B) : (A)) : ((XI) == 35 ? (D) : (C)))
+#define W4_PER_PLANE(XI) W4_KIND_SEL(XI, pp0, pp1, pp2, pp3)
+#define W4_NEXT_PLANE(PLANE, XI) { ++PLANE; XI = XI == 35 ? 0 : XI + 1; }
+  const int per_group = 25 * pp0 + 5 * (pp1 + pp2) + pp3;   // items of one group's 36 planes
+  const int total = (planes / 36) * per_group;
   const int S = (total + 7) >> 3;                 // items per XCD slice
   const int xcd = blockIdx.x & 7, jloc = blockIdx.x >> 3, nbl = gridDim.x >> 3;
   const int slice_lo = xcd * S, slice_hi = min(total, slice_lo + S);
@@ -152,8 +164,8 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
 
   // The descriptors span ALL planes and no lane ever relies on the range check: measured on gfx950, a descriptor of one
   // plane's size with the plane offset in soffset returned zeros for every plane but the first (the check evidently
-  // covers voffset + soffset here).  Tile rows beyond NT read the last valid row instead: their products land in
-  // accumulator rows the epilogue never stores.
+  // covers voffset + soffset here).  Tile rows beyond the plane's range [lo, hi) read its last row instead: their products
+  // land in accumulator rows the epilogue never stores.
   const unsigned plane_a_bytes = (unsigned)((size_t)NT * Cin * 4), plane_w_bytes = (unsigned)((size_t)Cout * Cin * 4);
   const v4i srd_a = make_srd(V, (unsigned)planes * plane_a_bytes);
   const v4i srd_w = make_srd(U, (unsigned)planes * plane_w_bytes);
@@ -173,19 +185,25 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
   }
 
   // ---- issue-side state: the item / chunk whose DMA is issued next ----
-  int iss_plane, iss_rem, iss_cc = 0;
+  int iss_plane, iss_xi = 0, iss_rem, iss_cc = 0;
   {
-    iss_plane = first / per_plane;
-    iss_rem = first - iss_plane * per_plane;
+    const int grp = first / per_group;
+    iss_plane = 36 * grp;
+    iss_rem = first - grp * per_group;
+    for (int pp_ = W4_PER_PLANE(iss_xi); iss_rem >= pp_; pp_ = W4_PER_PLANE(iss_xi)) {   // planes without rows are stepped over
+      iss_rem -= pp_;
+      W4_NEXT_PLANE(iss_plane, iss_xi)
+    }
   }
   unsigned l_voff[NPASS];
   unsigned soff_a, soff_w;
 #define W4_ITEM_SETUP()                                                                                  \
   {                                                                                                      \
     const int mt_ = iss_rem >> nt_shift, nt_ = iss_rem & (ntiles - 1);                                   \
+    const int lo_ = iss_xi < 30 ? 0 : lo5, last_ = W4_KIND_SEL(iss_xi, hi0, hi1, hi2, hi3) - 1;          \
     _Pragma("unroll") for (int j = 0; j < NPASS; ++j) {                                                  \
       if (j < NPA) {                                                                                     \
-        const int tau_ = min(mt_ * BM + l_row[j], NT - 1);                                               \
+        const int tau_ = min(lo_ + mt_ * BM + l_row[j], last_);                                          \
         l_voff[j] = (unsigned)((tau_ * Cin + l_c4[j]) * 4);                                              \
       } else {                                                                                           \
         l_voff[j] = (unsigned)(((nt_ * BN + l_row[j]) * Cin + l_c4[j]) * 4);                             \
@@ -211,9 +229,9 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
     if (++iss_cc == cpt) {                                                                               \
       iss_cc = 0;                                                                                        \
       iss_rem += nbl;                                                                                    \
-      while (iss_rem >= per_plane) {                                                                     \
-        iss_rem -= per_plane;                                                                            \
-        ++iss_plane;                                                                                     \
+      for (int pp_ = W4_PER_PLANE(iss_xi); iss_rem >= pp_; pp_ = W4_PER_PLANE(iss_xi)) {                 \
+        iss_rem -= pp_;                                                                                  \
+        W4_NEXT_PLANE(iss_plane, iss_xi)                                                                 \
       }                                                                                                  \
       W4_ITEM_SETUP()                                                                                    \
     } else {                                                                                             \
@@ -243,32 +261,34 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
     for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- compute-side state: the item whose chunks are being multiplied ----
-  int cmp_plane = iss_plane, cmp_rem = iss_rem, cmp_cc = 0;
+  int cmp_plane = iss_plane, cmp_xi = iss_xi, cmp_rem = iss_rem, cmp_cc = 0;
 
   float4 wa0[TN], xb0[TM], wa1[TN], xb1[TM];
   const bool early = NW == 4 || wave < 4;   // NW = 8: waves w and w+4 share a SIMD and issue their DMA bursts at different points
-  auto epilogue = [&]() {   // item complete: store its accumulators into the plane, start the next item from zero
-    cmp_cc = 0;
-    const int mt = cmp_rem >> nt_shift, nt = cmp_rem & (ntiles - 1);
-    float *dst = Mo + (size_t)cmp_plane * NT * Cout;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int co = nt * BN + wn * WN + 16 * j + 4 * q;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int m = mt * BM + wm * WM + 16 * i + t;
-        if (m < NT)   // plain stores: the non-temporal hint here was measured slower (179-181 -> 184-187 us per launch, round 4)
-          *reinterpret_cast<float4 *>(dst + (size_t)m * Cout + co) =
-              make_float4(acc[j][i][0], acc[j][i][1], acc[j][i][2], acc[j][i][3]);
-        acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-    cmp_rem += nbl;
-    while (cmp_rem >= per_plane) {
-      cmp_rem -= per_plane;
-      ++cmp_plane;
-    }
-  };
+  // item complete: store its accumulators into the plane, start the next item from zero
+#define W4_EPILOGUE()                                                                                             \
+  {                                                                                                               \
+    cmp_cc = 0;                                                                                                   \
+    const int mt = cmp_rem >> nt_shift, nt = cmp_rem & (ntiles - 1);                                              \
+    const int lo = cmp_xi < 30 ? 0 : lo5, hi = W4_KIND_SEL(cmp_xi, hi0, hi1, hi2, hi3);                           \
+    float *dst = Mo + (size_t)cmp_plane * NT * Cout;                                                              \
+    _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                              \
+      const int co = nt * BN + wn * WN + 16 * j + 4 * q;                                                          \
+      _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                            \
+        const int m = lo + mt * BM + wm * WM + 16 * i + t;                                                        \
+        /* plain stores: the non-temporal hint here was measured slower (179-181 -> 184-187 us per launch, round 4) */ \
+        if (m < hi)                                                                                               \
+          *reinterpret_cast<float4 *>(dst + (size_t)m * Cout + co) =                                              \
+              make_float4(acc[j][i][0], acc[j][i][1], acc[j][i][2], acc[j][i][3]);                                \
+        acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};                                                                    \
+      }                                                                                                           \
+    }                                                                                                             \
+    cmp_rem += nbl;                                                                                               \
+    for (int pp = W4_PER_PLANE(cmp_xi); cmp_rem >= pp; pp = W4_PER_PLANE(cmp_xi)) {                               \
+      cmp_rem -= pp;                                                                                              \
+      W4_NEXT_PLANE(cmp_plane, cmp_xi)                                                                            \
+    }                                                                                                             \
+  }
   if constexpr (PAIR) {
     W4_ITEM_SETUP()
     W4_ISSUE(0)
@@ -328,7 +348,7 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_sched_barrier(0);
       cmp_cc += 2;
-      if (cmp_cc == cpt) epilogue();
+      if (cmp_cc == cpt) W4_EPILOGUE()
     }
     return;
   }
@@ -378,7 +398,7 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_sched_barrier(0);
-    if (++cmp_cc == cpt) epilogue();
+    if (++cmp_cc == cpt) W4_EPILOGUE()
     const int tmp = s_cur;
     s_cur = s_nxt;
     s_nxt = s_nn;
@@ -389,12 +409,16 @@ __global__ __launch_bounds__(NW * 64) void wino4_gemm_kernel(const float *__rest
 #undef W4_ADVANCE
 #undef W4_FRAG
 #undef W4_MFMA_E
+#undef W4_EPILOGUE
+#undef W4_KIND_SEL
+#undef W4_PER_PLANE
+#undef W4_NEXT_PLANE
 }
 
 template <int BM, int BN, bool PAIR, int NW>
-static int launch_wino4_gemm_t(const float *V, const float *U, float *Mo, int NT, int Cin, int Cout, int planes, int nblocks,
-                               hipStream_t st) {
-  const int mtiles = (NT + BM - 1) / BM, ntiles = Cout / BN;
+static int launch_wino4_gemm_t(const float *V, const float *U, float *Mo, int NT, const Wino4Rows &rows, int Cin, int Cout,
+                               int planes, int nblocks, hipStream_t st) {
+  const int ntiles = Cout / BN;
   int nt_shift = 0;
   while ((1 << nt_shift) < ntiles) ++nt_shift;
   UOC_REQUIRE((1 << nt_shift) == ntiles, "winograd F(4x4): Cout / %d = %d is not a power of two", BN, ntiles);
@@ -405,7 +429,7 @@ static int launch_wino4_gemm_t(const float *V, const float *U, float *Mo, int NT
   static DeviceOnce attr_set;
   if (int rc = opt_in_dynamic_lds(reinterpret_cast<const void *>(&wino4_gemm_kernel<BM, BN, PAIR, NW>), lds, attr_set)) return rc;
   hipLaunchKernelGGL((wino4_gemm_kernel<BM, BN, PAIR, NW>), dim3(nblocks), dim3(NW * 64), lds, st, V, U, Mo, NT, Cin, Cout, planes,
-                     mtiles, nt_shift);
+                     rows, nt_shift);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
@@ -413,10 +437,9 @@ static int launch_wino4_gemm_t(const float *V, const float *U, float *Mo, int NT
 // Tile choice (static cost model, never timing: every candidate sums each output in the same cin order, so the result
 // does not depend on it): steps of the slowest block x tile area, mild preference for large tiles (fewer operand
 // bytes per MFMA).  One block per CU (the 110 KB LDS ring), grid = 8 XCDs x 32.
-// Every (BM, BN) of wino4_gemm_kernel, ONE list, in the order the cost model walks it (the first of equal costs wins); each is
-// instantiated with and without the pair loop.  The dispatch, wino4_tile_list and the tests' single-tile entry come from it.
-#define UOC_W4_TILES(X) \
-  X(96, 128) X(128, 128) X(160, 128) X(192, 128) X(96, 64) X(128, 64) X(160, 64) X(192, 64)
+// The tiles: UOC_W4_TILES (wino4_math.h), each instantiated with and without the pair loop.  The dispatch, wino4_tile_list
+// and the tests' single-tile entry come from that list.  Items are counted per plane kind (wino4_gemm_items): the model, the
+// grid and the kernel agree on the list of items for either plan.
 static const int kW4Tiles[][2] = {
 #define X(A, B) {A, B},
     UOC_W4_TILES(X)
@@ -428,13 +451,13 @@ static int plane_per_xcd() {
   return ncu / 8 > 0 ? ncu / 8 : 1;
 }
 
-void wino4_pick_tile(const int (*tiles)[2], int n, int NT, int Cout, int planes, int &bm, int &bn) {
+void wino4_pick_tile(const int (*tiles)[2], int n, const Wino4Rows &rows, int Cout, int G, int &bm, int &bn) {
   const int per_xcd = plane_per_xcd();
   double best = -1;
   for (int i = 0; i < n; ++i) {
     const int BM = tiles[i][0], BN = tiles[i][1];
     if (Cout % BN) continue;
-    const long items = (long)planes * ((NT + BM - 1) / BM) * (Cout / BN);
+    const long items = wino4_gemm_items(rows, G, BM, Cout / BN);
     const long S = (items + 7) / 8;
     const long steps = (S + per_xcd - 1) / per_xcd;
     const double cost = (double)steps * BM * BN * (1.0 + 0.05 * (192.0 / BM - 1.0)) * (BN == 64 ? 1.06 : 1.0);
@@ -446,25 +469,34 @@ void wino4_pick_tile(const int (*tiles)[2], int n, int NT, int Cout, int planes,
   }
 }
 
+void wino4_pick_tile(const int (*tiles)[2], int n, int NT, int Cout, int planes, int &bm, int &bn) {
+  wino4_pick_tile(tiles, n, wino4_rows_dense(NT), Cout, planes / 36, bm, bn);
+}
+
 // grid of a plane GEMM with tile (bm, bn): every XCD takes an eighth of the items, at most one block per CU
-int wino4_plane_grid(int NT, int Cout, int planes, int bm, int bn) {
+int wino4_plane_grid(const Wino4Rows &rows, int Cout, int G, int bm, int bn) {
   const int per_xcd = plane_per_xcd();
-  const long items = (long)planes * ((NT + bm - 1) / bm) * (Cout / bn);
+  const long items = wino4_gemm_items(rows, G, bm, Cout / bn);
   const long S = (items + 7) / 8;
   return 8 * (int)(S < per_xcd ? S : per_xcd);
 }
 
-static int launch_wino4_gemm(const float *V, const float *U, float *Mo, int NT, int Cin, int Cout, int planes, hipStream_t st,
-                             const W4Tile *tile) {
+int wino4_plane_grid(int NT, int Cout, int planes, int bm, int bn) {
+  return wino4_plane_grid(wino4_rows_dense(NT), Cout, planes / 36, bm, bn);
+}
+
+static int launch_wino4_gemm(const float *V, const float *U, float *Mo, int NT, const Wino4Rows &rows, int Cin, int Cout, int G,
+                             hipStream_t st, const W4Tile *tile) {
+  const int planes = 36 * G;
   int bm = 160, bn = Cout % 128 == 0 ? 128 : 64;
   if (tile) {
     bm = tile->bm;
     bn = tile->bn;
     UOC_REQUIRE((bn == 64 || bn == 128) && Cout % bn == 0, "winograd F(4x4): Cout=%d does not admit BN=%d", Cout, bn);
   } else {
-    wino4_pick_tile(kW4Tiles, (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0])), NT, Cout, planes, bm, bn);
+    wino4_pick_tile(kW4Tiles, (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0])), rows, Cout, G, bm, bn);
   }
-  const int nblocks = wino4_plane_grid(NT, Cout, planes, bm, bn);
+  const int nblocks = wino4_plane_grid(rows, Cout, G, bm, bn);
   // Pair loop (4-stage ring, one barrier per two K-chunks) against the 3-stage ring with one barrier per chunk, per launch shape,
   // same box: layer4 383 -> 377 / 569 -> 551 / 533 -> 516 us, layer3 117.4 -> 115.8 / 165 -> 161 / 150.5 -> 147 us, layer2
   // equal, the 2-chunk items of layer1 45.0 -> 45.6 us (worse: they keep the single-chunk loop); class average 154 -> 151.5 us
@@ -474,8 +506,8 @@ static int launch_wino4_gemm(const float *V, const float *U, float *Mo, int NT, 
   // variant NW = 4 measured 15-25 % slower in round 5, HISTORY.md)
 #define X(A, B)                                                                                                      \
   if (bm == A && bn == B)                                                                                            \
-    return pair ? launch_wino4_gemm_t<A, B, true, 8>(V, U, Mo, NT, Cin, Cout, planes, nblocks, st)                    \
-                : launch_wino4_gemm_t<A, B, false, 8>(V, U, Mo, NT, Cin, Cout, planes, nblocks, st);
+    return pair ? launch_wino4_gemm_t<A, B, true, 8>(V, U, Mo, NT, rows, Cin, Cout, planes, nblocks, st)              \
+                : launch_wino4_gemm_t<A, B, false, 8>(V, U, Mo, NT, rows, Cin, Cout, planes, nblocks, st);
   UOC_W4_TILES(X)
 #undef X
   set_error("winograd F(4x4): no GEMM tile %dx%d", bm, bn);
@@ -492,11 +524,21 @@ int wino4_tile_list(bool split, int *out_pairs, int cap) {
   return n;
 }
 
-void wino4_tile_choice(bool split, int NT, int Cout, int planes, int *bn, int *bm) {
-  if (split) return wino4_split_tile_choice(NT, Cout, planes, bn, bm);
+// The plan a layer runs with: the skipping one, unless the caller names the dense plan (tests, the split-precision GEMM) or
+// every tile is full (H / d and W / d multiples of 4: layer1, layer2) — then the two plans do the same work and the dense one
+// decodes a tile index with less arithmetic.
+static Wino4Geom w4_plan(int B, int H, int W, int d, bool dense) {
+  if (dense) return make_geom4(B, H, W, d);
+  const Wino4Geom geo = make_geom4_skip(B, H, W, d);
+  return geo.n[W4_FF] == geo.NT ? make_geom4(B, H, W, d) : geo;
+}
+
+void wino4_tile_choice(bool split, bool dense, int B, int H, int W, int d, int Cout, int G, int *bn, int *bm) {
+  const Wino4Geom geo = w4_plan(B, H, W, d, dense || split);
+  if (split) return wino4_split_tile_choice(geo.NT, Cout, 36 * G, bn, bm);
   *bm = 160;
   *bn = Cout % 128 == 0 ? 128 : 64;
-  wino4_pick_tile(kW4Tiles, (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0])), NT, Cout, planes, *bm, *bn);
+  wino4_pick_tile(kW4Tiles, (int)(sizeof(kW4Tiles) / sizeof(kW4Tiles[0])), wino4_rows(geo), Cout, G, *bm, *bn);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -539,9 +581,11 @@ long wino4_elem_blocks(long items) {
   return (blocks + 7) / 8 * 8;     // a multiple of 8: the input transform deals its blocks to the XCDs in contiguous eighths
 }
 
-static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st, const W4Tile *tile);
+static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st, const W4Tile *tile,
+                             bool dense);
 
-int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3, const W4Tile *tile) {
+int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_t st, const unsigned short *U3, const W4Tile *tile,
+                      bool dense) {
   UOC_REQUIRE(wino4_eligible(p), "winograd F(4x4): layer not eligible");
   UOC_REQUIRE(U && ws && p.in && p.out, "winograd F(4x4): null tensor/weight/workspace pointer");
   const int planes = 36 * p.G;
@@ -557,11 +601,11 @@ int launch_wino4_conv(const ConvParams &p, const float *U, float *ws, hipStream_
     for (int b0 = 0; b0 < p.B; b0 += bmax) {
       ConvParams q = p;
       q.B = p.B - b0 < bmax ? p.B - b0 : bmax;
-      if (int rc = U3 ? launch_wino4_slice_split(q, p.B, b0, U3, ws, st, tile) : launch_wino4_slice(q, p.B, b0, U, ws, st, tile)) return rc;
+      if (int rc = U3 ? launch_wino4_slice_split(q, p.B, b0, U3, ws, st, tile) : launch_wino4_slice(q, p.B, b0, U, ws, st, tile, dense)) return rc;
     }
     return UOC_OK;
   }
-  return U3 ? launch_wino4_slice_split(p, p.B, 0, U3, ws, st, tile) : launch_wino4_slice(p, p.B, 0, U, ws, st, tile);
+  return U3 ? launch_wino4_slice_split(p, p.B, 0, U3, ws, st, tile) : launch_wino4_slice(p, p.B, 0, U, ws, st, tile, dense);
 }
 
 // ---- the three stages of one layer ---------------------------------------------------------------------------------
@@ -571,45 +615,53 @@ static int w4_stage_input(const ConvParams &p, const Wino4Geom &geo, float *V, h
   const double Mpix = (double)p.B * p.H * p.W;
   const ProfTag tag = {{geo.NT, p.Cin, p.Cout, p.dil}};
   const int vec = w4_vec();
-  ProfScope prof(KC_WINO4_INPUT, st, 0.0, 4.0 * p.G * (Mpix * p.Cin + 36.0 * geo.NT * p.Cin), tag);
-  const long blocks = wino4_elem_blocks((long)p.G * geo.NT * (p.Cin / vec));
-    hipLaunchKernelGGL(wino4_input_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, p.in, V, geo, p.G, p.Cin);
+  // bytes: the activation read once, one V row stored per (plane, tile) pair of the plan
+  ProfScope prof(KC_WINO4_INPUT, st, 0.0, 4.0 * p.G * (Mpix * p.Cin + (double)wino4_plane_pairs(wino4_rows(geo)) * p.Cin), tag);
+  const long blocks = wino4_elem_blocks((long)p.G * geo.end[3] * (p.Cin / vec));
+  if (geo.dense)
+    hipLaunchKernelGGL((wino4_input_kernel<4, 1>), dim3((unsigned)blocks), dim3(256), 0, st, p.in, V, geo, p.G, p.Cin);
+  else
+    hipLaunchKernelGGL((wino4_input_kernel<4, 0>), dim3((unsigned)blocks), dim3(256), 0, st, p.in, V, geo, p.G, p.Cin);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
 
 static int w4_stage_gemm(const ConvParams &p, const Wino4Geom &geo, const float *U, float *V, float *Mw, hipStream_t st,
                          const W4Tile *tile) {
-  const int planes = 36 * p.G;
+  const Wino4Rows rows = wino4_rows(geo);
   const double Mpix = (double)p.B * p.H * p.W;
   const ProfTag tag = {{geo.NT, p.Cin, p.Cout, p.dil}};
   // algorithmic flops = the direct 3x3 convolution's; the matrix pipe executes 36/144 of them
-  // (+ the padding of partial tiles); bytes: V and U read once, M written once
+  // (+ the padding of partial tiles, less the planes they never read); bytes: the plan's rows of V and U read once, of M written once
   const double gflops = 2.0 * Mpix * p.Cout * p.Cin * 9.0 * p.G;
-  const double gbytes = 4.0 * planes * ((double)geo.NT * p.Cin + (double)p.Cout * p.Cin + (double)geo.NT * p.Cout);
+  const double gbytes = 4.0 * p.G * ((double)wino4_plane_pairs(rows) * (p.Cin + p.Cout) + 36.0 * p.Cout * p.Cin);
   ProfScope prof(KC_WINO4_GEMM, st, gflops, gbytes, tag);
-  return launch_wino4_gemm(V, U, Mw, geo.NT, p.Cin, p.Cout, planes, st, tile);
+  return launch_wino4_gemm(V, U, Mw, geo.NT, rows, p.Cin, p.Cout, p.G, st, tile);
 }
 
 int w4_stage_output(const ConvParams &p, const Wino4Geom &geo, const float *Mw, hipStream_t st) {
   const double Mpix = (double)p.B * p.H * p.W;
   const ProfTag tag = {{geo.NT, p.Cin, p.Cout, p.dil}};
   const int vec = w4_vec();
-  ProfScope prof(KC_WINO4_OUTPUT, st, 0.0, 4.0 * p.G * (36.0 * geo.NT * p.Cout + Mpix * p.Cout * (p.res ? 2 : 1)), tag);
-  const long blocks = wino4_elem_blocks((long)p.G * geo.NT * (p.Cout / vec));
-    hipLaunchKernelGGL(wino4_output_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, Mw, p.bias, p.res, p.out, geo, p.G, p.Cout, p.relu);
+  ProfScope prof(KC_WINO4_OUTPUT, st, 0.0, 4.0 * p.G * ((double)wino4_plane_pairs(wino4_rows(geo)) * p.Cout + Mpix * p.Cout * (p.res ? 2 : 1)), tag);
+  const long blocks = wino4_elem_blocks((long)p.G * geo.end[3] * (p.Cout / vec));
+  if (geo.dense)
+    hipLaunchKernelGGL((wino4_output_kernel<4, 1>), dim3((unsigned)blocks), dim3(256), 0, st, Mw, p.bias, p.res, p.out, geo, p.G, p.Cout, p.relu);
+  else
+    hipLaunchKernelGGL((wino4_output_kernel<4, 0>), dim3((unsigned)blocks), dim3(256), 0, st, Mw, p.bias, p.res, p.out, geo, p.G, p.Cout, p.relu);
   UOC_LAUNCH_CHECK();
   return UOC_OK;
 }
 
 // images b0 .. b0 + p.B - 1 of a batch of Bg (activation tensors [g][Bg][H][W][C])
-static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st, const W4Tile *tile) {
+static int launch_wino4_slice(const ConvParams &p0, int Bg, int b0, const float *U, float *ws, hipStream_t st, const W4Tile *tile,
+                             bool dense) {
   ConvParams p = p0;
   const size_t img_in = (size_t)p.H * p.W * p.Cin, img_out = (size_t)p.H * p.W * p.Cout;
   p.in += (size_t)b0 * img_in;
   p.out += (size_t)b0 * img_out;
   if (p.res) p.res += (size_t)b0 * img_out;
-  Wino4Geom geo = make_geom4(p.B, p.H, p.W, p.dil);
+  Wino4Geom geo = w4_plan(p.B, p.H, p.W, p.dil, dense);
   geo.Bg = Bg;
   float *V = ws, *Mw = ws + (size_t)36 * p.G * geo.NT * p.Cin;
   if (int rc = w4_stage_input(p, geo, V, st)) return rc;

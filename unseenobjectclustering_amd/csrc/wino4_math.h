@@ -16,11 +16,43 @@
 
 namespace uoc {
 
+// One image axis of n pixels: d dilation phases of T tiles each.  The first r = n % d phases ("long", index 0 below) hold
+// n / d + 1 pixels, the others ("short", index 1) n / d.  In a phase of h pixels the first h / 4 tiles have all four outputs
+// inside the image (F), one more follows if h % 4 != 0, with its first output inside but not its fourth (P), and the rest
+// of the T tiles have no output inside (E).
+struct Wino4Axis {
+  int r, f[2], p[2];
+};
+
+__host__ __device__ inline Wino4Axis make_axis4(int n, int d) {
+  Wino4Axis a;
+  a.r = n % d;
+  for (int k = 0; k < 2; ++k) {
+    const int h = n / d + 1 - k;
+    a.f[k] = h / 4;
+    a.p[k] = h % 4 != 0;
+  }
+  return a;
+}
+
+// Tile classes by which outputs lie inside the image.  The last interpolation point is the one at infinity: in wino4_at
+// only y[3] reads m[5].  So a tile whose fourth output ROW is outside the image reads no frequency of row i == 5 for an
+// output that is stored, one whose fourth COLUMN is outside none of column j == 5, and one without outputs none at all.
+enum { W4_PF = 0, W4_FF = 1, W4_FP = 2, W4_PP = 3, W4_EMPTY = 4 };   // (fourth row, fourth column) inside: F, outside: P
+
 struct Wino4Geom {
   int B, H, W, d, TH, TW, NT;  // TH x TW tiles of 4x4 outputs per (image, dilation phase); NT = B*d*d*TH*TW
   int Bg;                      // images per group in the activation tensors [g][Bg][H][W][C] (>= B: a launch may cover a slice of the batch)
+  // The plan.  dense: tiles in natural order (image, phase, tile row, tile column), every tile treated as FF.  Otherwise
+  // tiles are ordered by class, [PF | FF | FP | PP | EMPTY], so that the tiles a frequency plane needs are ONE range of
+  // rows (wino4_plane_rows); within a class: image, then the class's rows, then its columns (wino4_decode).
+  int dense;
+  int n[5];     // tiles per class, in the order above (dense: all in FF)
+  int end[4];   // n[0], n[0] + n[1], ... : the end of the four classes that hold outputs; end[3] = tiles with any work
+  Wino4Axis ay, ax;
 };
 
+// the dense plan: what every caller that does not ask for more gets (csrc/wino4_split.hip, tests/csrc/wino4_host_test.cpp)
 __host__ __device__ inline Wino4Geom make_geom4(int B, int H, int W, int d) {
   Wino4Geom g;
   g.B = B;
@@ -31,12 +63,100 @@ __host__ __device__ inline Wino4Geom make_geom4(int B, int H, int W, int d) {
   g.TW = ((W + d - 1) / d + 3) / 4;
   g.NT = B * d * d * g.TH * g.TW;
   g.Bg = B;
+  g.dense = 1;
+  g.ay = make_axis4(H, d);
+  g.ax = make_axis4(W, d);
+  g.n[W4_PF] = g.n[W4_FP] = g.n[W4_PP] = g.n[W4_EMPTY] = 0;
+  g.n[W4_FF] = g.NT;
+  g.end[0] = 0;
+  g.end[1] = g.end[2] = g.end[3] = g.NT;
   return g;
 }
 
+// the skipping plan: class-major tile order, every plane covers only the tiles that read it
+__host__ __device__ inline Wino4Geom make_geom4_skip(int B, int H, int W, int d) {
+  Wino4Geom g = make_geom4(B, H, W, d);
+  g.dense = 0;
+  const int yf = g.ay.r * g.ay.f[0] + (d - g.ay.r) * g.ay.f[1], yp = g.ay.r * g.ay.p[0] + (d - g.ay.r) * g.ay.p[1];
+  const int xf = g.ax.r * g.ax.f[0] + (d - g.ax.r) * g.ax.f[1], xp = g.ax.r * g.ax.p[0] + (d - g.ax.r) * g.ax.p[1];
+  g.n[W4_PF] = B * yp * xf;
+  g.n[W4_FF] = B * yf * xf;
+  g.n[W4_FP] = B * yf * xp;
+  g.n[W4_PP] = B * yp * xp;
+  g.end[0] = g.n[0];
+  for (int c = 1; c < 4; ++c) g.end[c] = g.end[c - 1] + g.n[c];
+  g.n[W4_EMPTY] = g.NT - g.end[3];
+  return g;
+}
+
+// class of tile tau: is its fourth output row / column inside the image (tau < g.end[3]: EMPTY tiles have neither)
+__host__ __device__ inline void wino4_tile_class(int tau, const Wino4Geom &g, bool &row4, bool &col4) {
+  row4 = g.dense || (tau >= g.end[0] && tau < g.end[2]);
+  col4 = g.dense || tau < g.end[1];
+}
+
+// Rows [lo, hi) of the tile order that frequency plane xi = 6*i + j needs, by plane kind = 2*(i == 5) + (j == 5):
+//   kind 0 (25 planes) every tile with an output, 1 (5): PF and FF, 2 (5): FF and FP, 3 (one plane): FF alone
+struct Wino4Rows {
+  int lo5;     // first row of the planes with i == 5 (the others start at 0)
+  int hi[4];   // end row per kind
+};
+
+__host__ __device__ inline Wino4Rows wino4_rows(const Wino4Geom &g) {
+  Wino4Rows r;
+  r.lo5 = g.end[0];
+  r.hi[0] = g.end[3];
+  r.hi[1] = g.end[1];
+  r.hi[2] = g.end[2];
+  r.hi[3] = g.end[1];
+  return r;
+}
+__host__ __device__ inline Wino4Rows wino4_rows_dense(int NT) {
+  Wino4Rows r;
+  r.lo5 = 0;
+  r.hi[0] = r.hi[1] = r.hi[2] = r.hi[3] = NT;
+  return r;
+}
+__host__ __device__ inline int wino4_plane_kind(int xi) { return (xi >= 30 ? 2 : 0) | (int)((0x820820820ull >> xi) & 1); }
+__host__ __device__ inline void wino4_plane_rows(const Wino4Rows &r, int xi, int &lo, int &hi) {
+  const int kind = wino4_plane_kind(xi);
+  lo = kind >= 2 ? r.lo5 : 0;
+  hi = kind == 0 ? r.hi[0] : kind == 1 ? r.hi[1] : kind == 2 ? r.hi[2] : r.hi[3];
+}
+// (plane, tile) pairs of one group that are computed, stored and loaded
+__host__ __device__ inline long wino4_plane_pairs(const Wino4Rows &r) {
+  return 25l * r.hi[0] + 5l * r.hi[1] + 5l * (r.hi[2] - r.lo5) + (r.hi[3] - r.lo5);
+}
+// Every block tile (BM tiles, BN output channels) of the fp32 plane GEMM (wino4_gemm_kernel), ONE list, in the order the
+// cost model walks it (the first of equal costs wins)
+#define UOC_W4_TILES(X) \
+  X(96, 128) X(128, 128) X(160, 128) X(192, 128) X(96, 64) X(128, 64) X(160, 64) X(192, 64)
+// Work items of the plane GEMM over G groups with block tile BM x (Cout / ntiles): a plane has ceil((hi - lo) / BM) * ntiles
+inline long wino4_gemm_items(const Wino4Rows &r, int G, int BM, int ntiles) {
+  const long m0 = (r.hi[0] + BM - 1) / BM, m1 = (r.hi[1] + BM - 1) / BM, m2 = (r.hi[2] - r.lo5 + BM - 1) / BM,
+             m3 = (r.hi[3] - r.lo5 + BM - 1) / BM;
+  return (long)G * ntiles * (25 * m0 + 5 * m1 + 5 * m2 + m3);
+}
+
+// k-th tile of one kind (0: F, 1: P, 2: E) along an axis -> its phase and its index within the phase: the long phases'
+// tiles of the kind come first, then the short phases'.  One division, by the count per phase of whichever part k is in.
+__host__ __device__ inline void w4_axis_decode(const Wino4Axis &a, int kind, int T, int k, int &phase, int &t) {
+  const int nl = kind == 0 ? a.f[0] : kind == 1 ? a.p[0] : T - a.f[0] - a.p[0], ol = kind == 0 ? 0 : kind == 1 ? a.f[0] : a.f[0] + a.p[0];
+  const int ns = kind == 0 ? a.f[1] : kind == 1 ? a.p[1] : T - a.f[1] - a.p[1], os = kind == 0 ? 0 : kind == 1 ? a.f[1] : a.f[1] + a.p[1];
+  const bool lng = k < a.r * nl;
+  const int n = lng ? nl : ns, kk = lng ? k : k - a.r * nl;
+  const int q = kk / n;
+  phase = (lng ? 0 : a.r) + q;
+  t = (lng ? ol : os) + kk - q * n;
+}
+
 // tile index -> image and the first output pixel of the tile; outputs are (oy + a*d, ox + e*d), a, e in 0..3, the
-// input patch is (oy + (i-1)*d, ox + (j-1)*d), i, j in 0..5 (dilation by phase decomposition as in csrc/wino.hip)
-__host__ __device__ inline void wino4_decode(int tau, const Wino4Geom &g, int &b, int &oy, int &ox) {
+// input patch is (oy + (i-1)*d, ox + (j-1)*d), i, j in 0..5 (dilation by phase decomposition as in csrc/wino.hip).
+// The skipping plan decodes with integers that travel in the geometry (no table): class from the four ends, then
+// (image, k-th row of the class's kind, k-th column of its kind), each axis by w4_axis_decode — also where the phase
+// images differ in size (H or W no multiple of d).  EMPTY tiles are the tiles of E rows with any column, then those of F
+// and P rows with E columns; no kernel visits them, so only the host can decode them.
+__host__ __device__ inline void wino4_decode_dense(int tau, const Wino4Geom &g, int &b, int &oy, int &ox) {
   const int tx = tau % g.TW;
   tau /= g.TW;
   const int ty = tau % g.TH;
@@ -47,6 +167,58 @@ __host__ __device__ inline void wino4_decode(int tau, const Wino4Geom &g, int &b
   b = tau / g.d;
   oy = py + 4 * ty * g.d;
   ox = px + 4 * tx * g.d;
+}
+
+__host__ __device__ inline void wino4_decode_skip(int tau, const Wino4Geom &g, int &b, int &oy, int &ox) {
+  const int d = g.d;
+  const int yf = g.ay.r * g.ay.f[0] + (d - g.ay.r) * g.ay.f[1], yp = g.ay.r * g.ay.p[0] + (d - g.ay.r) * g.ay.p[1];
+  const int xf = g.ax.r * g.ax.f[0] + (d - g.ax.r) * g.ax.f[1], xp = g.ax.r * g.ax.p[0] + (d - g.ax.r) * g.ax.p[1];
+  int ky, kx, ny, nx, py, ty, px, tx;
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if (tau >= g.end[3]) {
+    tau -= g.end[3];
+    const int ye = d * g.TH - yf - yp, xall = d * g.TW;
+    if (tau < g.B * ye * xall) {   // E rows, every column in natural order
+      const int xk = tau % xall;
+      tau /= xall;
+      w4_axis_decode(g.ay, 2, g.TH, tau % ye, py, ty);
+      b = tau / ye;
+      oy = py + 4 * ty * d;
+      ox = xk / g.TW + 4 * (xk % g.TW) * d;
+      return;
+    }
+    tau -= g.B * ye * xall;
+    ky = -1;   // F rows, then P rows
+    kx = 2;
+    ny = yf + yp;
+    nx = d * g.TW - xf - xp;
+  } else
+#endif
+  {
+    ky = tau < g.end[0] || tau >= g.end[2];    // PF, PP: P rows
+    kx = tau >= g.end[1];                      // FP, PP: P columns
+    tau -= tau < g.end[0] ? 0 : tau < g.end[1] ? g.end[0] : tau < g.end[2] ? g.end[1] : g.end[2];
+    ny = ky ? yp : yf;
+    nx = kx ? xp : xf;
+  }
+  const int t = tau / nx, xk = tau - t * nx;
+  b = t / ny;
+  int yk = t - b * ny;
+  if (ky < 0) {
+    ky = yk >= yf;
+    if (ky) yk -= yf;
+  }
+  w4_axis_decode(g.ay, ky, g.TH, yk, py, ty);
+  w4_axis_decode(g.ax, kx, g.TW, xk, px, tx);
+  oy = py + 4 * ty * d;
+  ox = px + 4 * tx * d;
+}
+
+__host__ __device__ inline void wino4_decode(int tau, const Wino4Geom &g, int &b, int &oy, int &ox) {
+  if (g.dense)
+    wino4_decode_dense(tau, g, b, oy, ox);
+  else
+    wino4_decode_skip(tau, g, b, oy, ox);
 }
 
 // ---- scalar / float4 arithmetic used by the templates below ----------------------------------------------------
@@ -187,11 +359,21 @@ __host__ __device__ inline void wino4_input_tile(const T (&d)[6][6], T (&v)[36])
 }
 
 // V[(g*36 + xi)][tile][cin] = (B^T d B)[xi] for channels VEC*cv .. VEC*cv+VEC-1 of tile tau; in: [g][Bg][H][W][C]
-template <int VEC>
+// PLAN: the geometry's plan where the caller knows it at compile time (the kernels are instantiated once per plan, so that
+// neither carries the other's decode in its registers): 1 = dense, 0 = skipping; -1 = read geo.dense.  Same arithmetic.
+template <int VEC, int PLAN = -1>
 __host__ __device__ inline void wino4_input_body(const float *in, float *V, const Wino4Geom &geo, int C, int g, int tau, int cv) {
   typedef typename W4Vec<VEC>::type T;
+  const bool dense = PLAN < 0 ? geo.dense != 0 : PLAN == 1;
+  if (!dense && tau >= geo.end[3]) return;   // no output inside the image: no plane reads this tile
   int b, oy, ox;
-  wino4_decode(tau, geo, b, oy, ox);
+  bool row4 = true, col4 = true;
+  if (dense) {
+    wino4_decode_dense(tau, geo, b, oy, ox);
+  } else {
+    wino4_decode_skip(tau, geo, b, oy, ox);
+    wino4_tile_class(tau, geo, row4, col4);
+  }
   const float *src = in + (((size_t)g * geo.Bg + b) * geo.H * geo.W) * C + VEC * cv;
   T d[6][6];
 #pragma unroll
@@ -211,8 +393,10 @@ __host__ __device__ inline void wino4_input_body(const float *in, float *V, cons
   wino4_input_tile(d, v);
   const size_t plane = (size_t)geo.NT * C;
   float *dst = V + (size_t)g * 36 * plane + (size_t)tau * C + VEC * cv;
+  // only the planes the tile's class needs (wino4_plane_rows): the others hold no row for this tile
 #pragma unroll
-  for (int k = 0; k < 36; ++k) W4_STREAM_STORE(T, dst + (size_t)k * plane, v[k]);
+  for (int k = 0; k < 36; ++k)
+    if ((k < 30 || row4) && (k % 6 != 5 || col4)) W4_STREAM_STORE(T, dst + (size_t)k * plane, v[k]);
 }
 
 // y[a][e] = (A^T m A)[a][e] of one tile's 36 frequencies m[6*i + j]  (columns first, then rows)
@@ -233,17 +417,32 @@ __host__ __device__ inline void wino4_output_tile(const T (&m)[36], T (&y)[4][4]
 }
 
 // out[g][b][y][x][cout] = relu?(A^T M A + bias (+ res)) for channels VEC*cv .. of tile tau; M: [(g*36 + xi)][tile][cout]
-template <int VEC>
+template <int VEC, int PLAN = -1>
 __host__ __device__ inline void wino4_output_body(const float *M, const float *bias, const float *res, float *out,
                                                   const Wino4Geom &geo, int Cout, int relu, int g, int tau, int cv) {
   typedef typename W4Vec<VEC>::type T;
+  const bool dense = PLAN < 0 ? geo.dense != 0 : PLAN == 1;
   const size_t plane = (size_t)geo.NT * Cout;
   const float *src = M + (size_t)g * 36 * plane + (size_t)tau * Cout + VEC * cv;
+  if (!dense && tau >= geo.end[3]) return;   // no output inside the image
+  int b, oy, ox;
+  bool row4 = true, col4 = true;
+  if (!dense) {
+    wino4_decode_skip(tau, geo, b, oy, ox);
+    row4 = oy + 3 * geo.d < geo.H;   // = wino4_tile_class, from what the stores below test anyway
+    col4 = ox + 3 * geo.d < geo.W;
+  }
+  // The planes the tile's class does not need were never computed for it: zeros stand in, so that the outputs they reach —
+  // the fourth row / column, which lie outside the image and are not stored — stay finite.
   T m[36];
 #pragma unroll
-  for (int k = 0; k < 36; ++k) m[k] = W4_STREAM_LOAD(T, src + (size_t)k * plane);
-  int b, oy, ox;
-  wino4_decode(tau, geo, b, oy, ox);
+  for (int k = 0; k < 36; ++k) {
+    if ((k < 30 || row4) && (k % 6 != 5 || col4))
+      m[k] = W4_STREAM_LOAD(T, src + (size_t)k * plane);
+    else
+      w4_zero(m[k]);
+  }
+  if (dense) wino4_decode_dense(tau, geo, b, oy, ox);   // after the loads are issued, as the kernel has always done
   const size_t gsz = (size_t)geo.Bg * geo.H * geo.W * Cout;
   const size_t o0 = (size_t)g * gsz + (((size_t)b * geo.H + oy) * geo.W + ox) * Cout + VEC * cv;
   const size_t oy_step = (size_t)geo.d * geo.W * Cout, ox_step = (size_t)geo.d * Cout;
