@@ -72,7 +72,8 @@ int uoc_ms_fps_fallbacks(void);
  * flag: 0, or UOC_ETIMEDOUT.  The host mirrors call it at the points where they synchronise anyway. */
 int uoc_ms_check(void *stream);
 
-/* Scratch bytes the clustering entry points need for (batch, n, m). */
+/* Scratch bytes the clustering entry points need for (batch, n, m).  d_ws of every uoc_ms_* call that takes one is
+ * 256-byte aligned: any other alignment is UOC_EINVAL before any device work. */
 size_t uoc_ms_workspace_bytes(int batch, int n, int m);
 
 /* Farthest-point seed selection — select_smart_seeds, mean_shift.py:128-189.
@@ -183,6 +184,7 @@ size_t uoc_net_workspace_bytes(const uoc_net *net, int B, int H, int W);
  * fp64 evaluation, but they are NOT bit-identical to it.  Call after uoc_net_finalize; on = 1 splits the transformed
  * weights once (hipMalloc + a synchronisation). */
 int uoc_net_set_split_precision(uoc_net *net, int on);
+/* d_ws: uoc_net_workspace_bytes(net, B, H, W) bytes, 256-byte aligned: any other alignment is UOC_EINVAL. */
 int uoc_net_forward(uoc_net *net, const float *d_rgb, const float *d_xyz, int B, int H, int W, float *d_embed,
                     void *d_ws, size_t ws_bytes, void *stream);
 
@@ -255,6 +257,8 @@ typedef struct uoc_roi_table {
   int32_t box[128][4];  /* x0, y0, x1, y1 inclusive, padded 25 % and clamped (:83-93)         */
 } uoc_roi_table;
 
+/* The one workspace of the ROI entry points below (the size does not depend on the frame).  d_ws 16-byte aligned: every
+ * region holds 4-byte words and starts at a multiple of 256 bytes from d_ws. */
 size_t uoc_roi_workspace_bytes(void);
 
 /* Input preparation (read_sample / compute_xyz, tools/test_images.py:96-133) on the device:
@@ -324,6 +328,7 @@ typedef struct uoc_eval_tables {
   int32_t bad_label;           /* != 0: a label id outside [0, 128) was seen (such pixels are skipped)         */
 } uoc_eval_tables;
 
+/* d_ws 256-byte aligned (UOC_EINVAL otherwise; the two regions hold 4-byte words). */
 size_t uoc_eval_workspace_bytes(int H, int W);
 /* d_pred, d_gt: [H][W] int32 label maps (0 = background); radius = bound_pix of boundary_overlap (:88-89),
  * the dilation structuring element is the disk x^2 + y^2 <= radius^2 (:94-98). */
@@ -357,6 +362,7 @@ typedef struct uoc_object {
   int32_t kept;           /* rows of the object in the packed cloud                                              */
 } uoc_object;
 
+/* d_ws 16-byte aligned: its regions hold 8-byte keys and fp64 sums and start at multiples of 256 bytes from d_ws. */
 size_t uoc_objects_workspace_bytes(int B, int H, int W);
 /* d_labels [B][H][W] int32, d_xyz [B][3][H][W] fp32 metres, d_attr (nullable) [B][attr_ch][H][W] fp32 with
  * attr_ch <= UOC_OBJECTS_MAX_ATTR.  d_objects [B][128].
@@ -409,7 +415,9 @@ size_t uoc_track_workspace_bytes(int B);
 int uoc_track_reset(void *d_state, int B, int H, int W, int which, void *stream);
 /* d_labels, d_out [B][H*W] int32 (distinct buffers); q = round(min_iou * 65536) in [1, 65536]; max_age >= 0;
  * d_lut (nullable) [B][128]: raw id -> slot of this step; d_tracks (nullable) [B][128]: the slot table after the step.
- * H*W must be below 2^31.  Three launches on `stream`, nothing synchronises. */
+ * H*W must be below 2^31.  Where d_lut / d_tracks are given, every word of them is written (rows of absent ids and of free
+ * slots are zero): they need no initialisation.  d_state and d_ws 16-byte aligned.  Three launches on `stream`, nothing
+ * synchronises. */
 int uoc_track_step(const int32_t *d_labels, int B, int H, int W, int q, int max_age, void *d_state, int32_t *d_out,
                    int32_t *d_lut, uoc_track *d_tracks, void *d_ws, size_t ws_bytes, void *stream);
 
@@ -1075,7 +1083,9 @@ size_t uoc_ident_workspace_bytes(int B);
 int uoc_ident_reset(void *d_state, int B, int which, void *stream);
 /* d_tracked, d_out [B][H*W] int32 (distinct buffers), H*W below 2^31; d_tracks [B][128]; d_sig [B][128][104]; q = round(min_sim * 65536) in [1, 65536]; r = round(min_size *
  * 256) in [0, 256]; max_lost >= 0; d_lut (nullable) [B][128]: slot -> entry of this step; d_ident (nullable)
- * [B][128][5]: the table after the step.  Two launches on `stream`, nothing synchronises. */
+ * [B][128][5]: the table after the step.  Where d_lut / d_ident are given, every word of them is written (row 0, invisible
+ * slots and free entries are zero): they need no initialisation.  d_state, d_ws and d_sig 16-byte aligned.  Two launches on
+ * `stream`, nothing synchronises. */
 int uoc_ident_step(const int32_t *d_tracked, const uoc_track *d_tracks, const int32_t *d_sig, int B, int H, int W, int q, int r,
                    int max_lost, void *d_state, int32_t *d_out, int32_t *d_lut, int32_t *d_ident, void *d_ws, size_t ws_bytes,
                    void *stream);

@@ -387,14 +387,16 @@ def call(name, device, *args, stream=True):
     check(rc, name)
 
 
-def workspace(name, device, *shape, who, hint):
+def workspace(name, device, *shape, who, hint, floor=0, zero=False):
     """The scratch tensor (uint8, from torch's stream-ordered cache: no allocation in steady state) of the size the
-    *_workspace_bytes function `name` gives for `shape`; a size of 0 is `who`'s NativeError "bad shape <hint>"."""
+    *_workspace_bytes function `name` gives for `shape`; a size of 0 is `who`'s NativeError "bad shape <hint>".
+    floor > 0: at least that many bytes and no error here, the entry point reports a bad shape itself.  zero: zero-filled,
+    for scratch whose contract is "all zero before and after every call"."""
     import torch
     nbytes = getattr(lib(), name)(*shape)
-    if nbytes == 0:
+    if nbytes == 0 and floor == 0:
         raise NativeError(f"{who}: bad shape {hint}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return (torch.zeros if zero else torch.empty)(max(nbytes, floor), dtype=torch.uint8, device=device)
 
 
 def host_words(rows, width):

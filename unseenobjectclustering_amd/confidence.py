@@ -86,7 +86,7 @@ def assign_confidence(X, Z, seed_labels, num_unique=None) -> AssignConfidence:
     labels, second, closest, rival = (torch.empty((B, n), dtype=torch.int32, device=dev) for _ in range(4))
     margin = torch.empty((B, n), dtype=torch.float32, device=dev)
     nws = L.uoc_ms_confidence_workspace_bytes(B, n, m, halves)
-    ws = torch.empty(max(int(nws), 16), dtype=torch.uint8, device=dev)
+    ws = _native.workspace("uoc_ms_confidence_workspace_bytes", dev, B, n, m, halves, who="confidence", hint=f"B={B} n={n} m={m}", floor=16)
     _native.call("uoc_ms_confidence", dev, X, halves, B, n, Z, sl, nu, m, _native.METRIC_COSINE, labels, margin, second, closest,
                  rival, ws, nws)
     return AssignConfidence(labels=labels, margin=margin, second=second, closest=closest, rival=rival)

@@ -21,7 +21,7 @@ namespace uoc {
 constexpr int EL = 128;  // label ids per map
 
 __device__ __forceinline__ unsigned pack_add(unsigned w, int lab) {
-  if (lab <= 0) return w;  // background is never a mask
+  if (lab <= 0 || lab >= EL) return w;  // background is never a mask; an id outside [0, 128) is no mask either (bad_label)
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const unsigned cur = (w >> (8 * k)) & 0xFFu;
@@ -46,6 +46,7 @@ __global__ __launch_bounds__(1024) void eval_stats_kernel(const int *__restrict_
     const int lp = pred[p], lg = gt[p];
     if ((unsigned)lp >= (unsigned)EL || (unsigned)lg >= (unsigned)EL) {
       atomicOr(bad, 1);
+      pk_pred[p] = pk_gt[p] = 0xFFFFFFFFu;  // a skipped pixel has no boundary: the match kernel reads every word of both maps
       continue;
     }
     atomicAdd(&s_cont[lg * EL + lp], 1);

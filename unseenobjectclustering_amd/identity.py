@@ -26,7 +26,9 @@ WORDS = _native.SIG_WORDS
 _HDR, _META, _NF = _native.IDENT_HEADER_WORDS, _native.IDENT_META_WORD, _native.IDENT_WORDS
 
 # the vote accumulators of uoc_signature: zeroed once, every call leaves them zero
-_acc = _native.PerStream(lambda dev, need: torch.zeros(need, dtype=torch.uint8, device=dev), size=lambda t: t.numel())
+_ACC_BYTES = NUM_IDS * WORDS * 4            # per frame: uoc_signature_workspace_bytes(B) = B times this
+_acc = _native.PerStream(lambda dev, B: _native.workspace("uoc_signature_workspace_bytes", dev, B, who="describe", hint=f"B={B}",
+                                                          zero=True), size=lambda t: t.numel() // _ACC_BYTES)
 
 
 class Signatures(_native.Fields):
@@ -98,7 +100,7 @@ def signature_table(labels, image, xyz=None):
     need = _native.lib().uoc_signature_workspace_bytes(B)
     if need == 0:
         raise _native.NativeError(f"describe: bad shape B={B}")
-    acc = _acc.get(dev, need)
+    acc = _acc.get(dev, B)
     sig = torch.empty((B, NUM_IDS, WORDS), dtype=torch.int32, device=dev)
     _native.call("uoc_signature", dev, labels, image, xyz, B, H, W, sig, acc, acc.numel())
     return sig

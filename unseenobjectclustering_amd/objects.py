@@ -38,8 +38,8 @@ class ObjectSet(_native.Fields):
         return self.points[self._offsets_host[k]:self._offsets_host[k + 1]]
 
 
-def _workspace(dev, nbytes):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+def _workspace(dev, B, H, W):
+    return _native.workspace("uoc_objects_workspace_bytes", dev, B, H, W, who="extract_objects", hint=f"B={B} H={H} W={W}", floor=1)
 
 
 def object_records(labels, xyz, attrs=None, max_points_per_object=None, capacity=None, want_points=True):
@@ -57,7 +57,7 @@ def object_records(labels, xyz, attrs=None, max_points_per_object=None, capacity
     pix = torch.empty((cap,), dtype=torch.int32, device=dev) if want_points else None
     total = torch.empty((1,), dtype=torch.int32, device=dev)
     nws = lib.uoc_objects_workspace_bytes(B, H, W)
-    ws = _workspace(dev, nws)
+    ws = _workspace(dev, B, H, W)
     M = 0 if max_points_per_object is None else int(max_points_per_object)
     _native.call("uoc_objects", dev, labels, xyz, attrs, C, B, H, W, M, rec, pts, pat, pix, cap, total, ws, nws)
     return rec, pts, pat, pix, total

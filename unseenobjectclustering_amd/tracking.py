@@ -55,7 +55,7 @@ class Tracker:
             return
         self._state = _native.workspace("uoc_track_state_bytes", dev, B, H, W, who="Tracker", hint=f"B={B} H={H} W={W} (H*W must be below 2^31)")
         self._words = self._state.view(torch.int32).view(B, -1)
-        self._ws = torch.empty(max(_native.lib().uoc_track_workspace_bytes(B), 16), dtype=torch.uint8, device=dev)
+        self._ws = _native.workspace("uoc_track_workspace_bytes", dev, B, who="Tracker", hint=f"B={B}", floor=16)
         self._lut = torch.zeros((B, NUM_SLOTS), dtype=torch.int32, device=dev)
         self._tracks = torch.zeros((B, NUM_SLOTS, _NF), dtype=torch.int32, device=dev)
         self._key = key
