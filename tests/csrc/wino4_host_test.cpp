@@ -19,8 +19,8 @@ static float frand() {  // xorshift, uniform in [-1, 1)
 }
 
 template <int VEC>
-static int run_case(int G, int B, int H, int W, int Cin, int Cout, int d, bool use_res, int relu) {
-  const Wino4Geom geo = make_geom4(B, H, W, d);
+static int run_case(int G, int B, int H, int W, int Cin, int Cout, int d, bool use_res, int relu, bool skip = false) {
+  const Wino4Geom geo = skip ? make_geom4_skip(B, H, W, d) : make_geom4(B, H, W, d);
   std::vector<float> in((size_t)G * B * H * W * Cin), w((size_t)G * 9 * Cout * Cin), bias((size_t)G * Cout),
       res((size_t)G * B * H * W * Cout), out((size_t)G * B * H * W * Cout, -1e30f);
   for (auto &v : in) v = frand();
@@ -70,8 +70,8 @@ static int run_case(int G, int B, int H, int W, int Cin, int Cout, int d, bool u
             if (fabs(acc) > scale) scale = fabs(acc);
           }
   const bool ok = worst < 2e-5 * scale;
-  printf("vec%d G%d B%d %dx%d %d->%d d%d res%d relu%d: tiles %d, max abs err %.3e (scale %.2f) %s\n", VEC, G, B, H, W, Cin, Cout, d,
-         (int)use_res, relu, geo.NT, worst, scale, ok ? "ok" : "FAIL");
+  printf("vec%d G%d B%d %dx%d %d->%d d%d res%d relu%d %s plan: tiles %d, max abs err %.3e (scale %.2f) %s\n", VEC, G, B, H, W, Cin, Cout, d,
+         (int)use_res, relu, skip ? "skipping" : "dense", geo.NT, worst, scale, ok ? "ok" : "FAIL");
   return ok ? 0 : 1;
 }
 

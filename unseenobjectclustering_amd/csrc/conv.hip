@@ -436,8 +436,15 @@ static int pick_bm(int M, int ntiles, int G, int BN, const int *cands, int n) {
   X(3, 64, 64, 1, 4) X(3, 80, 64, 1, 4) X(3, 96, 64, 1, 4)
 static const int kCfgProfClass[kNumCfg] = {KC_GLDS_160x128, KC_GLDS_80x128, KC_GLDS_160x64, KC_GLDS_80x64};
 
-// exactly the instantiation (family cfg, height bm); UOC_EINVAL if the list has no such tile
+// a family serves a layer only if its BN divides Cout: the kernel neither predicates nor clamps its weight rows
+static bool family_admits(int cfg, int Cout) {
+  return cfg >= 0 && cfg < kNumCfg && Cout >= kCfgs[cfg].BN && Cout % kCfgs[cfg].BN == 0;
+}
+
+// exactly the instantiation (family cfg, height bm); UOC_EINVAL if the list has no such tile or the family does not admit Cout
 static int launch_tile(const ConvParams &p, hipStream_t st, int cfg, int bm) {
+  UOC_REQUIRE(cfg >= 0 && cfg < kNumCfg, "conv: no tile family %d", cfg);
+  UOC_REQUIRE(family_admits(cfg, p.Cout), "conv: Cout=%d is not a multiple of the family's BN=%d", p.Cout, kCfgs[cfg].BN);
 #define X(C, BM, BN, WM_, WN_) \
   if (cfg == C && bm == BM) return launch_glds<BM, BN, WM_, WN_, false>(p, st, kCfgProfClass[C]);
   UOC_DIRECT_TILES(X)
@@ -508,12 +515,19 @@ static void tune_cache_load() {
   if (!path) return;
   FILE *f = fopen(path, "r");
   if (!f) return;
-  TuneEntry e;
-  while (g_ntuned < 256 && fscanf(f, "%d %d %d %d %d %d %d %d %d %d %d", &e.key.G, &e.key.B, &e.key.H, &e.key.W,
-                                  &e.key.Cin, &e.key.Cout, &e.key.K, &e.key.stride, &e.key.dil, &e.choice.cfg,
-                                  &e.choice.glds) == 11) {
+  // The file may be stale, edited or cut short: it is read line by line, and a line that is not eleven integers, has a
+  // non-positive dimension or names a family that does not admit its Cout is dropped (the lines after it still count).
+  char line[256];
+  while (g_ntuned < 256 && fgets(line, sizeof line, f)) {
+    TuneEntry e;
+    int end = 0;
+    if (sscanf(line, "%d %d %d %d %d %d %d %d %d %d %d %n", &e.key.G, &e.key.B, &e.key.H, &e.key.W, &e.key.Cin, &e.key.Cout,
+               &e.key.K, &e.key.stride, &e.key.dil, &e.choice.cfg, &e.choice.glds, &end) != 11 || line[end] != '\0')
+      continue;
+    const TuneKey &k = e.key;
+    if (k.G < 1 || k.B < 1 || k.H < 1 || k.W < 1 || k.Cin < 1 || k.Cout < 1 || k.K < 1 || k.stride < 1 || k.dil < 1) continue;
     e.choice.glds = 1;   // a cache written by a development build may name the register-staged kernel
-    if (e.choice.cfg >= 0 && e.choice.cfg < kNumCfg) g_tuned[g_ntuned++] = e;
+    if (family_admits(e.choice.cfg, k.Cout)) g_tuned[g_ntuned++] = e;
   }
   fclose(f);
 }
@@ -543,12 +557,13 @@ static Choice choose(const ConvParams &p, hipStream_t st, int glds_default) {
   int nearest = -1;
   for (int i = 0; i < g_ntuned; ++i) {
     if (!g_tuned[i].key.same_layer(key)) continue;
-    if (g_tuned[i].key.B == key.B) return g_tuned[i].choice;
+    // a stored choice is used only if its family admits this layer (the loader checks too): otherwise the static one
+    if (g_tuned[i].key.B == key.B) return family_admits(g_tuned[i].choice.cfg, p.Cout) ? g_tuned[i].choice : stat;
     if (nearest < 0 || abs(g_tuned[i].key.B - key.B) < abs(g_tuned[nearest].key.B - key.B)) nearest = i;
   }
   if (nearest >= 0) {
     // same layer, other batch: reuse if the tile is still legal, never re-tune mid-stream
-    return g_tuned[nearest].choice;
+    return family_admits(g_tuned[nearest].choice.cfg, p.Cout) ? g_tuned[nearest].choice : stat;
   }
   if (g_ntuned >= 256 || !p.tune || stream_is_capturing(st)) return stat;   // the tuner times launches with events: never inside a capture
   const bool prof_was = g_prof_enabled;
